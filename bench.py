@@ -62,6 +62,45 @@ TICK, STEP_SIZE, SEED = 2, 100_000, 101
 # lets the books fill up, so a run is at most 33 steps (scripts/device_ingress_rate.py is the same stream).
 WORKLOADS["INGRESS"] = (8192, 16, None)
 INGRESS_N, INGRESS_MAX_STEPS = 48, 33
+DUMP_BOOKS, DUMP_BYTES = 4096, 60 << 20  # --dump-outputs: books in the fixed sample, bound on the array bytes (< 64 MB)
+
+
+def dump_sample(n_books):
+    """The fixed, seeded sample of books whose outputs --dump-outputs writes (all of them when there are few)."""
+    return np.sort(np.random.default_rng(0).choice(n_books, size=min(n_books, DUMP_BOOKS), replace=False))
+
+
+def dump_outputs(path, env, books, extra=()):
+    """--dump-outputs: what the timed path's last step handed its caller, as float64 .npy files under `path` (exact for the
+    library's u32 fields and for ids and times below 2**53), so that two builds can be compared output for output.
+      level2       [len(books), 5 + 4L]  the end-of-step level-2 record of every sampled book
+      trade_counts [n_books]             trades so far per book
+      trades       [n, 7]                the last step's trade records of the sampled books: book, t, side, price, vol,
+                                         active_id, passive_id (a seeded sample of the rows if they would pass DUMP_BYTES)
+    `extra`: (name, array) pairs the path adds."""
+    os.makedirs(path, exist_ok=True)
+    out = {"level2": env.level2()[books], "trade_counts": env.trade_counts()}
+    out.update(extra)
+    t_begin = env.time(0) - STEP_SIZE  # every book's clock advances by step_size per step; a step's trades carry t >= its start
+    rows = []
+    for b in books:
+        total, base = env.trade_count(int(b))
+        n = 64
+        while True:  # read the retained records back from the newest until one is older than the last step
+            first = max(base, total - n)
+            a = env.trades(int(b), first=first, n=total - first)
+            if first == base or not len(a) or a["t"][0] < t_begin:
+                break
+            n *= 4
+        a = a[a["t"] >= t_begin]
+        rows.append(np.stack([np.full(len(a), b, np.float64)] + [a[f].astype(np.float64) for f in a.dtype.names], axis=1))
+    trades = np.concatenate(rows) if rows else np.zeros((0, 7))
+    room = (DUMP_BYTES - sum(np.asarray(v).size for v in out.values()) * 8) // (7 * 8)
+    if len(trades) > room:
+        trades = trades[np.sort(np.random.default_rng(1).choice(len(trades), size=max(0, room), replace=False))]
+    out["trades"] = trades
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def algorithmic_bytes(kind, S, W4, ev, tr, new, spl=1, pipe="split", n_ins=0.0):
@@ -190,6 +229,10 @@ def bench_ingress(args, torch):
         raise SystemExit(f"INGRESS: status / capacity flags set ({np.unique(env.flags())}): the rate would be of a run that dropped orders")
     keyed = (float(env.event_steps_keyed().sum()) - keyed0) / (B * K)
     tr_total = int(env.trade_counts().sum())
+    if args.dump_outputs:  # (+ the last step's submit results: every instruction's order id and every book's status)
+        books = dump_sample(B)
+        dump_outputs(args.dump_outputs, env, books, [("order_ids", out_ids.view(B, N).cpu().numpy()[books]),
+                                                     ("status", status.cpu().numpy()[books])])
     env.close()
     # kernel times: the last steps of the same stream on a fresh env, every launch between two events on the env's stream
     P = min(12, K)
@@ -503,7 +546,12 @@ def main():
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="N > 1: seconds a rendezvous / collective may take before it raises")
     ap.add_argument("--rank-timeout", type=float, default=900.0,
                     help="N > 1: seconds after which a rank that has not finished dumps its stacks and exits non-zero (0 = never)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the reported timed region write what its last step computed as DIR/<name>.npy "
+                         "(float64, a fixed sample of books, <= 64 MB), for comparing two builds on identical inputs")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs is a one-GPU option")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))  # nothing has touched torch or the GPU yet
@@ -668,6 +716,8 @@ def main():
     flags = env.flags()
     if flags.any():
         raise SystemExit(f"device flags set during the timed region: {np.unique(flags)} (trade/history capacity?)")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, dump_sample(B))
     n_trades = int(env.trade_counts().sum()) - tc0
     n_new = int(env.order_counts().sum()) - oc0  # orders created = New events of warm-up + timed region (device counters)
     st = env.stats()

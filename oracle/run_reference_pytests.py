@@ -5,8 +5,8 @@ Test infrastructure.  This pins the oracle: the reference's pure-Python half
 (``/root/reference/tests``) are imported from where they lie, with the PyO3
 extension ``bourse.core`` (Rust, unbuildable here) supplied by ``oracle/pyoracle.py``.
 Nothing is copied; ``/root/reference`` does not exist on the GPU box, so this
-script is never part of ``pytest tests/`` -- its result is recorded in DESIGN.md and
-re-checked by ``tests/test_oracle_conformance.py`` only when the reference is present.
+script is never part of ``pytest tests/`` -- its result is recorded in DESIGN.md; run it
+by hand next to a reference checkout (``BOURSE_REFERENCE`` names its directory).
 
 Usage:  python oracle/run_reference_pytests.py [extra pytest args]
 """

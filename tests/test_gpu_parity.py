@@ -840,8 +840,6 @@ KEYED_CASES = {
 @pytest.mark.parametrize("case", sorted(KEYED_CASES))
 def test_keyed_event_loop_window_and_fallback(bk, oracle, case, pipeline):
     c = KEYED_CASES[case]
-    if case == "age" and pipeline == "wave":
-        pytest.skip("one pipeline is enough for the long run")
     n_agents = sum(g[0] for g in c["groups"])
     _compare_random(bk, oracle, n_books=c["n_books"], groups=c["groups"], levels=16, n_steps=c["n_steps"], tick=1,
                     seed=4242, pipeline=pipeline, max_live=max(64, n_agents), trade_cap=n_agents * c["n_steps"])
