@@ -38,49 +38,6 @@
 
 namespace bkd {
 
-// -DBOURSE_AMD_STAMPS=1 (a diagnostic build, never the shipped library): every wave of k_step_batch / k_agents_wave adds
-// the shader-clock length of its phases to g_stamps[kernel * 8 + phase] and its count to [.. + 7]
-// (scripts/wave_phases.py reads them through bk_debug_stamps): where a wave's time goes UNDER the real pipeline's load.
-#ifndef BOURSE_AMD_STAMPS
-#define BOURSE_AMD_STAMPS 0
-#endif
-#if BOURSE_AMD_STAMPS && !defined(BOURSE_AMD_FSM_UNIT)
-// per-book accumulators, [book][kernel * 8 + phase] (plain read-modify-write by lane 0: one wave per book and kernel at a
-// time; contended atomics on a few shared words made the first version of this build 14x slower than the library)
-__device__ unsigned int* g_stamp_ptr;
-#define BK_STAMP_WORDS 24  // per book: k_step_batch's eight, k_agents_wave's eight, the decode's inner phases' eight
-#define BK_STAMP_FIELD    \
-  unsigned long long stamp_t; \
-  unsigned int stamp_book, stamp_t0;
-#define BK_STAMP_START(obj, book)                  \
-  (obj).stamp_t = __builtin_amdgcn_s_memtime(); \
-  (obj).stamp_t0 = (unsigned int)(obj).stamp_t;   \
-  (obj).stamp_book = (book)
-#define BK_STAMP(obj, kernel, phase, lane)                                                           \
-  do {                                                                                               \
-    const unsigned long long n_ = __builtin_amdgcn_s_memtime();                                      \
-    if ((lane) == 0) g_stamp_ptr[(size_t)(obj).stamp_book * BK_STAMP_WORDS + (kernel) * 8 + (phase)] += (unsigned int)(n_ - (obj).stamp_t); \
-    (obj).stamp_t = n_;                                                                              \
-  } while (0)
-// (+ the wave's absolute start / end of its LATEST run, low 32 bits of the clock: words 6 / 2 of k_step_batch's eight, 4 / 5
-// of k_agents_wave's - scripts/wave_phases.py --skew)
-#define BK_STAMP_COUNT(obj, kernel, lane)                                                                       \
-  if ((lane) == 0) {                                                                                            \
-    g_stamp_ptr[(size_t)(obj).stamp_book * BK_STAMP_WORDS + (kernel) * 8 + 7] += 1u;                                        \
-    g_stamp_ptr[(size_t)(obj).stamp_book * BK_STAMP_WORDS + (kernel) * 8 + ((kernel) ? 4 : 6)] = (obj).stamp_t0;            \
-    g_stamp_ptr[(size_t)(obj).stamp_book * BK_STAMP_WORDS + (kernel) * 8 + ((kernel) ? 5 : 2)] = (unsigned int)(obj).stamp_t; \
-  }
-// (diagnostic tallies in the words a run does not stamp: C5 as written leaves 8..23 - the k_agents_wave rows - free)
-#define BK_STAMP_TALLY(obj, word, lane) \
-  if ((lane) == 0) g_stamp_ptr[(size_t)(obj).stamp_book * BK_STAMP_WORDS + (word)] += 1u
-#else
-#define BK_STAMP_TALLY(obj, word, lane)
-#define BK_STAMP_FIELD
-#define BK_STAMP_START(obj, book)
-#define BK_STAMP(obj, kernel, phase, lane)
-#define BK_STAMP_COUNT(obj, kernel, lane)
-#endif
-
 constexpr int HDR_DW = 64;  // per-book header: 64 dwords, lane i holds dword i
 enum Hdr : int {
   H_T_LO = 0, H_T_HI, H_S0_LO, H_S0_HI, H_S1_LO, H_S1_HI,
@@ -372,7 +329,6 @@ struct Book {
   uint32_t tr_k, tr_price, tr_vol, tr_act, tr_pas;
   uint32_t tr_n;  // records buffered
   uint32_t hdr0;  // this lane's header dword as loaded (store_book<KEEP_HDR> rewrites it without reading it again)
-  BK_STAMP_FIELD
 };
 
 template <int R>
@@ -968,7 +924,6 @@ __device__ __forceinline__ bool keys_begin_wide(const Book<R>& B, const uint64_t
 #pragma unroll
   for (int r = 0; r < R; ++r)
     lim[r] = MARKETS ? newm[r] & ~__ballot(B.price[r] == (lane_bit(B.bid[r]) ? 0xFFFFFFFFu : 0u)) : newm[r];
-  BK_STAMP_TALLY(B, 9, lane);  // (diagnostic build: the narrow window failed)
   uint32_t pmax = 0, age = 0, vbig = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -980,10 +935,7 @@ __device__ __forceinline__ bool keys_begin_wide(const Book<R>& B, const uint64_t
   uint32_t dummy = 0xFFFFFFFFu;
   wave_reduce3(pmax, dummy, age);
   vbig = wave_umax(vbig);
-  if (pmax == 0xFFFFFFFFu || pmax < 2u || age + n_ev >= KEY_SMASK - 1u || vbig >= (1u << 22)) {
-    BK_STAMP_TALLY(B, pmax == 0xFFFFFFFFu ? 10 : (age + n_ev >= KEY_SMASK - 1u ? 11 : 12), lane);
-    return false;
-  }
+  if (pmax == 0xFFFFFFFFu || pmax < 2u || age + n_ev >= KEY_SMASK - 1u || vbig >= (1u << 22)) return false;
   const uint32_t pbase = pmax > KEY_PSPAN ? pmax - KEY_PSPAN : 0u, lowp = pbase + 2u;  // in the window: lowp <= price <= pmax
   // this step's listed slots (one event per slot at most): a 512-bit map in LDS
   if (lane < 2 * R) bins[lane] = 0u;
@@ -1017,17 +969,10 @@ __device__ __forceinline__ bool keys_begin_wide(const Book<R>& B, const uint64_t
     // (a market ask's price is 0 <= pbid: counted by the same compare)
     a_ask += (nw && !bidl && B.price[r] <= pbid) ? B.vol[r] : 0u;
   }
-  if (bad) {
-    BK_STAMP_TALLY(B, 13, lane);
-    return false;
-  }
+  if (bad) return false;
   w_bid = wave_add(w_bid);
   a_ask = wave_add(a_ask);
-  if (a_ask > w_bid) {
-    BK_STAMP_TALLY(B, 14, lane);
-    return false;
-  }
-  BK_STAMP_TALLY(B, 15, lane);
+  if (a_ask > w_bid) return false;
   K.pbase = pbase;
   K.sbase = B.seq_ctr - age - 1u;
 #pragma unroll
@@ -1411,14 +1356,12 @@ __device__ __forceinline__ uint32_t step_from_list(Book<R>& B, const DevArgs& a,
   }
   if (!MKT) n_own = n_ev;
   if (MKTK && listed) n_own = own_cnt;
-  BK_STAMP(B, 0, 3, lane);  // key set-up + event loop
   B.n_events += n_own;
   B.t = t0 + step_size;  // env.rs:129
   // env.rs:132-134.  Env::level_2_data (the "latest" record) only needs a launch's final snapshot;
   // with no history buffer every step's record is written there.
   snapshot<R>(B, a, book, lane, bins, hist_slot, B.flags, write_last, tick);
   flush_trades<R>(B, a, book, t0, lane);
-  BK_STAMP(B, 0, 4, lane);  // level-2 snapshot + trade flush
   return (uint32_t)(B.n_trades - trades_before);
 }
 
@@ -1515,9 +1458,6 @@ __global__ __launch_bounds__(256) void k_run_random(DevArgs a, uint64_t first_st
 // ==================================================================================
 enum Phase : uint32_t { PH_ACT = 0, PH_SIDE = 1, PH_TICK = 2, PH_VOL = 3, PH_SHUF = 4, PH_DONE = 5 };
 
-#ifndef BOURSE_AMD_FSM_FREERUN
-#define BOURSE_AMD_FSM_FREERUN 0
-#endif
 #ifndef BOURSE_AMD_FSM_TOP_VGPR
 #define BOURSE_AMD_FSM_TOP_VGPR 231  // highest VGPR k_agents_fsm claims (0 = only what it uses); see the kernel's prologue
 #endif
@@ -1609,13 +1549,7 @@ __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
     // at hand is one register pair per segment, not a per-draw select over the pool's registers (lanes re-converge at
     // a segment's end as they do at a group's; the benchmark groups are 64-aligned: no extra boundary there).
     for (uint32_t sbeg = gend - G.n; sbeg < gend;) {
-#if BOURSE_AMD_FSM_FREERUN
-      // MEASUREMENT BUILD (docs/EXPERIMENTS.md): no re-convergence at the 64-slot segment boundary inside a
-      // group - the live word is selected per lane from the lane's own agent index (2 (R - 1) more vector instructions per draw)
-      const uint32_t send = gend;
-#else
       const uint32_t send = gend < (sbeg | 63u) + 1u ? gend : (sbeg | 63u) + 1u;
-#endif
       uint64_t w = live[0];
 #pragma unroll
       for (int r = 1; r < R; ++r) w = ((sbeg >> 6) == (uint32_t)r) ? live[r] : w;
@@ -1635,14 +1569,7 @@ __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
         // gen::<f32>() < activity_rate (:91-93): (x >> 8) < thr as ONE 64-bit compare x < thr << 8 (thr <= 2^24)
         uint64_t C_HIT = __builtin_amdgcn_ballot_w64((uint64_t)x < thr8);
         uint64_t C_ACC = __builtin_amdgcn_ballot_w64((uint32_t)m <= zone);
-#if BOURSE_AMD_FSM_FREERUN
-        uint64_t wl = live[0];
-#pragma unroll
-        for (int r = 1; r < R; ++r) wl = ((n >> 6) == (uint32_t)r) ? live[r] : wl;
-        uint64_t C_LIVE = __builtin_amdgcn_ballot_w64(((wl >> (n & 63)) & 1ull) != 0);
-#else
         uint64_t C_LIVE = __builtin_amdgcn_ballot_w64(((w >> (n & 63)) & 1ull) != 0);  // Active order held (:95-97)
-#endif
         asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1)
                      : "s"(P_ACT), "s"(P_SIDE), "s"(P_TICK), "s"(P_VOL), "s"(C_HIT), "s"(C_ACC), "s"(C_LIVE));
         rng.advance();
@@ -1756,7 +1683,6 @@ __global__ __launch_bounds__(64, R >= 8 ? 5 : 1) void k_step_batch(DevArgs a, ui
 template <int R, bool MKT, bool POOLPEND>
 __device__ __forceinline__ void step_batch_book(const DevArgs& a, uint32_t book, int lane, uint32_t* lds, uint64_t step_index,
                                                 uint32_t write_last, Book<R>& B, Rng& rng, uint32_t hist_slot) {
-  BK_STAMP_START(B, book);
   StepRaw<R> w;
   const uint32_t mkt_book0 = MKT ? (book / a.assets) * a.assets : book;
   const uint32_t* st = a.state + (size_t)book * a.state_stride;
@@ -1769,13 +1695,7 @@ __device__ __forceinline__ void step_batch_book(const DevArgs& a, uint32_t book,
     w.pv[r] = POOLPEND ? make_uint2(0u, 0u) : reinterpret_cast<const uint2*>(bt + BT_EV + 32 * R)[r * 64 + lane];
   }
   load_state_scalars<R>(w, st);  // (behind the vector loads: its wait hides under their round trip)
-#if BOURSE_AMD_STAMPS && !defined(BOURSE_AMD_FSM_UNIT)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // phase 0 = the loads' round trip
-#endif
-  BK_STAMP(B, 0, 0, lane);
   step_batch_raw<R, MKT, POOLPEND>(a, book, lane, lds, step_index, write_last, w, B, rng, hist_slot);
-  BK_STAMP(B, 0, 5, lane);  // store
-  BK_STAMP_COUNT(B, 0, lane);
 }
 // ... from what load_step_raw / the wrapper above loaded
 template <int R, bool MKT, bool POOLPEND>
@@ -1845,7 +1765,6 @@ __device__ __forceinline__ void step_batch_raw(const DevArgs& a, uint32_t book, 
   }
   B.next_id = base;
   uint32_t n_own = 0;
-  BK_STAMP(B, 0, 1, lane);  // unpack + placing masks + new orders into the pool
   const uint32_t ntr = step_from_list<R, MKT, MKT && POOLPEND, !POOLPEND, POOLPEND && !MKT>(B, a, book, lane, ev, n_ev, lds, hist_slot,
                                                                write_last != 0, MKT ? a.asset_div[asset] : a.tick_div,
                                                                mine, n_own, asset);

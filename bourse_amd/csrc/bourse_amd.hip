@@ -21,6 +21,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bourse_amd.h"
@@ -438,6 +439,18 @@ void launch_timed(bk_env* env, int kind, K kernel, dim3 grid, dim3 block, uint32
   }
 }
 
+// f(std::integral_constant<int, R>{}) for the env's pool registers per book R = 1, 2, 4, anything else 8: the one place a
+// runtime R picks a kernel instantiation
+template <typename F>
+auto by_R(int R, F&& f) {
+  switch (R) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
 template <int R>
 int launch_run(bk_env* env, const DevArgs& a, uint64_t first_step, uint32_t n_steps) {
   const uint32_t blocks = (env->cfg.n_books + 3) / 4;
@@ -660,12 +673,6 @@ int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n
   WaveArgs wva{};
   if (wave)
     if (int rc = wave_args(env, &wva)) return rc;
-  // (diagnostic: BOURSE_AMD_MW_LDS_PAD=bytes of unused dynamic LDS added to every k_agents_mixed_wave workgroup - an occupancy
-  // sensitivity probe: how much does the members' decode lose at FEWER waves per SIMD, i.e. what could more buy?)
-  static const uint32_t mw_pad = [] {
-    const char* e = std::getenv("BOURSE_AMD_MW_LDS_PAD");
-    return e ? static_cast<uint32_t>(std::max(0, std::atoi(e))) & ~3u : 0u;
-  }();
   // (experiment, docs/EXPERIMENTS.md: BOURSE_AMD_STEP_DECODE=1 runs a part's inner steps of the wave_split pipeline as ONE launch
   // each - k_step_decode = events of step s + decode of step s + 1)
   static const bool step_decode = [] {
@@ -673,14 +680,10 @@ int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n
     return e && std::atoi(e) != 0;
   }();
   const bool fuse_sd = step_decode && wave && MIXED == 0 && env->M == 1 && !env->warming;
-  static const uint32_t wave_pad = [] {  // (the same probe for k_agents_wave: BOURSE_AMD_WAVE_LDS_PAD)
-    const char* e = std::getenv("BOURSE_AMD_WAVE_LDS_PAD");
-    return e ? static_cast<uint32_t>(std::max(0, std::atoi(e))) & ~3u : 0u;
-  }();
   if (MIXED == 3) {
     if (!env->mw_attr_set) {  // > 64 KB of dynamic LDS at R = 8 (160 KB per workgroup on MI355X); per device
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_wave<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 static_cast<int>(mixed_wave_lds_bytes(R) + mw_pad)));
+                                 static_cast<int>(mixed_wave_lds_bytes(R))));
       env->mw_attr_set = true;
     }
     if (!env->wl_list.p) {
@@ -742,7 +745,7 @@ int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n
       const uint64_t step_no = first_step + s;
       if (MIXED == 3)
         launch_timed(env, 1, &k_agents_mixed_wave<R>, dim3((nb + MW_WPB - 1) / MW_WPB), dim3(64 * MW_WPB),
-                     static_cast<uint32_t>(mixed_wave_lds_bytes(R)) + mw_pad, st, a, ma, wva,
+                     static_cast<uint32_t>(mixed_wave_lds_bytes(R)), st, a, ma, wva,
                      WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u});
       else if (MIXED == 2 && M > 1)
         launch_timed(env, 1, &k_agents_mixed_lanes<R, true>, dim3((nb + 63) / 64), dim3(64), mixed_lanes_lds_bytes(R, true), st, a,
@@ -755,7 +758,7 @@ int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n
       else if (wave && fuse_sd && s > 0)
         ;  // (the previous step's k_step_decode has decoded this step already)
       else if (wave)
-        launch_timed(env, 1, &k_agents_wave<R>, dim3((nb + 3) / 4), dim3(256), wave_pad, st, a, wva);
+        launch_timed(env, 1, &k_agents_wave<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, wva);
       else
         launch_timed(env, 1, &k_agents_fsm<R>, dim3((nb + 63) / 64), dim3(64), fsm_lds, st, a);
       if (P > 1 && s == 0) HIPCHK(hipEventRecord(env->ev_first[i], st));
@@ -1249,13 +1252,7 @@ int bk_step(bk_env* env) {
   if (total)
     HIPCHK(hipMemcpyAsync(env->ev.p, env->ev_stage, total * sizeof(HostEvent), hipMemcpyHostToDevice, env->stream));
   const DevArgs a = env->args();
-  int rc = BK_OK;
-  switch (env->R) {
-    case 1: rc = launch_events<1>(env, a, env->steps_done, max_queue); break;
-    case 2: rc = launch_events<2>(env, a, env->steps_done, max_queue); break;
-    case 4: rc = launch_events<4>(env, a, env->steps_done, max_queue); break;
-    default: rc = launch_events<8>(env, a, env->steps_done, max_queue); break;
-  }
+  const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, max_queue); });
   if (rc != BK_OK) return rc;
   env->steps_done += 1;
   for (size_t b = 0; b < B; ++b) {
@@ -1505,8 +1502,7 @@ int bk_submit_instructions_host(bk_env* env, const uint64_t* book_offsets, const
   // Large batches in three groups of ~a third of the bytes, each uploaded as soon as it is staged: the link works on group g
   // while the host copies group g + 1 (a caller that fetches the ids before every step - the reference's call shape - waits
   // for copy + upload + k_ingest + download in sequence: 0.25 + 0.2 ms of it at 8 192 books x 48 instructions were these two).
-  const char* one_pass = getenv("BOURSE_AMD_HI_ONE_PASS");  // (=1: stage everything, then upload - for measurements)
-  const bool grouped = n * 27 >= (3u << 20) && !(one_pass && *one_pass == '1');
+  const bool grouped = n * 27 >= (3u << 20);
   if (!grouped) hi_copy(env, segs, 7);
   if (grouped) hi_copy(env, segs + 0, 2);
   HIPCHK(up(h.o_off, (B + 1) * 8));
@@ -1601,15 +1597,9 @@ int bk_step_async(bk_env* env) {
   if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_step_async steps the device-resident queues: call bk_device_ingress_enable first");
   if (int rc = use_device(env)) return rc;
   const DevArgs a = env->args();
-  int rc = BK_OK;
   // (the shuffle permutation's LDS is sized for a full queue: the host does not know the queues' lengths - nothing of this
   // step has been on the host)
-  switch (env->R) {
-    case 1: rc = launch_events<1>(env, a, env->steps_done, env->qcap); break;
-    case 2: rc = launch_events<2>(env, a, env->steps_done, env->qcap); break;
-    case 4: rc = launch_events<4>(env, a, env->steps_done, env->qcap); break;
-    default: rc = launch_events<8>(env, a, env->steps_done, env->qcap); break;
-  }
+  const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, env->qcap); });
   if (rc != BK_OK) return rc;
   HIPCHK(hipMemsetAsync(env->dqlen.p, 0, static_cast<size_t>(env->cfg.n_books / env->M) * 4, env->stream));
   env->steps_done += 1;
@@ -1811,13 +1801,9 @@ static void query_fused_resident(bk_env* env) {
   if (env->fused_resident || !env->wave_ok()) return;
   if (hipSetDevice(env->cfg.device) != hipSuccess) return;
   int blocks = 0, cus = 0;
-  hipError_t e = hipSuccess;
-  switch (env->R) {
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_run_wave<1>, 512, 0); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_run_wave<2>, 512, 0); break;
-    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_run_wave<4>, 512, 0); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_run_wave<8>, 512, 0); break;
-  }
+  hipError_t e = by_R(env->R, [&](auto r) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_run_wave<decltype(r)::value>, 512, 0);
+  });
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->cfg.device);
   if (e == hipSuccess && blocks > 0 && cus > 0) env->fused_resident = static_cast<uint32_t>(blocks) * 8u * static_cast<uint32_t>(cus);
   (void)hipGetLastError();
@@ -1841,7 +1827,6 @@ int bk_run(bk_env* env, uint64_t n_steps) {
     a.groups[0] = Group{};
     a.n_agents_total = 0;
   }
-  int rc = BK_OK;
   const uint32_t ns = static_cast<uint32_t>(n_steps);
   if (env->n_mixed || a.n_groups) env->device_flow = true;
   // Which kernels (bk_env::plan - the rule itself is documented there and in DESIGN.md 2.1):
@@ -1852,38 +1837,22 @@ int bk_run(bk_env* env, uint64_t n_steps) {
   //  * the lane-per-book members' update keeps a filled order's pool slot reserved until its member's next update, so a
   //    pool the wave-per-book kernels just fit can overflow there (flagged): it is only ever taken on request (mode 2) or
   //    for markets, where the other kernels do not exist - nothing of the library's choosing is left to guard.
-#define BK_BY_R(CALL_1, CALL_2, CALL_4, CALL_8) \
-  switch (env->R) {                             \
-    case 1: rc = CALL_1; break;                 \
-    case 2: rc = CALL_2; break;                 \
-    case 4: rc = CALL_4; break;                 \
-    default: rc = CALL_8; break;                \
-  }
-#define BK_SPLIT(MODE) \
-  BK_BY_R((launch_split<1, MODE>(env, a, env->steps_done, ns)), (launch_split<2, MODE>(env, a, env->steps_done, ns)), \
-          (launch_split<4, MODE>(env, a, env->steps_done, ns)), (launch_split<8, MODE>(env, a, env->steps_done, ns)))
-  switch (env->plan().kind) {
-    case bk_env::PL_MIXED_WAVE: BK_SPLIT(3) break;
-    case bk_env::PL_MIXED_LANES: BK_SPLIT(2) break;
-    case bk_env::PL_MIXED_WPB: BK_SPLIT(1) break;
-    case bk_env::PL_MIXED_FUSED:
-      env->ml_valid = false;
-      BK_BY_R(launch_mixed<1>(env, a, env->steps_done, ns), launch_mixed<2>(env, a, env->steps_done, ns),
-              launch_mixed<4>(env, a, env->steps_done, ns), launch_mixed<8>(env, a, env->steps_done, ns))
-      break;
-    case bk_env::PL_FUSED_WAVE:
-      BK_BY_R(launch_wave_fused<1>(env, a, env->steps_done, ns), launch_wave_fused<2>(env, a, env->steps_done, ns),
-              launch_wave_fused<4>(env, a, env->steps_done, ns), launch_wave_fused<8>(env, a, env->steps_done, ns))
-      break;
-    case bk_env::PL_SPLIT_WAVE:
-    case bk_env::PL_SPLIT_LANES: BK_SPLIT(0) break;  // (launch_split<R, 0> takes k_agents_wave when env->use_wave())
-    case bk_env::PL_FUSED_RANDOM:
-      BK_BY_R(launch_run<1>(env, a, env->steps_done, ns), launch_run<2>(env, a, env->steps_done, ns),
-              launch_run<4>(env, a, env->steps_done, ns), launch_run<8>(env, a, env->steps_done, ns))
-      break;
-  }
-#undef BK_SPLIT
-#undef BK_BY_R
+  const int rc = by_R(env->R, [&](auto r) -> int {
+    constexpr int R = decltype(r)::value;
+    switch (env->plan().kind) {
+      case bk_env::PL_MIXED_WAVE: return launch_split<R, 3>(env, a, env->steps_done, ns);
+      case bk_env::PL_MIXED_LANES: return launch_split<R, 2>(env, a, env->steps_done, ns);
+      case bk_env::PL_MIXED_WPB: return launch_split<R, 1>(env, a, env->steps_done, ns);
+      case bk_env::PL_MIXED_FUSED:
+        env->ml_valid = false;
+        return launch_mixed<R>(env, a, env->steps_done, ns);
+      case bk_env::PL_FUSED_WAVE: return launch_wave_fused<R>(env, a, env->steps_done, ns);
+      case bk_env::PL_SPLIT_WAVE:  // (launch_split<R, 0> takes k_agents_wave when env->use_wave())
+      case bk_env::PL_SPLIT_LANES: return launch_split<R, 0>(env, a, env->steps_done, ns);
+      case bk_env::PL_FUSED_RANDOM: return launch_run<R>(env, a, env->steps_done, ns);
+    }
+    return BK_OK;
+  });
   if (rc != BK_OK) return rc;
   env->steps_done += n_steps;
   return BK_OK;
@@ -2652,27 +2621,6 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }
-
-#if BOURSE_AMD_STAMPS
-// diagnostic build only (book_device.hpp BK_STAMP): per-book phase accumulators, BK_STAMP_WORDS u32 per book.
-// bk_debug_stamps(n_books, out): the first call allocates + zeroes them and returns nothing; later calls copy them out
-// (out: n_books * BK_STAMP_WORDS) and zero.
-int bk_debug_stamps(uint32_t n_books, unsigned int* out) {
-  static unsigned int* dev = nullptr;
-  static uint32_t cap = 0;
-  HIPCHK(hipDeviceSynchronize());
-  if (!dev || cap < n_books) {
-    if (dev) (void)hipFree(dev);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dev), static_cast<size_t>(n_books) * BK_STAMP_WORDS * 4));
-    cap = n_books;
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(bkd::g_stamp_ptr), &dev, sizeof(dev)));
-  } else if (out) {
-    HIPCHK(hipMemcpy(out, dev, static_cast<size_t>(n_books) * BK_STAMP_WORDS * 4, hipMemcpyDeviceToHost));
-  }
-  HIPCHK(hipMemset(dev, 0, static_cast<size_t>(cap) * BK_STAMP_WORDS * 4));
-  return BK_OK;
-}
-#endif
 
 // DPP reduction self-test (tests only): in[n_waves*64] -> out[n_waves*4] = {min, max, sum, sel-sum}
 int bk_selftest_reduce(const uint32_t* in_host, uint32_t n_waves, uint32_t* out_host) {

@@ -492,11 +492,6 @@ __device__ __forceinline__ bool step_events_keyed(Book<R>& B, const DevArgs& a, 
   return true;
 }
 
-// timing experiments only (scripts/ev_phase_times.sh): -DBOURSE_AMD_EV_SKIP=bits leaves phases of k_step_events out (results
-// are then wrong): 1 the shuffle's swaps, 2 the order-log writes, 4 matching
-#ifndef BOURSE_AMD_EV_SKIP
-#define BOURSE_AMD_EV_SKIP 0
-#endif
 #ifndef BOURSE_AMD_EV_OCC
 #define BOURSE_AMD_EV_OCC(R) ((R) <= 4 ? 8 : 5)
 #endif
@@ -544,7 +539,7 @@ __global__ __launch_bounds__(64, BOURSE_AMD_EV_OCC_M(R, MODS)) void k_step_event
   const uint32_t e0 = a.ev_len ? mkt * a.ev_stride : a.ev_off[mkt];
   const uint32_t n_ev = a.ev_len ? a.ev_len[mkt] : a.ev_off[mkt + 1] - e0;
   uint32_t n_own = 0;
-  LogCtx lg{(a.order_log && !(BOURSE_AMD_EV_SKIP & 2)) ? a.order_log + (size_t)book * a.log_cap : nullptr, a.log_cap};
+  LogCtx lg{a.order_log ? a.order_log + (size_t)book * a.log_cap : nullptr, a.log_cap};
 
   const uint64_t t0 = B.t;
   B.trade_vol = 0;
@@ -566,13 +561,12 @@ __global__ __launch_bounds__(64, BOURSE_AMD_EV_OCC_M(R, MODS)) void k_step_event
   // table is read from global memory (one block change every few steps), the draws, targets and bucket words use the LDS
   // the keyed form takes over afterwards (a market's books each shuffle their copy of the market's stream, from their own
   // cache record).  Longer queues keep the loop below.
-  const bool wave_shuffle = BOURSE_AMD_EV_WAVE_SHUFFLE && !BOURSE_AMD_EV_SKIP && wa.wcache != nullptr && (MKT || a.assets == 1u) && n_ev >= 2u &&
+  const bool wave_shuffle = BOURSE_AMD_EV_WAVE_SHUFFLE && wa.wcache != nullptr && (MKT || a.assets == 1u) && n_ev >= 2u &&
                             n_ev >= wave_shuffle_min && n_ev <= 64u * R;
   if (wave_shuffle) {
     constexpr uint32_t S = 64u * R;
     uint32_t* wc = wa.wcache + (size_t)book * WC_STRIDE;
     WaveDecoder<R, false> D;
-    BK_STAMP_START(D, book);
     D.tab = wa.jt_block;
     D.evl = perm;
     D.pm = nullptr;
@@ -597,7 +591,7 @@ __global__ __launch_bounds__(64, BOURSE_AMD_EV_OCC_M(R, MODS)) void k_step_event
   } else {
     RngLane v{(uint32_t)rng.s0, (uint32_t)(rng.s0 >> 32), (uint32_t)rng.s1, (uint32_t)(rng.s1 >> 32)};
     asm volatile("" : "+v"(v.a0), "+v"(v.a1), "+v"(v.b0), "+v"(v.b1));  // (uniform values: keep the compiler from moving them back to the scalar unit)
-    for (uint32_t i = (BOURSE_AMD_EV_SKIP & 1) ? 0u : n_ev; i-- > 1;) {
+    for (uint32_t i = n_ev; i-- > 1;) {
       const uint32_t range = i + 1u, zone = (range << __builtin_clz(range)) - 1u;  // UniformInt<u32>::sample_single (App. B.3)
       uint32_t j;
       for (;;) {
@@ -626,10 +620,10 @@ __global__ __launch_bounds__(64, BOURSE_AMD_EV_OCC_M(R, MODS)) void k_step_event
   bool keyed = false;
   uint32_t done = 0;  // events already processed (whole chunks)
   if constexpr (!CHUNKS) {
-    keyed = BOURSE_AMD_EV_KEYED && has_asm && !(BOURSE_AMD_EV_SKIP & ~1) && (MKT || a.assets == 1u) && B.trading && n_ev != 0u && n_ev <= S_ &&
+    keyed = BOURSE_AMD_EV_KEYED && has_asm && (MKT || a.assets == 1u) && B.trading && n_ev != 0u && n_ev <= S_ &&
             step_events_keyed<R, MKT, MODS>(B, a, book, t0, lane, n_ev, e0, perm, perm, lg, asset, n_own, bins);
     done = keyed ? n_ev : 0u;
-  } else if (BOURSE_AMD_EV_KEYED && has_asm && !(BOURSE_AMD_EV_SKIP & ~1) && (MKT || a.assets == 1u) && B.trading && n_ev != 0u &&
+  } else if (BOURSE_AMD_EV_KEYED && has_asm && (MKT || a.assets == 1u) && B.trading && n_ev != 0u &&
              (n_ev <= S_ || 2u * ((n_ev + 63u) & ~63u) + ev_keyed_lds_bytes(R) <= lds_bytes)) {
     uint16_t* wk = n_ev <= S_ ? perm : perm + ((n_ev + 63u) & ~63u);  // (one chunk: the work area takes the permutation's bytes over)
     keyed = true;
@@ -670,7 +664,7 @@ __global__ __launch_bounds__(64, BOURSE_AMD_EV_OCC_M(R, MODS)) void k_step_event
       bool filled = false;
       uint32_t status = 1;  // Active
       uint64_t end = ~0ull;
-      if (B.trading && !(BOURSE_AMD_EV_SKIP & 4)) {
+      if (B.trading) {
         filled = match<R>(B, a, book, t0, lane, k, is_bid, p, v, id, lg);
         if (filled) {
           status = 2;

@@ -179,9 +179,6 @@ __device__ __forceinline__ uint32_t first_above_near(uint64_t lo, uint64_t hi, u
 // slot) is global memory for the split pipeline (the step batch) and LDS for the fused kernel.
 // MASKS: also keep the placing / side masks of the step's new orders (the fused kernel reads them; the split form's
 // k_step_batch rebuilds them from the event words, so its decode does not pay two LDS atomics per placement for them).
-#ifndef BOURSE_AMD_GEN_FAKE
-#define BOURSE_AMD_GEN_FAKE 0
-#endif
 template <int R, bool MASKS = true>
 struct WaveDecoder {
   const uint4* tab;    // LDS: T^256 table
@@ -202,7 +199,6 @@ struct WaveDecoder {
   bool was_cached;     // load_cache found the record valid: finish() then stores the lane states only if the block changed
   uint32_t gen_end;    // draws generated so far (stream origin = start of the cached block)
   uint32_t pos;        // stream position: draws consumed so far
-  BK_STAMP_FIELD
 
   // cached lane states valid for the book's RNG state (s0l..s1h)?  else lane j = T^(4 j) of it, by doubling
   __device__ __forceinline__ void load_cache(const uint32_t* wc, uint32_t s0l, uint32_t s0h, uint32_t s1l, uint32_t s1h,
@@ -245,23 +241,14 @@ struct WaveDecoder {
       // the stream position may still lie in the block being left when the launch ends (look-ahead): its chunk-start
       // states go to the cache record now (a fire-and-forget 1 KB store instead of four live registers)
       wcs[lane] = cs;
-#if BOURSE_AMD_GEN_FAKE  // TIMING EXPERIMENT (results are wrong): what would the decode cost if generation were free?
-      cs.x = cs.x * 0x9E3779B1u + 0x7F4A7C15u; cs.y ^= cs.x >> 7; cs.z += cs.y; cs.w ^= cs.z << 3;
-#else
       cs = wv_jump(tab, cs);
-#endif
     }
     RngLane t{cs.x, cs.y, cs.z, cs.w};
     uint4 x;
-#if BOURSE_AMD_GEN_FAKE >= 2
-    x.x = cs.x * 0x85EBCA6Bu; x.y = (cs.y ^ cs.x) * 0xC2B2AE35u; x.z = (cs.z + cs.x) * 0x27D4EB2Fu; x.w = (cs.w ^ cs.y) * 0x165667B1u;
-    x.x ^= x.x >> 15; x.y ^= x.y >> 13; x.z ^= x.z >> 16; x.w ^= x.w >> 14;
-#else
     x.x = t.next_u32();
     x.y = t.next_u32();
     x.z = t.next_u32();
     x.w = t.next_u32();
-#endif
     reinterpret_cast<uint4*>(ring)[((gen_end >> 2) + lane) & (WV_RING / 4 - 1)] = x;
     gen_end += WV_BLOCK;
     wave_sync();
@@ -285,7 +272,6 @@ struct WaveDecoder {
         // ---- window [w0, w0 + 64) of the stream + 64 draws of look-ahead
         const uint32_t w0 = pos & ~63u;
         ensure(w0 + 128u);
-        BK_STAMP(*this, 2, 0, lane);  // (diagnostic build) generation
         const uint32_t xc = ring[(w0 + lane) & (WV_RING - 1)], xn = ring[(w0 + 64u + lane) & (WV_RING - 1)];
         // p = gen::<f32>() < activity_rate (random_agent.rs:91-93) as an integer threshold (host_math.hpp)
         const uint64_t H = __ballot((xc >> 8) < G.thr);
@@ -329,7 +315,6 @@ struct WaveDecoder {
         uint32_t p = pos - w0;
         uint32_t agw = 0;
         bool slow = false;
-        BK_STAMP(*this, 2, 1, lane);  // the window's masks, searches, placements and continuations
         {
           // to the first hit at or after p (or the end of the window / group)
           const uint64_t m = H >> p;
@@ -413,7 +398,6 @@ struct WaveDecoder {
             }
           }
         }
-        BK_STAMP(*this, 2, 2, lane);  // the walk
         // ---- the window's events, one lane each: list entry and the new order's fields
         {
           const bool acted = (agw & WV_ACTED) != 0, placed = (agw & EV_NEW) != 0;
@@ -462,7 +446,6 @@ struct WaveDecoder {
           p = q - w0;
         }
         pos = w0 + p;
-        BK_STAMP(*this, 2, 3, lane);  // the window's events out (+ the slow path)
       }
     }
     wave_sync();
@@ -514,10 +497,6 @@ struct WaveDecoder {
       // draws consumed: up to the accepted draw that served index 1, else the whole window
       pos = w0 + ((i < 1u && acc) ? (64u - (uint32_t)__builtin_clzll(acc)) : 64u);
     }
-    BK_STAMP(*this, 2, 4, lane);  // the shuffle's draws: acceptance fixed point, swap targets
-#ifdef BOURSE_AMD_SKIP_RESOLUTION  // (timing experiment: the draws and their acceptance only - results are then wrong)
-    return;
-#endif
     if constexpr (R <= 2) {
       // All swap targets j_i are known: resolve the whole Fisher-Yates in parallel instead of n dependent LDS round
       // trips.  Steps run i = n-1 .. 1; the value that ends at position x was at position j_x just before step x, and a
@@ -781,7 +760,6 @@ __device__ __forceinline__ void agents_wave_book(const DevArgs& a, const WaveArg
   uint32_t* wc = wa.wcache + (size_t)book * WC_STRIDE;
 
   WaveDecoder<R, false> D;
-  BK_STAMP_START(D, book);
   D.tab = L.tab;
   D.ring = L.ring[wv];
   D.evl = L.evl[wv];
@@ -813,14 +791,11 @@ __device__ __forceinline__ void agents_wave_book(const DevArgs& a, const WaveArg
     D.load_cache(wc, rdl(hdr, H_S0_LO), rdl(hdr, H_S0_HI), rdl(hdr, H_S1_LO), rdl(hdr, H_S1_HI), wa.jt_lane);
   }
   const uint32_t lim = 64u + (wa.lookahead < 1u ? 1u : (wa.lookahead > 64u ? 64u : wa.lookahead));
-  BK_STAMP(D, 1, 0, lane);  // lane-state cache in
   static_assert(H_LIVE0 == 32, "the live masks are read at byte offset 0x80 above");
   const uint64_t lv0 = R <= 2 ? mk64(hl[0], hl[1]) : 0ull;
   const uint64_t lv1 = R == 2 ? mk64(hl[2], hl[3]) : 0ull;
   const uint32_t n_ev = D.agents(a, lim, hdr, H_LIVE0, lv0, lv1);
-  BK_STAMP(D, 1, 1, lane);  // agents.update: generation, windows, walk
   D.shuffle(n_ev);
-  BK_STAMP(D, 1, 2, lane);  // shuffle
 
   // ---- publish: RNG state, lane-state cache, step batch
   uint32_t n0, n1, n2, n3;
@@ -834,8 +809,6 @@ __device__ __forceinline__ void agents_wave_book(const DevArgs& a, const WaveArg
     const uint32_t lo = 2u * k < n_ev ? D.evl[2u * k] : 0u, hi = 2u * k + 1u < n_ev ? D.evl[2u * k + 1u] : 0u;
     bt[BT_EV + k] = lo | (hi << 16);
   }
-  BK_STAMP(D, 1, 3, lane);  // publish
-  BK_STAMP_COUNT(D, 1, lane);
 }
 
 template <int R>

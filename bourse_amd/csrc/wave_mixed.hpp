@@ -34,11 +34,6 @@
 
 namespace bkd {
 
-// timing experiments only (scripts/mw_phase_times.sh): -DBOURSE_AMD_MW_SKIP=bits leaves phases out (results are then
-// wrong): 1 the shuffle, 2 the traders' windows, 4 the cancel pass, 8 the window's order placement
-#ifndef BOURSE_AMD_MW_SKIP
-#define BOURSE_AMD_MW_SKIP 0
-#endif
 #ifndef BOURSE_AMD_TWO_ROUND
 #define BOURSE_AMD_TWO_ROUND 1
 #endif
@@ -326,7 +321,7 @@ __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixe
     uint16_t* my = wl.list + ((size_t)book * MAX_MEMBERS + j) * wl.cap;
     const uint32_t len = rfl(wl.len[(size_t)book * MAX_MEMBERS + j]);
     uint32_t keep_pos = 0;
-    for (uint32_t c = 0; c < ((BOURSE_AMD_MW_SKIP & 4) ? 0u : len); c += 64u) {
+    for (uint32_t c = 0; c < len; c += 64u) {
       const uint32_t idx = c + (uint32_t)lane;
       const uint32_t slot = idx < len ? (uint32_t)my[idx] : 0u;
       const bool alive = idx < len && ((lvw[(slot >> 5) & 15u] >> (slot & 31u)) & 1u) != 0u;  // else: filled / cancelled meanwhile
@@ -369,7 +364,7 @@ __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixe
       hdr_out = lane == H_GST + 4 * (int)j + 3 ? (uint32_t)(lb >> 32) : hdr_out;
       gflags |= 1u << j;
     }
-    if ((BOURSE_AMD_MW_SKIP & 2) || (!noise && ((thr_l == 0 && thr_m == 0) || sgn == 0))) {
+    if (!noise && ((thr_l == 0 && thr_m == 0) || sgn == 0)) {
       S.pos += 2u * D.n;  // two threshold draws per trader, nobody can act (momentum_agent.rs:165,193)
       S.ensure(S.pos);    // (the position never runs ahead of the generated blocks: finish() locates it in the last two)
       if (lane == 0) wl.len[(size_t)book * MAX_MEMBERS + j] = keep_pos;
@@ -449,7 +444,7 @@ __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixe
       S.pos = rdl(f_end, last);
       if (__ballot(vis && over)) new_flags |= FLAG_DECODE_LOOKAHEAD;
       // ---- the window's orders, all at once.  Limit: place_buy/sell_limit_order (common.rs:92-141)
-      const bool do_a = vis && hit_a && !(BOURSE_AMD_MW_SKIP & 8);
+      const bool do_a = vis && hit_a;
       bool buy_a = sgn > 0, ok_a = false;
       uint32_t price_a = 0;
       const double arg_a = D.mu + D.sigma * zval;
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixe
       }
       ok_a = ok_a || defer_a;
       if (__ballot(do_a && !ok_a)) new_flags |= FLAG_PRICE_TICK;
-      const bool do_b = vis && hit_b && !(BOURSE_AMD_MW_SKIP & 8);
+      const bool do_b = vis && hit_b;
       const bool buy_b = noise ? (S.at(qb + 1u) >> 63) == 0ull : sgn > 0;
       const uint64_t CA = __ballot(do_a && ok_a), CB = __ballot(do_b);
       const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(CA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)CA, 0u)) +
@@ -562,7 +557,7 @@ __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixe
     Dc.pos = S.pos;
     Dc.was_cached = false;  // (finish() always stores the lane states: ~1 500 draws per step cross several blocks)
   }
-  if (!(BOURSE_AMD_MW_SKIP & 1)) Dc.shuffle(n_ev);
+  Dc.shuffle(n_ev);
 
   // ---- publish: RNG state + lane-state cache, member state, ids, cursor, flags; the step batch
   uint32_t n0, n1, n2, n3;

@@ -1,24 +1,22 @@
 # Where k_step_events' HBM traffic goes (17.7 KB measured vs 13.1 KB algorithmic per book-step at 8 192
-# books): FETCH_SIZE / WRITE_SIZE passes of `bench.py --workload INGRESS` with the two suspects toggled -
-#   the wave-parallel shuffle's lane-state record (BOURSE_AMD_EV_SEQ_SHUFFLE=1: draw by draw, no record) and
-#   the order log (a -DBOURSE_AMD_EV_SKIP=2 build: no log writes; build_variants/libbourse_amd_nolog.so, built in the container).
+# books): FETCH_SIZE / WRITE_SIZE passes of `bench.py --workload INGRESS` with and without the wave-parallel shuffle's
+#   lane-state record (BOURSE_AMD_EV_SEQ_SHUFFLE=1: draw by draw, no record).
 # GPU box:  bash scripts/pmc_step_events.sh [books] [extra bench args]   -> gpurun_out/pmc_step_events/summary_<books>.txt
 R=${GRAFT_REPO_ROOT:-/root/repo}; B=${1:-8192}; shift || true; XA="$*"
 OUT=$R/gpurun_out/pmc_step_events; mkdir -p $OUT; cd /tmp && export TMPDIR=/tmp
 PA="--workload INGRESS --books $B --steps 24 --warmup 6 --no-cpu-baseline --preheat-steps 0 $XA"
-for V in shipped noshuf nolog noshuf_nolog; do
-  unset BOURSE_AMD_EV_SEQ_SHUFFLE BOURSE_AMD_LIBRARY
-  case $V in noshuf*) export BOURSE_AMD_EV_SEQ_SHUFFLE=1;; esac
-  case $V in *nolog) export BOURSE_AMD_LIBRARY=$R/build_variants/libbourse_amd_nolog.so;; esac
+for V in shipped noshuf; do
+  unset BOURSE_AMD_EV_SEQ_SHUFFLE
+  case $V in noshuf) export BOURSE_AMD_EV_SEQ_SHUFFLE=1;; esac
   for C in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $C -d $OUT/${V}_$C -o p -f csv -- python3 $R/bench.py $PA > $OUT/${V}_$C.json 2> $OUT/${V}_$C.err
   done
 done
-unset BOURSE_AMD_EV_SEQ_SHUFFLE BOURSE_AMD_LIBRARY
+unset BOURSE_AMD_EV_SEQ_SHUFFLE
 python3 - <<PY | tee $OUT/summary_$B.txt
 import collections, csv, glob, json
 print("k_step_events / k_ingest HBM traffic per book-step at $B books (rocprofv3 --pmc FETCH_SIZE x 2 [gfx950] + WRITE_SIZE, KiB -> B), bench args: $PA")
-for v in ("shipped", "noshuf", "nolog", "noshuf_nolog"):
+for v in ("shipped", "noshuf"):
     tot = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(lambda: collections.defaultdict(float))
     for c in ("FETCH_SIZE", "WRITE_SIZE"):
         for f in glob.glob("$OUT/%s_%s/**/*counter_collection.csv" % (v, c), recursive=True):
