@@ -3,7 +3,8 @@
 // Host side of the drop-in boundary: owns the device state of B independent books, keeps the
 // host-visible half of `bourse_de::Env` (order creation, id assignment, the per-step event
 // queue — crates/step_sim/src/env.rs:166-219) and launches the step kernels.  There is no CPU
-// execution path: without a usable GPU every entry point fails with BK_NO_DEVICE.
+// execution path: without a usable GPU every entry point fails with BK_NO_DEVICE.  Which kernels a bk_run launches is
+// decided in pipeline_plan.hpp (make_plan); the launch code here only follows that plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +36,7 @@ extern template __global__ void k_agents_fsm<8>(DevArgs);
 }  // namespace bkd
 #include "host_math.hpp"
 #include "host_pool.hpp"
+#include "pipeline_plan.hpp"
 #include "mixed_agents.hpp"
 #include "wave_agents.hpp"
 #include "wave_mixed.hpp"
@@ -71,30 +73,6 @@ uint64_t fnv1a(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
     if (_e != hipSuccess)                                                                         \
       return fail(BK_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(_e));               \
   } while (0)
-
-// AgentSets of Noise / Momentum members on independent books: from this many books the members' update runs one WAVE per
-// book with the stream decoded 64 draws at a time (k_agents_mixed_wave, wave_mixed.hpp) in front of the event kernel
-constexpr uint32_t MIXED_WAVE_MIN_BOOKS = 512;
-// The auto rule for RandomAgents books, derived from the SHAPE (pool registers R = pool / 64) instead of a book count
-// swept at one shape (scripts/shape_sweep.py, profiles/r03/shape_sweep.txt: C2 R = 1, C3 R = 2, a 256-slot pool R = 4,
-// C5 R = 8, 1 024 .. 65 536 books):
-//   * `wave` (k_run_wave: decode + events fused, book in registers across the launch) while the batch fits the chip in
-//     ONE residency round of that kernel - asked of the runtime (hipOccupancyMaxActiveBlocksPerMultiprocessor x 8 books
-//     per workgroup x CUs: 6 144 books at R <= 2, 4 096 at R = 4, 2 048 at R = 8); one book more and a second round at a
-//     fraction of the occupancy costs more than the split form's launches (C3: 103 M at 6 144, 94 M at 7 168 books).
-//     64-slot pools are the exception: their book-step is so short that the persistent kernel wins up to the lane split's
-//     take-over (C2: 195 M vs 170 M at 8 192, 216 vs 206 at 16 384);
-//   * `wave_split` (k_agents_wave + k_step_batch, three parts) from there;
-//   * `split` (lane-per-book k_agents_fsm + k_step_batch, four parts) from lane_split_min_books(R): its 125 us chain
-//     per step needs that many books to be hidden.  Crossovers re-measured at the end of round 4, after the decode and
-//     both event loops got faster (profiles/r04/shape_sweep_crossovers.txt, twice: the second sweep after the decode's last
-//     trims and the event waves' priority rule): 26 k / 26.4 - 27.9 k (two boxes) / 25.3 k / 26.5 k books for R = 1, 2, 4, 8 (round 3: 23 k /
-//     24.5 k / 18 k / 24.5 k - the 256-slot pools' wave_split gained most: 53 -> 76 M).
-// behind the wave-parallel decode the event waves run at priority 1 from this many books (book_device.hpp k_step_batch).  Re-swept
-// at the end of round 4: pools of <= 128 slots gain from 8 192 books now (132.5 -> 135.3 M there, +1 % at 12 288; round 3: -2 %
-// at 8 192), the 512-slot pools still lose below 16 384 (C5 stand-in 32.0 -> 31.4 M at 8 192)
-constexpr uint32_t wave_step_prio_books(int R) { return R <= 2 ? 8192u : 16384u; }
-constexpr uint32_t lane_split_min_books(int R) { return R == 4 ? 25600u : (R == 2 ? 27648u : 26624u); }
 
 struct HostOrder {  // immutable half of an order, fixed at create_order (orderbook.rs:356-396)
   uint8_t bid;
@@ -145,83 +123,22 @@ struct bk_env {
   HostEvent* ev_stage = nullptr;  // pinned staging of the same (uploaded at link speed)
   uint32_t* off_stage = nullptr;
   uint32_t batch_stride = 0;
-  // 0 auto, 1 fused (k_run_random), 2 split (k_agents_fsm + k_step_batch), 3 split with wave-per-book AgentSet members,
-  // 4 wave_split (k_agents_wave + k_step_batch), 5 wave (k_run_wave: wave-parallel decode + events, persistent)
-  int pipeline = 0;
+  int pipeline = 0;  // the caller's request, 0 auto .. 5 (pipeline_plan.hpp PlanInput::request)
   DevBuf<uint32_t> warm_snap;         // bk_warm: state + L2 copy of the scratch steps
   bool warming = false;               // bk_warm's scratch steps: no history slots, no trade records
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
   uint32_t wave_lookahead = 64;
   uint32_t stagger_us = ~0u;    // parts of a split launch start i x stagger_us apart; ~0 = default rule, 0 = by events
-  int wave_parts = 0;           // 0 = as the lane split (n_parts / min_part)
-  bool wave_ok() const { return !n_mixed && M == 1 && !groups.empty(); }  // RandomAgents on independent books
+  int wave_parts = 0;           // bk_set_wave_options: 0 = by the rule (pipeline_plan.hpp wave_parts)
   // AgentSets with Noise / Momentum members on independent books: wave-parallel decode of the members' update
   bool wl_valid = false;    // the wave-per-book members' lists (wl_list) describe the pools as of steps_done
   DevBuf<uint16_t> wl_list;    // [n_books][MAX_MEMBERS][pool]: k_agents_mixed_wave's lists, book-major
   DevBuf<uint32_t> wl_len;
   bool mw_attr_set = false;
-  bool use_mixed_wave() const {
-    return n_mixed && M == 1 &&
-           (pipeline == 4 || (pipeline == 0 && cfg.n_books >= MIXED_WAVE_MIN_BOOKS));
-  }
   uint32_t fused_resident = 0;   // books one residency round of k_run_wave<R> holds on this device (0 = not asked yet)
-  uint32_t wave_fused_max() const {
-    if (R == 1) return lane_split_min_books(1) - 1u;
-    const uint32_t res = fused_resident ? fused_resident : (R == 8 ? 2048u : 6144u);
-    // (256-slot pools: a round holds 6 144 books like the 128-slot ones, but the split form is already ahead at 5 120 -
-    // 37.7 vs 33.8 M - and level at 4 096)
-    // (512-slot pools: two workgroups per CU fit since round 4 - 4 096 books - but the split form is 4 % ahead there: 25.4 vs 24.4 M)
-    return R >= 8 ? std::min(res, 2048u) : (R >= 4 ? std::min(res, 4096u) : res);
-  }
-  bool use_wave() const {        // split form: k_agents_wave + k_step_batch
-    return wave_ok() && (pipeline == 4 || (pipeline == 0 && cfg.n_books > wave_fused_max() && cfg.n_books < lane_split_min_books(R)));
-  }
-  bool use_wave_fused() const {  // persistent fused form: k_run_wave
-    return wave_ok() && (pipeline == 5 || (pipeline == 0 && cfg.n_books <= wave_fused_max()));
-  }
-  int wave_split_parts() const {
-    if (wave_parts > 0)  // set explicitly (tests, sweeps): any batch of >= 64 books per part
-      return static_cast<int>(std::max(1u, std::min(static_cast<uint32_t>(wave_parts), cfg.n_books / 64u)));
-    // One part per hardware queue (four) once a part holds 2 048 books.  Re-swept in round 4, after the event loops got
-    // faster (scripts/exp_c5p.sh): C5 as written 32.3 / 32.8 / 34.0 / 21.9 M in 2 / 3 / 4 / 5 parts (round 3: two parts), C5
-    // stand-in 26.1 / 27.0 / 19.3 M in 3 / 4 / 5, the C3 shards 116.7 / 117.7 M (8 192 books) and 140.0 / 139.7 M (16 384) in
-    // 3 / 4; a fifth part shares a queue and halves the rate.
-    return static_cast<int>(std::max(1u, std::min(4u, cfg.n_books / 2048u)));
-  }
-  // THE pipeline choice: the one function bk_run launches from and bk_get_pipeline reports from (they duplicated the rule
-  // until round 4).  `pipeline` is the caller's request (0 auto); a request the env's agents cannot take (e.g. "wave" for
-  // a market) falls back as the comments say.
-  enum PlanKind {
-    PL_FUSED_RANDOM,  // k_run_random: one wave per book, all phases, n_steps per launch (also: no agents = plain steps)
-    PL_FUSED_WAVE,    // k_run_wave: wave-parallel decode + events, persistent
-    PL_SPLIT_LANES,   // k_agents_fsm (one lane per book / market) + k_step_batch
-    PL_SPLIT_WAVE,    // k_agents_wave (one wave per book, stream decoded 64 draws at a time) + k_step_batch
-    PL_MIXED_FUSED,   // k_run_mixed: AgentSet members, fused
-    PL_MIXED_WAVE,    // k_agents_mixed_wave + k_step_batch<POOLPEND>
-    PL_MIXED_LANES,   // k_agents_mixed_lanes + k_step_batch<POOLPEND> (markets' only pipeline; on request otherwise)
-    PL_MIXED_WPB,     // k_agents_mixed (one wave per book, scalar) + k_step_batch<POOLPEND> (mode 3, on request)
-  };
-  struct Plan {
-    PlanKind kind;
-    int parts;
-  };
-  Plan plan() const {
-    if (n_mixed) {
-      if (use_mixed_wave()) return {PL_MIXED_WAVE, wave_split_parts()};
-      if (pipeline == 2 || M > 1) return {PL_MIXED_LANES, parts()};
-      if (pipeline == 3) return {PL_MIXED_WPB, parts()};
-      return {PL_MIXED_FUSED, 1};
-    }
-    if (use_wave_fused()) return {PL_FUSED_WAVE, 1};
-    if (use_wave()) return {PL_SPLIT_WAVE, wave_split_parts()};
-    // (auto with RandomAgents on independent books never gets here below lane_split_min_books: the wave forms take it)
-    if ((pipeline >= 2 && pipeline != 5) || M > 1 || (pipeline == 0 && wave_ok())) return {PL_SPLIT_LANES, parts()};
-    return {PL_FUSED_RANDOM, 1};
-  }
-  // split pipeline: the batch is cut into n_parts contiguous parts, each on its own stream and started one
-  // k_agents_fsm apart, so the latency-bound lane-per-book kernel of one part runs under the issue-bound
-  // wave-per-book kernel of another.
+  bool step_decode = false;      // BOURSE_AMD_STEP_DECODE (pipeline_plan.hpp)
+  // split pipeline geometry (pipeline_plan.hpp lane_parts)
   int n_parts = 4;  // one per hardware queue (part_streams)
   uint32_t min_part = 4096;  // books (markets) per part below which the batch is cut in fewer parts
   static constexpr int MAX_PARTS = 8;
@@ -244,10 +161,6 @@ struct bk_env {
   bool ml_valid = false;  // the lists describe the pool as of steps_done (false after a wave-per-book launch / restore)
   uint32_t member_asset[MAX_MEMBERS] = {0, 0, 0, 0};
   uint32_t n_fixed_a[MAX_ASSETS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int parts() const {
-    const uint32_t units = cfg.n_books / M;
-    return static_cast<int>(std::max(1u, std::min(static_cast<uint32_t>(n_parts), units / min_part)));
-  }
   MixedLists lists() const {
     return MixedLists{ml_list.p, ml_len.p, ml_inl.p, static_cast<uint32_t>(R) * 64u, cfg.n_books, cfg.n_books / M};
   }
@@ -451,15 +364,6 @@ auto by_R(int R, F&& f) {
   }
 }
 
-template <int R>
-int launch_run(bk_env* env, const DevArgs& a, uint64_t first_step, uint32_t n_steps) {
-  const uint32_t blocks = (env->cfg.n_books + 3) / 4;
-  env->prof_now = env->profile > 0;
-  ProfScope ps(env, 0);
-  hipLaunchKernelGGL(k_run_random<R>, dim3(blocks), dim3(256), 0, env->stream, a, first_step, n_steps);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
-}
 int wave_args(bk_env* env, WaveArgs* wva);
 template <int R>
 int launch_events(bk_env* env, const DevArgs& a, uint64_t step_index, uint32_t max_queue) {
@@ -512,18 +416,6 @@ int launch_events(bk_env* env, const DevArgs& a, uint64_t step_index, uint32_t m
   return BK_OK;
 }
 
-template <int R>
-int launch_mixed(bk_env* env, const DevArgs& a, uint64_t first_step, uint32_t n_steps) {
-  const uint32_t blocks = (env->cfg.n_books + 3) / 4;
-  env->prof_now = env->profile > 0;
-  ProfScope ps(env, 0);
-  const MixedArgs ma = env->margs();
-  env->wl_valid = false;  // (the wave-per-book lists no longer describe the pools)
-  hipLaunchKernelGGL(k_run_mixed<R>, dim3(blocks), dim3(256), 0, env->stream, a, ma, first_step, n_steps);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
-}
-
 // jump tables (T^256, then T^(4 << b)) and the per-book lane-state cache of the wave-parallel decode, on first use
 int wave_args(bk_env* env, WaveArgs* wva) {
   if (!env->jump_tabs.p) {
@@ -543,17 +435,6 @@ int wave_args(bk_env* env, WaveArgs* wva) {
   wva->jt_lane = env->jump_tabs.p + 512;
   wva->wcache = env->wcache.p;
   wva->lookahead = env->wave_lookahead;
-  return BK_OK;
-}
-
-template <int R>
-int launch_wave_fused(bk_env* env, const DevArgs& a, uint64_t first_step, uint32_t n_steps) {
-  WaveArgs wva{};
-  if (int rc = wave_args(env, &wva)) return rc;
-  env->prof_now = env->profile > 0;
-  ProfScope ps(env, 0);
-  hipLaunchKernelGGL(k_run_wave<R>, dim3((env->cfg.n_books + 7) / 8), dim3(512), 0, env->stream, a, wva, first_step, n_steps);
-  HIPCHK(hipGetLastError());
   return BK_OK;
 }
 
@@ -631,91 +512,117 @@ const std::vector<hipStream_t>& part_streams(int device) {
   return pool.emplace(device, std::move(chosen)).first->second;
 }
 
-// split pipeline: per step and per part one lane-per-book launch (RNG-serial phases) + one wave-per-book launch
-// MIXED: 0 RandomAgents groups (k_agents_fsm), 1 AgentSet members one wave per book (k_agents_mixed), 2 members one lane
-// per book (k_agents_mixed_lanes)
-template <int R, int MIXED = 0>
-int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n_steps) {
-  const MixedArgs ma = env->margs();
-  const uint32_t fsm_lds = fsm_lds_bytes(R);
-  if (MIXED == 0 && !env->fsm_attr_set) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_fsm<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(fsm_lds)));
-    env->fsm_attr_set = true;
-  }
-  if (MIXED == 2) {
-    const size_t NB = env->cfg.n_books, cap = static_cast<size_t>(R) * 64, NU = NB / env->M;
-    if (!env->ml_list.p) {
-      HIPCHK(env->ml_list.alloc(MAX_MEMBERS * cap * NU));
-      HIPCHK(env->ml_len.alloc(MAX_MEMBERS * NU));
-      HIPCHK(env->ml_inl.alloc(2 * static_cast<size_t>(R) * NB));
+// The per-kind set-up of a bk_run launch: dynamic-LDS attributes, the members' lists (allocated on first use, rebuilt from
+// the owner tags when another pipeline changed the pools) and which of them still describe the pools, the wave decode's tables
+template <int R>
+int prepare_launch(bk_env* env, const Plan& pl, const DevArgs& a0, WaveArgs* wva) {
+  switch (pl.kind) {
+    case PL_FUSED_RANDOM: break;
+    case PL_SPLIT_LANES:
+    case PL_SPLIT_WAVE:
+      if (!env->fsm_attr_set) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_fsm<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(fsm_lds_bytes(R))));
+        env->fsm_attr_set = true;
+      }
+      if (pl.kind == PL_SPLIT_WAVE) return wave_args(env, wva);
+      break;
+    case PL_FUSED_WAVE: return wave_args(env, wva);
+    case PL_MIXED_LANES: {
+      const size_t NB = env->cfg.n_books, cap = static_cast<size_t>(R) * 64, NU = NB / env->M;
+      if (!env->ml_list.p) {
+        HIPCHK(env->ml_list.alloc(MAX_MEMBERS * cap * NU));
+        HIPCHK(env->ml_len.alloc(MAX_MEMBERS * NU));
+        HIPCHK(env->ml_inl.alloc(2 * static_cast<size_t>(R) * NB));
+        env->ml_valid = false;
+      }
+      if (!env->lds_attr_set) {  // allow > 64 KB of dynamic LDS (160 KB per workgroup on MI355X); the attribute is per device
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, true))));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, false))));
+        env->lds_attr_set = true;
+      }
+      if (!env->ml_valid) {
+        hipLaunchKernelGGL(k_mixed_lists_rebuild<R>, dim3((env->cfg.n_books + 3) / 4), dim3(256), 0, env->stream, a0, env->margs(),
+                           env->lists());
+        HIPCHK(hipGetLastError());
+        env->ml_valid = true;
+      }
+      env->wl_valid = false;  // (the wave-per-book lists no longer describe the pools)
+      break;
+    }
+    case PL_MIXED_WPB:
+    case PL_MIXED_FUSED:
       env->ml_valid = false;
-    }
-    if (!env->lds_attr_set) {  // allow > 64 KB of dynamic LDS (160 KB per workgroup on MI355X); the attribute is per device
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, true))));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, false))));
-      env->lds_attr_set = true;
-    }
-    if (!env->ml_valid) {
-      hipLaunchKernelGGL(k_mixed_lists_rebuild<R>, dim3((env->cfg.n_books + 3) / 4), dim3(256), 0, env->stream, a0, ma,
-                         env->lists());
-      HIPCHK(hipGetLastError());
-      env->ml_valid = true;
-    }
-  } else if (MIXED == 1) {
-    env->ml_valid = false;
-  }
-  if (MIXED == 1 || MIXED == 2) env->wl_valid = false;  // (the wave-per-book lists no longer describe the pools)
-  const MixedLists ml = env->lists();
-  const bool wave = (MIXED == 0 && env->use_wave()) || MIXED == 3;
-  WaveArgs wva{};
-  if (wave)
-    if (int rc = wave_args(env, &wva)) return rc;
-  // (experiment, docs/EXPERIMENTS.md: BOURSE_AMD_STEP_DECODE=1 runs a part's inner steps of the wave_split pipeline as ONE launch
-  // each - k_step_decode = events of step s + decode of step s + 1)
-  static const bool step_decode = [] {
-    const char* e = std::getenv("BOURSE_AMD_STEP_DECODE");
-    return e && std::atoi(e) != 0;
-  }();
-  const bool fuse_sd = step_decode && wave && MIXED == 0 && env->M == 1 && !env->warming;
-  if (MIXED == 3) {
-    if (!env->mw_attr_set) {  // > 64 KB of dynamic LDS at R = 8 (160 KB per workgroup on MI355X); per device
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_wave<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 static_cast<int>(mixed_wave_lds_bytes(R))));
-      env->mw_attr_set = true;
-    }
-    if (!env->wl_list.p) {
-      HIPCHK(env->wl_list.alloc(static_cast<size_t>(env->cfg.n_books) * MAX_MEMBERS * R * 64));
-      HIPCHK(env->wl_len.alloc(static_cast<size_t>(env->cfg.n_books) * MAX_MEMBERS));
       env->wl_valid = false;
-    }
-    if (!env->wl_valid) {  // another pipeline (or a restore / a fresh env) changed the pools: lists from the owner tags
-      hipLaunchKernelGGL(k_wave_lists_rebuild<R>, dim3((env->cfg.n_books + 3) / 4), dim3(256), 0, env->stream, a0, ma,
-                         WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u});
-      HIPCHK(hipGetLastError());
-      env->wl_valid = true;
-    }
-    env->ml_valid = false;
+      break;
+    case PL_MIXED_WAVE:
+      if (int rc = wave_args(env, wva)) return rc;
+      if (!env->mw_attr_set) {  // > 64 KB of dynamic LDS at R = 8 (160 KB per workgroup on MI355X); per device
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_wave<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(mixed_wave_lds_bytes(R))));
+        env->mw_attr_set = true;
+      }
+      if (!env->wl_list.p) {
+        HIPCHK(env->wl_list.alloc(static_cast<size_t>(env->cfg.n_books) * MAX_MEMBERS * R * 64));
+        HIPCHK(env->wl_len.alloc(static_cast<size_t>(env->cfg.n_books) * MAX_MEMBERS));
+        env->wl_valid = false;
+      }
+      if (!env->wl_valid) {  // another pipeline (or a restore / a fresh env) changed the pools: lists from the owner tags
+        hipLaunchKernelGGL(k_wave_lists_rebuild<R>, dim3((env->cfg.n_books + 3) / 4), dim3(256), 0, env->stream, a0, env->margs(),
+                           WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u});
+        HIPCHK(hipGetLastError());
+        env->wl_valid = true;
+      }
+      env->ml_valid = false;
+      break;
   }
+  return BK_OK;
+}
+
+// The streams and fork / join events of a multi-part launch, on first use
+int prepare_parts(bk_env* env) {
+  if (env->ev_fork) return BK_OK;
+  const std::vector<hipStream_t>& ps = part_streams(env->cfg.device);
+  if (ps.empty()) return fail(BK_HIP_ERROR, "could not create the parts' streams");
+  for (int i = 0; i < bk_env::MAX_PARTS; ++i) {
+    env->part_stream[i] = ps[static_cast<size_t>(i) % ps.size()];  // more parts than queues: they share
+    if (!env->ev_first[i]) HIPCHK(hipEventCreateWithFlags(&env->ev_first[i], hipEventDisableTiming));
+    if (!env->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&env->ev_join[i], hipEventDisableTiming));
+  }
+  // last: ev_fork doubles as "the parts' streams and events are set up" (a failure above leaves it unset, so the
+  // next bk_run tries again instead of launching on null streams)
+  HIPCHK(hipEventCreateWithFlags(&env->ev_fork, hipEventDisableTiming));
+  return BK_OK;
+}
+
+// fused kinds: all n_steps in one launch on the env's stream
+template <int R>
+int launch_fused(bk_env* env, const Plan& pl, const DevArgs& a, const WaveArgs& wva, uint64_t first_step, uint32_t n_steps) {
+  const uint32_t nb = env->cfg.n_books;
+  env->prof_now = env->profile > 0;
+  ProfScope ps(env, 0);
+  if (pl.kind == PL_MIXED_FUSED)
+    hipLaunchKernelGGL(k_run_mixed<R>, dim3((nb + 3) / 4), dim3(256), 0, env->stream, a, env->margs(), first_step, n_steps);
+  else if (pl.kind == PL_FUSED_WAVE)
+    hipLaunchKernelGGL(k_run_wave<R>, dim3((nb + 7) / 8), dim3(512), 0, env->stream, a, wva, first_step, n_steps);
+  else
+    hipLaunchKernelGGL(k_run_random<R>, dim3((nb + 3) / 4), dim3(256), 0, env->stream, a, first_step, n_steps);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+// split kinds: per step and per part one agents launch (the RNG-serial phases) + one wave-per-book event launch
+template <int R>
+int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs& wva, uint64_t first_step, uint32_t n_steps) {
+  const MixedArgs ma = env->margs();
+  const MixedLists ml = env->lists();
   const uint32_t M = env->M;
   const uint32_t B = env->cfg.n_books / M;  // units the parts are cut in: books, or markets of M books
-  // small batches: one part on the caller's stream
-  const int P = wave ? env->wave_split_parts() : env->parts();
-  if (P > 1 && !env->ev_fork) {
-    const std::vector<hipStream_t>& ps = part_streams(env->cfg.device);
-    if (ps.empty()) return fail(BK_HIP_ERROR, "could not create the parts' streams");
-    for (int i = 0; i < bk_env::MAX_PARTS; ++i) {
-      env->part_stream[i] = ps[static_cast<size_t>(i) % ps.size()];  // more parts than queues: they share
-      if (!env->ev_first[i]) HIPCHK(hipEventCreateWithFlags(&env->ev_first[i], hipEventDisableTiming));
-      if (!env->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&env->ev_join[i], hipEventDisableTiming));
-    }
-    // last: ev_fork doubles as "the parts' streams and events are set up" (a failure above leaves it unset, so the
-    // next bk_run tries again instead of launching on null streams)
-    HIPCHK(hipEventCreateWithFlags(&env->ev_fork, hipEventDisableTiming));
-  }
+  const int P = pl.parts;  // (small batches: one part on the caller's stream)
   if (P > 1) {
+    if (int rc = prepare_parts(env)) return rc;
     HIPCHK(hipEventRecord(env->ev_fork, env->stream));
     for (int i = 0; i < P; ++i) HIPCHK(hipStreamWaitEvent(env->part_stream[i], env->ev_fork, 0));
   }
@@ -726,54 +633,45 @@ int launch_split(bk_env* env, const DevArgs& a0, uint64_t first_step, uint32_t n
       a.book_begin = static_cast<uint32_t>(static_cast<uint64_t>(B) * i / P) & ~3u;
       a.book_end = (i + 1 == P) ? B : (static_cast<uint32_t>(static_cast<uint64_t>(B) * (i + 1) / P) & ~3u);
       a.hist_slot0 = a.hist_cap ? static_cast<uint32_t>((first_step + s) % a.hist_cap) : 0u;
-      a.step_prio = (wave && B >= wave_step_prio_books(R)) ? 1u : 0u;
+      a.step_prio = pl.step_prio ? 1u : 0u;
       const uint32_t nb = a.book_end - a.book_begin;
       hipStream_t st = P > 1 ? env->part_stream[i] : env->stream;
-      if (P > 1 && s == 0 && i > 0) {  // stagger the parts
-        // by time: i x stagger_us.  The lane split's parts cycle through a ~180 us agents kernel and a ~140 us event
-        // kernel; one agents kernel apart (the round-1 rule) puts part 2 at 360 us = almost in phase with part 0 again.
-        // Measured at C3 (driver's 20-step regions): 60 us apart 186-189 M first region / 199-201 M later ones against
-        // 182 / 192-195 M (BOURSE_AMD_STAGGER_US overrides; other pipelines keep the event-based stagger)
-        // (round 3, 20-step regions, first / median of five: 0 us 226 / 229 M, 20 us 240 / 246, 35 us 238 / 244, 50 us 241 / 242,
-        // 70 us 235 / 238; no difference over 200 steps)
-        const uint32_t stagger = env->stagger_us != ~0u ? env->stagger_us : ((MIXED == 0 && !wave && P >= 3) ? 30u : 0u);
-        if (stagger > 0)
-          hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, st, static_cast<uint32_t>(i) * stagger * 100u);
-        else                           // by one agents kernel each
+      if (P > 1 && s == 0 && i > 0) {  // stagger the parts: by time, or by one agents kernel each
+        if (pl.stagger_us > 0)
+          hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, st, static_cast<uint32_t>(i) * pl.stagger_us * 100u);
+        else
           HIPCHK(hipStreamWaitEvent(st, env->ev_first[i - 1], 0));
       }
       const uint64_t step_no = first_step + s;
-      if (MIXED == 3)
+      if (pl.agents == AG_MIXED_WAVE)
         launch_timed(env, 1, &k_agents_mixed_wave<R>, dim3((nb + MW_WPB - 1) / MW_WPB), dim3(64 * MW_WPB),
                      static_cast<uint32_t>(mixed_wave_lds_bytes(R)), st, a, ma, wva,
                      WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u});
-      else if (MIXED == 2 && M > 1)
+      else if (pl.agents == AG_MIXED_LANES_MKT)
         launch_timed(env, 1, &k_agents_mixed_lanes<R, true>, dim3((nb + 63) / 64), dim3(64), mixed_lanes_lds_bytes(R, true), st, a,
                      ma, ml);
-      else if (MIXED == 2)
+      else if (pl.agents == AG_MIXED_LANES)
         launch_timed(env, 1, &k_agents_mixed_lanes<R, false>, dim3((nb + 63) / 64), dim3(64), mixed_lanes_lds_bytes(R, false), st,
                      a, ma, ml);
-      else if (MIXED == 1)
+      else if (pl.agents == AG_MIXED_WPB)
         launch_timed(env, 1, &k_agents_mixed<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, ma);
-      else if (wave && fuse_sd && s > 0)
+      else if (pl.agents == AG_WAVE && pl.step_decode && s > 0)
         ;  // (the previous step's k_step_decode has decoded this step already)
-      else if (wave)
+      else if (pl.agents == AG_WAVE)
         launch_timed(env, 1, &k_agents_wave<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, wva);
       else
-        launch_timed(env, 1, &k_agents_fsm<R>, dim3((nb + 63) / 64), dim3(64), fsm_lds, st, a);
+        launch_timed(env, 1, &k_agents_fsm<R>, dim3((nb + 63) / 64), dim3(64), fsm_lds_bytes(R), st, a);
       if (P > 1 && s == 0) HIPCHK(hipEventRecord(env->ev_first[i], st));
-      // the lane-per-book members' update reads the touches from the latest level-2 record: keep it current
-      const uint32_t write_last = (s + 1 == n_steps || a.hist_cap == 0 || MIXED >= 2) ? 1u : 0u;
-      if (MIXED && M > 1)
+      const uint32_t write_last = (s + 1 == n_steps || a.hist_cap == 0 || pl.write_last) ? 1u : 0u;
+      if (pl.step_poolpend && pl.step_mkt)
         launch_timed(env, 2, &k_step_batch<R, true, true>, dim3(nb * M), dim3(64), 0u, st, a, step_no, write_last);
-      else if (MIXED)
+      else if (pl.step_poolpend)
         launch_timed(env, 2, &k_step_batch<R, false, true>, dim3(nb), dim3(64), 0u, st, a, step_no, write_last);
-      else if (M > 1)
+      else if (pl.step_mkt)
         launch_timed(env, 2, &k_step_batch<R, true>, dim3(nb * M), dim3(64), 0u, st, a, step_no, write_last);
-      else if (fuse_sd && s + 1 < n_steps) {
-        DevArgs an = a;  // (the decode half belongs to the NEXT step; nothing in it reads the history slot)
-        launch_timed(env, 2, &k_step_decode<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, an, wva, step_no, write_last);
-      } else
+      else if (pl.step_decode && s + 1 < n_steps)  // (the decode half belongs to the NEXT step; nothing in it reads the history slot)
+        launch_timed(env, 2, &k_step_decode<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, wva, step_no, write_last);
+      else
         launch_timed(env, 2, &k_step_batch<R, false>, dim3(nb), dim3(64), 0u, st, a, step_no, write_last);
     }
   }
@@ -976,6 +874,7 @@ int bk_env_create(const bk_config* cfg, bk_env** out) {
   if (const char* sq = std::getenv("BOURSE_AMD_EV_SEQ_SHUFFLE")) env->ev_seq_shuffle = *sq == '1';
   if (const char* sm = std::getenv("BOURSE_AMD_EV_WAVE_SHUFFLE_MIN")) env->ev_shuffle_min = std::atoi(sm);
   if (const char* su = std::getenv("BOURSE_AMD_STAGGER_US")) env->stagger_us = static_cast<uint32_t>(std::max(0, std::atoi(su)));
+  if (const char* sd = std::getenv("BOURSE_AMD_STEP_DECODE")) env->step_decode = std::atoi(sd) != 0;
   if (const char* mp = std::getenv("BOURSE_AMD_MIN_PART")) {
     const int v = std::atoi(mp);
     if (v >= 64) env->min_part = static_cast<uint32_t>(v);
@@ -1798,7 +1697,6 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
 
 // books one residency round of the fused wave kernel holds (the auto rule's `wave` limit): asked of the runtime once
 static void query_fused_resident(bk_env* env) {
-  if (env->fused_resident || !env->wave_ok()) return;
   if (hipSetDevice(env->cfg.device) != hipSuccess) return;
   int blocks = 0, cus = 0;
   hipError_t e = by_R(env->R, [&](auto r) {
@@ -1812,10 +1710,21 @@ static void query_fused_resident(bk_env* env) {
             env->fused_resident);
 }
 
+// THE pipeline choice (pipeline_plan.hpp): bk_run launches from it, bk_get_pipeline reports it
+static Plan env_plan(bk_env* env) {
+  PlanInput in{env->R, env->cfg.n_books, env->M, !env->groups.empty(), env->n_mixed, env->pipeline, env->n_parts, env->wave_parts,
+               env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode};
+  if (!in.fused_resident && random_books(in)) {
+    query_fused_resident(env);
+    in.fused_resident = env->fused_resident;
+  }
+  return make_plan(in);
+}
+
 int bk_run(bk_env* env, uint64_t n_steps) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (n_steps == 0) return BK_OK;
-  query_fused_resident(env);
+  const Plan pl = env_plan(env);
   if (n_steps > 0xFFFFFFFFull) return fail(BK_INVALID_ARGUMENT, "n_steps too large for one launch");
   if (int rc = use_device(env)) return rc;
   if (env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_run cannot be mixed with submitted instructions on the same env");
@@ -1829,7 +1738,7 @@ int bk_run(bk_env* env, uint64_t n_steps) {
   }
   const uint32_t ns = static_cast<uint32_t>(n_steps);
   if (env->n_mixed || a.n_groups) env->device_flow = true;
-  // Which kernels (bk_env::plan - the rule itself is documented there and in DESIGN.md 2.1):
+  // Which kernels (pipeline_plan.hpp - the rule itself is documented there and in DESIGN.md 2.1):
   //  * the fused kernels keep a book in registers across all steps of the launch but run the RNG-serial phases on the
   //    scalar unit of ONE wave per book; the split forms move them to one lane per book (>= 64 books per wave to pay off)
   //    or decode the stream wave-parallel, in front of the lean event kernel, the batch cut in parts that overlap;
@@ -1839,19 +1748,10 @@ int bk_run(bk_env* env, uint64_t n_steps) {
   //    for markets, where the other kernels do not exist - nothing of the library's choosing is left to guard.
   const int rc = by_R(env->R, [&](auto r) -> int {
     constexpr int R = decltype(r)::value;
-    switch (env->plan().kind) {
-      case bk_env::PL_MIXED_WAVE: return launch_split<R, 3>(env, a, env->steps_done, ns);
-      case bk_env::PL_MIXED_LANES: return launch_split<R, 2>(env, a, env->steps_done, ns);
-      case bk_env::PL_MIXED_WPB: return launch_split<R, 1>(env, a, env->steps_done, ns);
-      case bk_env::PL_MIXED_FUSED:
-        env->ml_valid = false;
-        return launch_mixed<R>(env, a, env->steps_done, ns);
-      case bk_env::PL_FUSED_WAVE: return launch_wave_fused<R>(env, a, env->steps_done, ns);
-      case bk_env::PL_SPLIT_WAVE:  // (launch_split<R, 0> takes k_agents_wave when env->use_wave())
-      case bk_env::PL_SPLIT_LANES: return launch_split<R, 0>(env, a, env->steps_done, ns);
-      case bk_env::PL_FUSED_RANDOM: return launch_run<R>(env, a, env->steps_done, ns);
-    }
-    return BK_OK;
+    WaveArgs wva{};
+    if (int rc = prepare_launch<R>(env, pl, a, &wva)) return rc;
+    return is_split(pl.kind) ? launch_split<R>(env, pl, a, wva, env->steps_done, ns)
+                             : launch_fused<R>(env, pl, a, wva, env->steps_done, ns);
   });
   if (rc != BK_OK) return rc;
   env->steps_done += n_steps;
@@ -2472,20 +2372,11 @@ int bk_profile_read_kind(bk_env* env, int kind, double* total_ms, uint64_t* n_la
 
 int bk_get_pipeline(bk_env* env, int* split, int* n_parts) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
-  query_fused_resident(env);
-  const bk_env::Plan pl = env->plan();  // the same function bk_run launches from
-  int code = 0;
-  switch (pl.kind) {
-    case bk_env::PL_FUSED_RANDOM:
-    case bk_env::PL_MIXED_FUSED: code = 0; break;
-    case bk_env::PL_SPLIT_LANES:
-    case bk_env::PL_MIXED_LANES:
-    case bk_env::PL_MIXED_WPB: code = 1; break;
-    case bk_env::PL_SPLIT_WAVE:
-    case bk_env::PL_MIXED_WAVE: code = 2; break;
-    case bk_env::PL_FUSED_WAVE: code = 3; break;
-  }
-  if (split) *split = code;
+  const Plan pl = env_plan(env);  // the same plan bk_run launches from
+  // by PlanKind: 0 fused, 1 split (lane-per-book agents), 2 wave_split, 3 wave
+  static constexpr int code[] = {0, 3, 1, 2, 0, 2, 1, 1};
+  static_assert(PL_MIXED_WPB == 7, "one code per PlanKind");
+  if (split) *split = code[pl.kind];
   if (n_parts) *n_parts = pl.parts;
   return BK_OK;
 }
