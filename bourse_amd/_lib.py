@@ -154,6 +154,7 @@ SIGNATURES = {
     "bk_clear_flags": (_i32, [_vp, _u32]),
     "bk_flags_summary": (_i32, [_vp, _p32, _p64]),
     "bk_warm": (_i32, [_vp, _u64]),
+    "bk_set_agent_order_log": (_i32, [_vp, _i32]),
     "bk_rng_state": (_i32, [_vp, _u32, _p64]),
     "bk_live_orders": (_i32, [_vp, _u32, _u32, _vp, _p32]),
     "bk_stats_compute": (_i32, [_vp, C.POINTER(Stats)]),

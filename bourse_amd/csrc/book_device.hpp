@@ -441,7 +441,7 @@ __device__ __forceinline__ void flush_trades_compact(Book<R>& B, const DevArgs& 
 }
 
 // ----------------------------------------------------------------------------------
-// order log (host-driven path only): single-lane scattered 32-byte updates
+// order log (host-driven path; on-device agents through k_step_batch_log): single-lane scattered 32-byte updates
 // ----------------------------------------------------------------------------------
 struct LogCtx {
   DevOrderLog* base;  // this book's log or nullptr
@@ -576,12 +576,20 @@ __device__ __forceinline__ bool match(Book<R>& B, const DevArgs& a, uint32_t boo
 // survive between stages (scalar instructions are the scarce resource of this kernel).
 // CLS: the event word itself says New / Cancellation and the side (`ew`, k_agents_fsm's lists); otherwise the slot's
 // pend and side masks do.
-template <int R, int RS, bool CLS = false>
+// LOG (k_step_batch_log, `lg` = the book's order log, one LogCtx): every change of an order is written to the log as
+// k_step_events writes it (step_events.hpp) - the placement with its status and key, each passive fill, a Cancellation of
+// an order still Active.  (The log rides in a parameter pack that is empty without LOG: the other kernels' code stays as
+// it is.)
+template <int R, int RS, bool CLS = false, bool LOG = false, class... Lg>
 __device__ __forceinline__ void slot_event_at(Book<R>& B, const DevArgs& a, uint32_t book, uint64_t t0, int lane,
-                                              uint32_t k, uint32_t sl, uint32_t ew = 0) {
+                                              uint32_t k, uint32_t sl, uint32_t ew = 0, const Lg&... lg) {
   const LogCtx nolog{nullptr, 0};
   const uint64_t bit = 1ull << sl;
   if (CLS ? !(ew & EV_NEW) : !(B.pend[RS] & bit)) {
+    if constexpr (LOG) {
+      if (B.live[RS] & bit)  // (the order was filled meanwhile: nothing changes, orderbook.rs:622-644)
+        log_write(lg..., B.flags, lane, rdl(B.id[RS], sl), 3, rdl(B.vol[RS], sl), rdl(B.price[RS], sl), 0, t0 + k, false);
+    }
     B.live[RS] &= ~bit;  // Cancellation
     return;
   }
@@ -592,10 +600,16 @@ __device__ __forceinline__ void slot_event_at(Book<R>& B, const DevArgs& a, uint
   bool filled = false, market;
   if (CLS ? (ew & EV_BID) != 0 : (B.bid[RS] & bit) != 0) {
     market = p == 0xFFFFFFFFu;
-    if (B.trading) filled = match_side<R, true>(B, a, book, t0, lane, k, p, v, id, nolog);
+    if (B.trading) {
+      if constexpr (LOG) filled = match_side<R, true>(B, a, book, t0, lane, k, p, v, id, lg...);
+      else filled = match_side<R, true>(B, a, book, t0, lane, k, p, v, id, nolog);
+    }
   } else {
     market = p == 0u;
-    if (B.trading) filled = match_side<R, false>(B, a, book, t0, lane, k, p, v, id, nolog);
+    if (B.trading) {
+      if constexpr (LOG) filled = match_side<R, false>(B, a, book, t0, lane, k, p, v, id, lg...);
+      else filled = match_side<R, false>(B, a, book, t0, lane, k, p, v, id, nolog);
+    }
   }
   if (!market && !filled) {  // rest the remainder with a fresh priority stamp
     B.vol[RS] = wrl(v, sl, B.vol[RS]);
@@ -603,18 +617,29 @@ __device__ __forceinline__ void slot_event_at(Book<R>& B, const DevArgs& a, uint
     B.live[RS] |= bit;
     B.seq_ctr += 1;
   }
+  if constexpr (LOG) {  // place_order's outcome (orderbook.rs:488-611), as k_step_events logs a New
+    const uint64_t tk = t0 + k;
+    uint32_t status = 1;  // Active
+    uint64_t end = ~0ull;
+    if (filled || market) {
+      status = filled ? 2u : (B.trading ? 3u : 4u);  // Filled / unfilled market remainder Cancelled / Rejected
+      end = tk;
+    }
+    // key: provisional (price, 0) from create_order (orderbook.rs:388-391) unless the order rests (:501-505)
+    log_write(lg..., B.flags, lane, id, status, v, p, tk, end, true, true, status == 1 ? tk : 0ull);
+  }
 }
 
-template <int R, int RS = 0, bool CLS = false>
+template <int R, int RS = 0, bool CLS = false, bool LOG = false, class... Lg>
 __device__ __forceinline__ void process_slot_event(Book<R>& B, const DevArgs& a, uint32_t book, uint64_t t0, int lane,
-                                                   uint32_t k, uint32_t n, uint32_t ew = 0) {
+                                                   uint32_t k, uint32_t n, uint32_t ew = 0, const Lg&... lg) {
   if constexpr (RS + 1 < R) {
     if ((n >> 6) == (uint32_t)RS)
-      slot_event_at<R, RS, CLS>(B, a, book, t0, lane, k, n & 63, ew);
+      slot_event_at<R, RS, CLS, LOG>(B, a, book, t0, lane, k, n & 63, ew, lg...);
     else
-      process_slot_event<R, RS + 1, CLS>(B, a, book, t0, lane, k, n, ew);
+      process_slot_event<R, RS + 1, CLS, LOG>(B, a, book, t0, lane, k, n, ew, lg...);
   } else {
-    slot_event_at<R, RS, CLS>(B, a, book, t0, lane, k, n & 63, ew);
+    slot_event_at<R, RS, CLS, LOG>(B, a, book, t0, lane, k, n & 63, ew, lg...);
   }
 }
 
@@ -1184,11 +1209,14 @@ __device__ __forceinline__ void slot_event_keyed(Book<R>& B, KeyState<R>& K, con
 // MKT: the list is the MARKET's queue (market_env.rs:110-121); this book processes the events of its own agents'
 // slots (`mine`) at their global positions t0 + k and skips the rest.  Returns trades; `n_own` = events processed.
 // TAGGED (MKT lists written by k_agents_mixed_lanes): entry = slot | asset << 12, ownership by the tag.
-template <int R, bool MKT = false, bool TAGGED = false, bool CLS = false, bool PENDKEY = false>
+// LOG (k_step_batch_log): the event-by-event loop, writing the order log `lg` (one LogCtx; the keyed and assembly loops
+// keep no log).
+template <int R, bool MKT = false, bool TAGGED = false, bool CLS = false, bool PENDKEY = false, bool LOG = false, class... Lg>
 __device__ __forceinline__ uint32_t step_from_list(Book<R>& B, const DevArgs& a, uint32_t book, int lane,
                                                    const uint32_t (&ev)[R], uint32_t n_ev, uint32_t* bins,
                                                    uint32_t hist_slot, bool write_last, const UDiv& tick,
-                                                   const uint64_t (&mine)[R], uint32_t& n_own, uint32_t asset = 0) {
+                                                   const uint64_t (&mine)[R], uint32_t& n_own, uint32_t asset = 0,
+                                                   const Lg&... lg) {
   const uint64_t step_size = mk64(a.step_lo, a.step_hi);
   const uint64_t t0 = B.t;
   B.trade_vol = 0;  // reset_trade_vol (env.rs:118)
@@ -1222,7 +1250,7 @@ __device__ __forceinline__ uint32_t step_from_list(Book<R>& B, const DevArgs& a,
       own_cnt += (uint32_t)__builtin_popcountll(__ballot(own && (uint32_t)(re * 64 + lane) < n_ev));
     }
   }
-  if constexpr ((R == 2 || R == 1) && (!MKT || MKTK) && CLS && BOURSE_AMD_ASM_EVENTS) {
+  if constexpr (!LOG && (R == 2 || R == 1) && (!MKT || MKTK) && CLS && BOURSE_AMD_ASM_EVENTS) {
     listed = true;
     // hand-written event loops (event_asm.hpp); they return whenever the 64-record trade buffer is full
     uint32_t k = 0;
@@ -1264,7 +1292,7 @@ __device__ __forceinline__ uint32_t step_from_list(Book<R>& B, const DevArgs& a,
                            B.seq[0], evm[0], B.tr_k, B.tr_price, B.tr_vol, B.tr_act, B.tr_pas))
         flush_trades<R>(B, a, book, t0, lane);
     }
-  } else if (KeyState<R> K; (CLS || PENDKEY) && (!MKT || MKTK) && BOURSE_AMD_KEYED_EVENTS &&
+  } else if (KeyState<R> K; !LOG && (CLS || PENDKEY) && (!MKT || MKTK) && BOURSE_AMD_KEYED_EVENTS &&
              (keys_begin<R, !CLS>(B, newm, rfl(n_ev), K) ||
               // (members' lists only: RandomAgents draw their prices from a bounded tick window, and the extra path costs
               // k_step_batch<8>'s RandomAgents instantiation 32 B of scratch at its 96-register claim)
@@ -1350,7 +1378,7 @@ __device__ __forceinline__ uint32_t step_from_list(Book<R>& B, const DevArgs& a,
           if (!mask_test<R>(mine, slot)) continue;
           ++n_own;
         }
-        process_slot_event<R, 0, CLS>(B, a, book, t0, lane, kb + l, slot, ew);
+        process_slot_event<R, 0, CLS, LOG>(B, a, book, t0, lane, kb + l, slot, ew, lg...);
       }
     }
   }
@@ -1637,12 +1665,14 @@ __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
   }
 }
 
-template <int R, bool MKT, bool POOLPEND>
+template <int R, bool MKT, bool POOLPEND, bool LOG = false>
 __device__ __forceinline__ void step_batch_book(const DevArgs& a, uint32_t book, int lane, uint32_t* lds, uint64_t step_index,
-                                                uint32_t write_last, Book<R>& B, Rng& rng, uint32_t hist_slot);
-template <int R, bool MKT, bool POOLPEND>
+                                                uint32_t write_last, Book<R>& B, Rng& rng, uint32_t hist_slot,
+                                                uint4* dorders = nullptr);
+template <int R, bool MKT, bool POOLPEND, bool LOG = false>
 __device__ __forceinline__ void step_batch_raw(const DevArgs& a, uint32_t book, int lane, uint32_t* lds, uint64_t step_index,
-                                               uint32_t write_last, const StepRaw<R>& w, Book<R>& B, Rng& rng, uint32_t hist_slot);
+                                               uint32_t write_last, const StepRaw<R>& w, Book<R>& B, Rng& rng, uint32_t hist_slot,
+                                               uint4* dorders = nullptr);
 // POOLPEND (split pipeline of AgentSets with Noise/Momentum members, k_agents_mixed): the new orders already sit in the
 // pool with their pend bit and id (created by the members' update); the batch only carries the shuffled event list.
 template <int R, bool MKT, bool POOLPEND = false>
@@ -1678,11 +1708,27 @@ __global__ __launch_bounds__(64, R >= 8 ? 5 : 1) void k_step_batch(DevArgs a, ui
   step_batch_book<R, MKT, POOLPEND>(a, book, lane, lds, step_index, write_last, B, rng, a.hist_slot0);
 }
 
+// k_step_batch of the RandomAgents split pipelines with the order log (bk_set_agent_order_log): the same step, on the
+// event-by-event loop, with every order the agents create and every change of it recorded for the readers -
+// dorders[book][id] = the immutable half {start_vol, trader, price, bid} {create_lo, create_hi, 0, 0} (k_ingest's layout),
+// order_log[book][id] = the mutable half.  (A kernel of its own: k_step_batch's names and code stay as they are.)
+template <int R, bool MKT>
+__global__ __launch_bounds__(64) void k_step_batch_log(DevArgs a, uint64_t step_index, uint32_t write_last, uint4* dorders) {
+  __shared__ uint32_t lds[LDS_DW_PER_WAVE];
+  if (a.step_prio) __builtin_amdgcn_s_setprio(1);
+  const int lane = threadIdx.x;
+  const uint32_t book = MKT ? a.book_begin * a.assets + blockIdx.x : a.book_begin + blockIdx.x;
+  if (book >= (MKT ? a.book_end * a.assets : a.book_end)) return;
+  Book<R> B;
+  Rng rng;
+  step_batch_book<R, MKT, false, true>(a, book, lane, lds, step_index, write_last, B, rng, a.hist_slot0, dorders);
+}
+
 // One book's Env::step from its step batch (the body of k_step_batch; round 4's two experimental kernels ran it in front of the next step's
 // decode).  lds: LDS_DW_PER_WAVE dwords of this wave's.  Leaves the stored book in B / rng for a caller that goes on.
-template <int R, bool MKT, bool POOLPEND>
+template <int R, bool MKT, bool POOLPEND, bool LOG>
 __device__ __forceinline__ void step_batch_book(const DevArgs& a, uint32_t book, int lane, uint32_t* lds, uint64_t step_index,
-                                                uint32_t write_last, Book<R>& B, Rng& rng, uint32_t hist_slot) {
+                                                uint32_t write_last, Book<R>& B, Rng& rng, uint32_t hist_slot, uint4* dorders) {
   StepRaw<R> w;
   const uint32_t mkt_book0 = MKT ? (book / a.assets) * a.assets : book;
   const uint32_t* st = a.state + (size_t)book * a.state_stride;
@@ -1695,12 +1741,13 @@ __device__ __forceinline__ void step_batch_book(const DevArgs& a, uint32_t book,
     w.pv[r] = POOLPEND ? make_uint2(0u, 0u) : reinterpret_cast<const uint2*>(bt + BT_EV + 32 * R)[r * 64 + lane];
   }
   load_state_scalars<R>(w, st);  // (behind the vector loads: its wait hides under their round trip)
-  step_batch_raw<R, MKT, POOLPEND>(a, book, lane, lds, step_index, write_last, w, B, rng, hist_slot);
+  step_batch_raw<R, MKT, POOLPEND, LOG>(a, book, lane, lds, step_index, write_last, w, B, rng, hist_slot, dorders);
 }
 // ... from what load_step_raw / the wrapper above loaded
-template <int R, bool MKT, bool POOLPEND>
+template <int R, bool MKT, bool POOLPEND, bool LOG>
 __device__ __forceinline__ void step_batch_raw(const DevArgs& a, uint32_t book, int lane, uint32_t* lds, uint64_t step_index,
-                                               uint32_t write_last, const StepRaw<R>& w, Book<R>& B, Rng& rng, uint32_t hist_slot) {
+                                               uint32_t write_last, const StepRaw<R>& w, Book<R>& B, Rng& rng, uint32_t hist_slot,
+                                               uint4* dorders) {
   const uint32_t mkt_book0 = MKT ? (book / a.assets) * a.assets : book;
   const uint32_t asset = book - mkt_book0;
   uint32_t* st = a.state + (size_t)book * a.state_stride;
@@ -1759,15 +1806,38 @@ __device__ __forceinline__ void step_batch_raw(const DevArgs& a, uint32_t book, 
     // create_order ids: dense, in agent order (orderbook.rs:363): base + #placing agents below this slot
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
     B.id[r] = sel(pend, base + rank, B.id[r]);
+    if constexpr (LOG) {
+      // create_order's record of each new order (orderbook.rs:356-396), lane-parallel: the trader id is the agent's index
+      // within its group (random_agent.rs:106, 231), created at the step's start time; ids beyond the log's capacity are
+      // flagged at their placement (log_write)
+      const uint32_t slot = 64u * r + (uint32_t)lane, id = base + rank;
+      uint32_t trader = 0, gb = 0;
+      for (uint32_t g = 0; g < a.n_groups; ++g) {
+        const uint32_t ge = gb + a.groups[g].n;
+        trader = (slot >= gb && slot < ge) ? slot - gb : trader;
+        gb = ge;
+      }
+      if (lane_bit(pend) && id < a.log_cap) {
+        uint4* d = dorders + ((size_t)book * a.log_cap + id) * 2;
+        d[0] = make_uint4(pv.y, trader, pv.x, (uint32_t)lane_bit(side));
+        d[1] = make_uint4((uint32_t)B.t, (uint32_t)(B.t >> 32), 0u, 0u);
+      }
+    }
     base += __builtin_popcountll(pend);
     B.bid[r] = (B.bid[r] & ~pend) | (side & pend);
     B.pend[r] = pend;  // handed to step_from_list, which clears it (the event words classify themselves: EV_NEW)
   }
   B.next_id = base;
   uint32_t n_own = 0;
-  const uint32_t ntr = step_from_list<R, MKT, MKT && POOLPEND, !POOLPEND, POOLPEND && !MKT>(B, a, book, lane, ev, n_ev, lds, hist_slot,
-                                                               write_last != 0, MKT ? a.asset_div[asset] : a.tick_div,
-                                                               mine, n_own, asset);
+  uint32_t ntr;
+  if constexpr (LOG)
+    ntr = step_from_list<R, MKT, false, true, false, true>(B, a, book, lane, ev, n_ev, lds, hist_slot, write_last != 0,
+                                                           MKT ? a.asset_div[asset] : a.tick_div, mine, n_own, asset,
+                                                           LogCtx{a.order_log + (size_t)book * a.log_cap, a.log_cap});
+  else
+    ntr = step_from_list<R, MKT, MKT && POOLPEND, !POOLPEND, POOLPEND && !MKT>(B, a, book, lane, ev, n_ev, lds, hist_slot,
+                                                                               write_last != 0, MKT ? a.asset_div[asset] : a.tick_div,
+                                                                               mine, n_own, asset);
   store_book<R, !POOLPEND>(B, rng, st, lane, step_index + 1, ntr, n_own);
   if (POOLPEND) {
 #pragma unroll

@@ -193,6 +193,9 @@ struct bk_env {
   DevBuf<uint4> dq, dorders;       // [n_markets][qcap] event records; [n_books][max_orders][2] immutable halves
   DevBuf<uint32_t> dqlen;          // [n_markets] queue lengths
   uint64_t ingest_epoch = 0;       // bumped by every submit / step: invalidates the readers' mirrors
+  // bk_set_agent_order_log: bk_run's RandomAgents record their orders in dorders / order_log (k_step_batch_log); the
+  // readers mirror them like the device ingress's
+  bool agent_log = false;
   // HOST arrays through the device ingress (bk_submit_instructions_host): two slots of pinned + device staging, the
   // upload of ticket t + 1 on a copy stream of its own under the step kernel of ticket t, ids / status back on a third
   struct HostIngress {
@@ -663,7 +666,11 @@ int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs&
         launch_timed(env, 1, &k_agents_fsm<R>, dim3((nb + 63) / 64), dim3(64), fsm_lds_bytes(R), st, a);
       if (P > 1 && s == 0) HIPCHK(hipEventRecord(env->ev_first[i], st));
       const uint32_t write_last = (s + 1 == n_steps || a.hist_cap == 0 || pl.write_last) ? 1u : 0u;
-      if (pl.step_poolpend && pl.step_mkt)
+      if (pl.step_log && pl.step_mkt)
+        launch_timed(env, 2, &k_step_batch_log<R, true>, dim3(nb * M), dim3(64), 0u, st, a, step_no, write_last, env->dorders.p);
+      else if (pl.step_log)
+        launch_timed(env, 2, &k_step_batch_log<R, false>, dim3(nb), dim3(64), 0u, st, a, step_no, write_last, env->dorders.p);
+      else if (pl.step_poolpend && pl.step_mkt)
         launch_timed(env, 2, &k_step_batch<R, true, true>, dim3(nb * M), dim3(64), 0u, st, a, step_no, write_last);
       else if (pl.step_poolpend)
         launch_timed(env, 2, &k_step_batch<R, false, true>, dim3(nb), dim3(64), 0u, st, a, step_no, write_last);
@@ -727,11 +734,12 @@ int refresh_log(bk_env* env, uint32_t book) {
   return BK_OK;
 }
 
-// Device-resident ingress: the readers' view of one book's orders.  The immutable halves written by k_ingest and the
-// book's id counter are fetched into the same BookHost fields the host-driven path fills at bk_place_order, so every
-// reader below works unchanged; valid until the next submit / step (ingest_epoch).
+// Device-resident ingress and logged on-device agents: the readers' view of one book's orders.  The immutable halves
+// written by k_ingest / k_step_batch_log and the book's id counter are fetched into the same BookHost fields the
+// host-driven path fills at bk_place_order, so every reader below works unchanged; valid until the next submit / step /
+// bk_run (ingest_epoch).
 int mirror_orders(bk_env* env, uint32_t book) {
-  if (!env->device_ingress) return BK_OK;
+  if (!env->device_ingress && !env->agent_log) return BK_OK;
   BookHost& bh = env->books[book];
   if (bh.mirror_epoch == env->ingest_epoch) return BK_OK;
   HIPCHK(hipSetDevice(env->cfg.device));
@@ -748,7 +756,7 @@ int mirror_orders(bk_env* env, uint32_t book) {
     const uint4 a = rows[2 * id], b = rows[2 * id + 1];
     bh.orders[id] = HostOrder{static_cast<uint8_t>(a.w & 1u), a.x, a.z, a.y, (static_cast<uint64_t>(b.y) << 32) | b.x};
   }
-  bh.n_uploaded = count;  // every order has had a log entry since k_ingest created it
+  bh.n_uploaded = count;  // every order has had a log entry since k_ingest / k_step_batch_log created it
   bh.log_fresh = false;
   bh.mirror_epoch = env->ingest_epoch;
   return BK_OK;
@@ -1174,7 +1182,7 @@ int bk_device_ingress_enable(bk_env* env, uint32_t queue_capacity) {
   }
   if (queue_capacity == 0 || queue_capacity > EV_LDS_CAP)
     return fail(BK_INVALID_ARGUMENT, "queue_capacity must be in 1..8192 events per book (market) and step");
-  if (env->device_flow || env->n_mixed || !env->groups.empty())
+  if (env->device_flow || env->n_mixed || !env->groups.empty() || env->agent_log)
     return fail(BK_INVALID_ARGUMENT, "an env runs ONE order flow: on-device agents (bk_run) or submitted instructions");
   for (const BookHost& bh : env->books)
     if (!bh.queue.empty() || !bh.orders.empty())
@@ -1630,6 +1638,9 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
     return bk_set_random_market_agents(env, n_members, g.data(), assets);
   }
   if (n_members > MAX_MEMBERS) return fail(BK_INVALID_ARGUMENT, "at most 4 members in a set with Noise/Momentum agents");
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "the agents' order log (bk_set_agent_order_log) records RandomAgents only: "
+                                     "a set with Noise / Momentum members cannot be installed on a logging env");
   if (int rc = use_device(env)) return rc;
   std::vector<MixedDesc> ds(n_members);
   uint32_t fixed_a[MAX_ASSETS] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1713,7 +1724,7 @@ static void query_fused_resident(bk_env* env) {
 // THE pipeline choice (pipeline_plan.hpp): bk_run launches from it, bk_get_pipeline reports it
 static Plan env_plan(bk_env* env) {
   PlanInput in{env->R, env->cfg.n_books, env->M, !env->groups.empty(), env->n_mixed, env->pipeline, env->n_parts, env->wave_parts,
-               env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode};
+               env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode, env->agent_log};
   if (!in.fused_resident && random_books(in)) {
     query_fused_resident(env);
     in.fused_resident = env->fused_resident;
@@ -1755,6 +1766,35 @@ int bk_run(bk_env* env, uint64_t n_steps) {
   });
   if (rc != BK_OK) return rc;
   env->steps_done += n_steps;
+  if (env->agent_log) env->ingest_epoch += 1;  // the agents created and changed orders: the readers mirror again
+  return BK_OK;
+}
+
+int bk_set_agent_order_log(bk_env* env, int on) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!on) {
+    if (env->agent_log) return fail(BK_INVALID_ARGUMENT, "the agents' order log cannot be switched off once it is on");
+    return BK_OK;
+  }
+  if (env->agent_log) return BK_OK;
+  if (env->cfg.max_orders == 0)
+    return fail(BK_INVALID_ARGUMENT, "the agents' order log needs max_orders > 0 (its capacity per book)");
+  if (env->steps_done || env->device_flow)
+    return fail(BK_INVALID_ARGUMENT, "switch the agents' order log on before the env's first bk_run: it could not hold "
+                                     "the orders created before");
+  if (env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "this env takes its instructions from device memory (bk_device_ingress_enable), which "
+                                     "logs its orders already");
+  if (env->n_mixed)
+    return fail(BK_INVALID_ARGUMENT, "the agents' order log records RandomAgents only: this env has an AgentSet with "
+                                     "Noise / Momentum members");
+  for (const BookHost& bh : env->books)
+    if (!bh.orders.empty() || !bh.queue.empty())
+      return fail(BK_INVALID_ARGUMENT, "the agents' order log is for bk_run's on-device agents: this env holds host-driven orders");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(env->dorders.alloc(static_cast<size_t>(env->cfg.n_books) * env->cfg.max_orders * 2));
+  env->agent_log = true;
+  env->ingest_epoch += 1;
   return BK_OK;
 }
 
@@ -2051,6 +2091,11 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (int rc = check_book(env, book)) return rc;
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
+  // (the agents' log holds what k_step_batch_log wrote for every id below the book's counter: a loaded book's orders
+  // would be mirrored from rows nothing wrote)
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with the agents' order log (bk_set_agent_order_log) is not "
+                                     "supported");
   BookHost& bh = env->books[book];
   if (!env->books[book - book % env->M].queue.empty())
     return fail(BK_INVALID_ARGUMENT, "events are queued for this book (market)");
@@ -2465,6 +2510,8 @@ int bk_checkpoint_save(bk_env* env, void* out, uint64_t nbytes) {
   if (!env || !out) return fail(BK_INVALID_ARGUMENT, "null argument");
   if (nbytes < bk_checkpoint_bytes(env)) return fail(BK_INVALID_ARGUMENT, "checkpoint buffer too small");
   if (env->device_ingress) return fail(BK_INVALID_ARGUMENT, "checkpointing a host-driven env is not supported");
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "checkpointing an env with the agents' order log (bk_set_agent_order_log) is not supported");
   for (const BookHost& bh : env->books)
     if (!bh.orders.empty()) return fail(BK_INVALID_ARGUMENT, "checkpointing a host-driven env is not supported");
   if (int rc = use_device(env)) return rc;
@@ -2480,6 +2527,10 @@ int bk_checkpoint_save(bk_env* env, void* out, uint64_t nbytes) {
 
 int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
   if (!env || !in) return fail(BK_INVALID_ARGUMENT, "null argument");
+  // (a restored book's id counter would cover orders the agents' log never saw: their rows are unwritten)
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "restoring a checkpoint into an env with the agents' order log (bk_set_agent_order_log) is "
+                                     "not supported");
   const uint64_t* h = static_cast<const uint64_t*>(in);
   if (nbytes < CKPT_HDR * 8 || h[0] != CKPT_MAGIC)
     return fail(BK_INVALID_ARGUMENT, "not a bourse_amd checkpoint of this version (bad magic)");

@@ -44,6 +44,7 @@ struct PlanInput {                // what the rule reads of an env
   uint32_t fused_resident = 0;    // books one residency round of k_run_wave<R> holds on this device (0 = not asked yet)
   uint32_t stagger_us = ~0u;      // BOURSE_AMD_STAGGER_US, ~0 = the default rule
   bool warming = false, step_decode = false;  // bk_warm's scratch steps; BOURSE_AMD_STEP_DECODE
+  bool order_log = false;         // bk_set_agent_order_log: the agents' orders are logged (only the split kinds can)
 };
 
 enum PlanKind {
@@ -70,6 +71,7 @@ struct Plan {  // every choice the launch code makes; the fused kinds leave all 
   bool step_prio = false;        // the event waves run at priority 1
   bool write_last = false;       // every step writes the latest level-2 record (otherwise only a launch's last one)
   bool step_decode = false;      // k_step_decode<R> takes a part's inner steps: events of step s + decode of step s + 1
+  bool step_log = false;         // k_step_batch_log<R, MKT> instead of k_step_batch<R, MKT>: the order log is written
 };
 
 inline bool is_split(PlanKind k) { return k != PL_FUSED_RANDOM && k != PL_FUSED_WAVE && k != PL_MIXED_FUSED; }
@@ -124,6 +126,12 @@ inline PlanKind plan_kind(const PlanInput& in) {
 inline Plan make_plan(const PlanInput& in) {
   Plan p;
   p.kind = plan_kind(in);
+  // the order log of the agents' orders is written by the split forms' event kernel only: a RandomAgents env that logs
+  // takes the split form of the fused kind the rule picked (k_run_wave -> wave_split, k_run_random -> split)
+  if (in.order_log && in.groups && !in.n_mixed) {
+    if (p.kind == PL_FUSED_WAVE) p.kind = PL_SPLIT_WAVE;
+    if (p.kind == PL_FUSED_RANDOM) p.kind = PL_SPLIT_LANES;
+  }
   if (!is_split(p.kind)) return p;
   const bool mixed = p.kind != PL_SPLIT_LANES && p.kind != PL_SPLIT_WAVE;
   const bool wave = p.kind == PL_SPLIT_WAVE || p.kind == PL_MIXED_WAVE;  // (both on independent books only)
@@ -149,7 +157,9 @@ inline Plan make_plan(const PlanInput& in) {
   p.write_last = p.kind == PL_MIXED_LANES || p.kind == PL_MIXED_WAVE;
   // (experiment, docs/EXPERIMENTS.md: BOURSE_AMD_STEP_DECODE=1 runs a part's inner steps of the wave_split pipeline as ONE
   // launch each - k_step_decode = events of step s + decode of step s + 1)
-  p.step_decode = in.step_decode && p.kind == PL_SPLIT_WAVE && !in.warming;
+  // (bk_warm's scratch steps leave the log alone: they run the log-less kernel and the books are put back)
+  p.step_log = in.order_log && !in.warming;
+  p.step_decode = in.step_decode && p.kind == PL_SPLIT_WAVE && !in.warming && !p.step_log;
   return p;
 }
 

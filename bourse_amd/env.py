@@ -575,6 +575,13 @@ class ManyBookEnv:
             if self.strict:
                 self.raise_on_flags()
 
+    def enable_agent_order_log(self):
+        """Record the orders ``run``'s RandomAgents create (``bk_set_agent_order_log``): ``orders`` / ``order_status`` /
+        ``order_keys`` / ``book_state`` then answer for them as ``Env::get_orders`` / ``order_status`` do after
+        ``sim_runner`` (env.rs:253-290).  Needs ``max_orders > 0`` (the log's capacity per book, 80 B per order) and must be
+        called before the first ``run``; the env then runs the split pipelines with the logging event kernel."""
+        check(self._L.bk_set_agent_order_log(self._h, 1))
+
     def warm(self, n_steps: int = 100):
         """``bk_warm``: ``n_steps`` of this env's own kernels on its own books, then everything is put back (state,
         level-2 records, step counter; no history slot or trade record is written).  Brings the GPU's clocks up and

@@ -64,7 +64,8 @@ typedef struct bk_config {
   uint64_t seed;            /* book b is seeded seed + book_offset + b (identity for B = 1) */
   uint64_t book_offset;     /* global index of this GPU's first book (multi-GPU sharding) */
   uint32_t max_live_orders; /* live-order pool per book, rounded up to 64, 128, 256 or 512 (0 = 128; more is refused) */
-  uint32_t max_orders;      /* order-log capacity per book for the host-driven path (0 = no log) */
+  uint32_t max_orders;      /* order-log capacity per book: host-driven orders, the device ingress, and bk_run's
+                               RandomAgents after bk_set_agent_order_log (0 = no log) */
   uint32_t trade_capacity;  /* trade records retained per book between bk_clear_trades() calls */
   uint32_t history_capacity;/* L2 history ring: the last N steps are retained (0 = keep only the latest record) */
   int32_t device;           /* HIP device ordinal */
@@ -289,6 +290,18 @@ int bk_run(bk_env* env, uint64_t n_steps);
  * ~15 ms of load to come back, and a pipeline's first launch pays one-off set-up.  Asynchronous like bk_run.  (No
  * counterpart in the reference: a CPU has no launch set-up to hide.) */
 int bk_warm(bk_env* env, uint64_t n_steps);
+/* Opt-in order log of bk_run's RandomAgents (independent books and markets): every order the agents create is recorded
+ * with its trader id (the agent's index within its group), status, remaining volume, arrival / end times and key, so that
+ * bk_order_count / bk_get_orders / bk_order_status / bk_get_order_keys answer after bk_run as Env::get_orders /
+ * order_status do after sim_runner (env.rs:253-290).  Needs max_orders > 0 (ids beyond it set BK_FLAG_ORDER_LOG_FULL and
+ * the readers then return BK_CAPACITY); 80 B per order per book.  Call before the env's first bk_run.  Refused
+ * (BK_INVALID_ARGUMENT) on a device-ingress env (which logs already) and with Noise / Momentum members installed
+ * (bk_set_agents / bk_set_market_agents then refuse such members); bk_checkpoint_save, bk_checkpoint_load and
+ * bk_load_book refuse a logging env (the log holds only the orders its own bk_run steps created).  A
+ * logging env runs the split pipelines (split or wave_split in place of the fused ones) with the logging event kernel;
+ * bk_warm's scratch steps leave the log and the id counters as they were.  on = 0 leaves an env without the log as it is
+ * and is refused once the log is on (it cannot be switched off). */
+int bk_set_agent_order_log(bk_env* env, int on);
 /* One env runs ONE of the two order flows: once bk_run has stepped it with on-device agents, bk_place_order /
  * bk_cancel_order / bk_modify_order / bk_submit_instructions* / bk_step return BK_INVALID_ARGUMENT (host order ids would
  * restart at 0 and collide with the agents'); and bk_run refuses an env that holds host-placed orders. */

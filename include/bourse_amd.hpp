@@ -172,6 +172,8 @@ class ManyEnv {
   void set_random_agents(const std::vector<bk_random_agents>& groups) {
     check(bk_set_random_agents(h_, static_cast<uint32_t>(groups.size()), groups.data()));
   }
+  // record the agents' orders (bk_set_agent_order_log; before the first run): env(b).get_orders() answers after run
+  void enable_agent_order_log() { check(bk_set_agent_order_log(h_, 1)); }
   void run(uint64_t n_steps) {
     check(bk_run(h_, n_steps));
     check(bk_env_sync(h_));
