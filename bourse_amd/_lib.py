@@ -87,6 +87,11 @@ ORDER_DTYPE = np.dtype(
      "formats": ["u1", "u1", "<u8", "<u8", "<u4", "<u4", "<u4", "<u4", "<u8"],
      "offsets": [0, 1, 8, 16, 24, 28, 32, 36, 40], "itemsize": 48})
 
+# bk_random_agents (RandomAgentsCfg) as a numpy structured dtype: the rows of ManyBookEnv.set_random_agents_per_book's table
+RANDOM_AGENTS_DTYPE = np.dtype(
+    {"names": ["n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate"],
+     "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<f4"], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 28})
+
 class IngressArrays(C.Structure):
     """bk_ingress_arrays: the pinned staging arrays of the next bk_submit_instructions_host call."""
     _fields_ = [("capacity", C.c_uint64), ("book_offsets", C.c_void_p), ("action", C.c_void_p), ("side", C.c_void_p),
@@ -126,6 +131,7 @@ SIGNATURES = {
     "bk_set_random_agents": (_i32, [_vp, _u32, C.POINTER(RandomAgentsCfg)]),
     "bk_set_tick_sizes": (_i32, [_vp, _u32, _p32]),
     "bk_set_random_market_agents": (_i32, [_vp, _u32, C.POINTER(RandomAgentsCfg), _p32]),
+    "bk_set_random_agents_per_book": (_i32, [_vp, _u32, _vp, _p32]),
     "bk_set_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc)]),
     "bk_set_market_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc), _p32]),
     "bk_run": (_i32, [_vp, _u64]),

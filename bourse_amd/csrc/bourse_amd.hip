@@ -33,8 +33,13 @@ extern template __global__ void k_agents_fsm<1>(DevArgs);
 extern template __global__ void k_agents_fsm<2>(DevArgs);
 extern template __global__ void k_agents_fsm<4>(DevArgs);
 extern template __global__ void k_agents_fsm<8>(DevArgs);
+extern template __global__ void k_agents_fsm<1, true>(DevArgs, const Group*);
+extern template __global__ void k_agents_fsm<2, true>(DevArgs, const Group*);
+extern template __global__ void k_agents_fsm<4, true>(DevArgs, const Group*);
+extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 }  // namespace bkd
 #include "host_math.hpp"
+#include "agent_table.hpp"
 #include "host_pool.hpp"
 #include "pipeline_plan.hpp"
 #include "mixed_agents.hpp"
@@ -184,6 +189,10 @@ struct bk_env {
     return *pool;
   }
   std::vector<Group> groups;
+  // bk_set_random_agents_per_book: the per-unit table (unit u = book u, or market u), table[u * n_groups + g], on the host
+  // (the hash) and on the device (the PB kernels); `groups` then holds unit 0's row, whose sizes and assets every unit shares
+  std::vector<Group> table;
+  DevBuf<Group> dtable;
   uint32_t n_agents_total = 0;
   uint64_t agents_hash = 0;   // FNV-1a of the installed agent set (checkpoint compatibility)
   // device-resident instruction ingress (bk_device_ingress_enable): the queues, the id counters and the immutable halves of
@@ -526,6 +535,8 @@ int prepare_launch(bk_env* env, const Plan& pl, const DevArgs& a0, WaveArgs* wva
       if (!env->fsm_attr_set) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_fsm<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(fsm_lds_bytes(R))));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_fsm<R, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fsm_lds_bytes(R))));
         env->fsm_attr_set = true;
       }
       if (pl.kind == PL_SPLIT_WAVE) return wave_args(env, wva);
@@ -608,6 +619,9 @@ int launch_fused(bk_env* env, const Plan& pl, const DevArgs& a, const WaveArgs& 
   ProfScope ps(env, 0);
   if (pl.kind == PL_MIXED_FUSED)
     hipLaunchKernelGGL(k_run_mixed<R>, dim3((nb + 3) / 4), dim3(256), 0, env->stream, a, env->margs(), first_step, n_steps);
+  else if (pl.kind == PL_FUSED_WAVE && pl.agents_per_book)
+    hipLaunchKernelGGL((k_run_wave<R, true>), dim3((nb + 7) / 8), dim3(512), 0, env->stream, a, wva, first_step, n_steps,
+                       static_cast<const Group*>(env->dtable.p));
   else if (pl.kind == PL_FUSED_WAVE)
     hipLaunchKernelGGL(k_run_wave<R>, dim3((nb + 7) / 8), dim3(512), 0, env->stream, a, wva, first_step, n_steps);
   else
@@ -623,6 +637,7 @@ int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs&
   const MixedLists ml = env->lists();
   const uint32_t M = env->M;
   const uint32_t B = env->cfg.n_books / M;  // units the parts are cut in: books, or markets of M books
+  const Group* table = env->dtable.p;        // (pl.agents_per_book: the per-unit table)
   const int P = pl.parts;  // (small batches: one part on the caller's stream)
   if (P > 1) {
     if (int rc = prepare_parts(env)) return rc;
@@ -660,8 +675,12 @@ int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs&
         launch_timed(env, 1, &k_agents_mixed<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, ma);
       else if (pl.agents == AG_WAVE && pl.step_decode && s > 0)
         ;  // (the previous step's k_step_decode has decoded this step already)
+      else if (pl.agents == AG_WAVE && pl.agents_per_book)
+        launch_timed(env, 1, &k_agents_wave<R, true>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, wva, table);
       else if (pl.agents == AG_WAVE)
         launch_timed(env, 1, &k_agents_wave<R>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, wva);
+      else if (pl.agents_per_book)
+        launch_timed(env, 1, &k_agents_fsm<R, true>, dim3((nb + 63) / 64), dim3(64), fsm_lds_bytes(R), st, a, table);
       else
         launch_timed(env, 1, &k_agents_fsm<R>, dim3((nb + 63) / 64), dim3(64), fsm_lds_bytes(R), st, a);
       if (P > 1 && s == 0) HIPCHK(hipEventRecord(env->ev_first[i], st));
@@ -1557,40 +1576,45 @@ int bk_set_random_market_agents(bk_env* env, uint32_t n_groups, const bk_random_
                                 const uint32_t* assets) {
   if (!env || (!groups && n_groups)) return fail(BK_INVALID_ARGUMENT, "null argument");
   if (n_groups > MAX_GROUPS) return fail(BK_INVALID_ARGUMENT, "at most 8 agent groups");
-  std::vector<Group> gs;
+  std::vector<Group> gs(n_groups);
   uint64_t total = 0;
-  for (uint32_t g = 0; g < n_groups; ++g) {
-    const bk_random_agents& r = groups[g];
-    if (r.tick_lo >= r.tick_hi || r.vol_lo >= r.vol_hi)
-      return fail(BK_INVALID_ARGUMENT, "empty tick/vol range");  // gen_range asserts low < high
-    // every sampled price tick * tick_size must pass create_order's tick check (else `.unwrap()` panics,
-    // random_agent.rs:103-110)
-    const uint32_t asset = assets ? assets[g] : 0u;
-    if (asset >= env->M) return fail(BK_INVALID_ARGUMENT, "group asset index out of range");
-    if (r.tick_size % env->asset_tick[asset] != 0)
-      return fail(BK_PRICE_NOT_TICK_MULTIPLE, "agent tick_size must be a multiple of the env tick_size");
-    if (static_cast<uint64_t>(r.tick_hi - 1) * r.tick_size >= 0xFFFFFFFFull || r.tick_lo == 0)
-      return fail(BK_INVALID_ARGUMENT, "limit prices must lie in (0, u32::MAX)");
-    Group G{};
-    G.n = r.n_agents;
-    G.thr = activity_threshold(r.activity_rate);
-    G.tick_lo = r.tick_lo;
-    G.tick_rng = r.tick_hi - r.tick_lo;
-    G.tick_zone = sample_zone(G.tick_rng);
-    G.vol_lo = r.vol_lo;
-    G.vol_rng = r.vol_hi - r.vol_lo;
-    G.vol_zone = sample_zone(G.vol_rng);
-    G.tick_size = r.tick_size;
-    G.asset = asset;
-    total += r.n_agents;
-    gs.push_back(G);
-  }
-  if (total > env->cfg.max_live_orders)
-    return fail(BK_CAPACITY, "sum of n_agents exceeds max_live_orders (one pool slot per agent)");
+  std::string msg;
+  if (int rc = make_groups(groups, n_groups, assets, env->M, env->asset_tick, gs.data(), &total, &msg))  // (agent_table.hpp)
+    return fail(rc, msg);
+  if (total > env->cfg.max_live_orders) return fail(BK_CAPACITY, CAPACITY_MSG);
   env->groups = gs;
   env->n_agents_total = static_cast<uint32_t>(total);
   env->n_mixed = 0;
-  env->agents_hash = gs.empty() ? 0 : fnv1a(gs.data(), gs.size() * sizeof(Group));
+  env->table.clear();  // (replaces a per-unit table)
+  (void)env->dtable.alloc(0);
+  env->agents_hash = gs.empty() ? 0 : groups_hash(gs.data(), gs.size());
+  return BK_OK;
+}
+
+// RandomAgents groups whose parameters differ per unit (book, or market when assets > 1): every row is checked and
+// preprocessed as bk_set_random_market_agents does one (agent_table.hpp make_group_table); the table goes to the device,
+// where the PB forms of k_agents_fsm / k_agents_wave / k_run_wave read unit u's row.  Nothing changes on a failure.
+int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_random_agents* groups, const uint32_t* assets) {
+  if (!env || (!groups && n_groups)) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (n_groups == 0) return fail(BK_INVALID_ARGUMENT, "a per-unit table needs at least one group");
+  if (n_groups > MAX_GROUPS) return fail(BK_INVALID_ARGUMENT, "at most 8 agent groups");
+  const uint32_t n_units = env->cfg.n_books / env->M;
+  std::vector<Group> t;
+  uint64_t total = 0;
+  std::string msg;
+  if (int rc = make_group_table(groups, n_units, n_groups, assets, env->M, env->asset_tick, env->cfg.max_live_orders, t, &total, &msg))
+    return fail(rc, msg);
+  if (int rc = use_device(env)) return rc;
+  DevBuf<Group> d;
+  HIPCHK(d.alloc(t.size()));
+  HIPCHK(hipMemcpy(d.p, t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice));
+  std::swap(env->dtable.p, d.p);  // (the previous table, if any, is freed with `d`)
+  std::swap(env->dtable.n, d.n);
+  env->groups.assign(t.begin(), t.begin() + n_groups);
+  env->table.swap(t);
+  env->n_agents_total = static_cast<uint32_t>(total);
+  env->n_mixed = 0;
+  env->agents_hash = groups_hash(env->table.data(), env->table.size());
   return BK_OK;
 }
 
@@ -1701,6 +1725,8 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
   for (uint32_t as = 0; as < MAX_ASSETS; ++as) env->n_fixed_a[as] = fixed_a[as];
   env->ml_valid = false;
   env->groups.clear();
+  env->table.clear();
+  (void)env->dtable.alloc(0);
   env->n_agents_total = 0;
   env->agents_hash = fnv1a(env->member_asset, sizeof(env->member_asset), fnv1a(ds.data(), ds.size() * sizeof(MixedDesc)));
   return BK_OK;
@@ -1724,7 +1750,8 @@ static void query_fused_resident(bk_env* env) {
 // THE pipeline choice (pipeline_plan.hpp): bk_run launches from it, bk_get_pipeline reports it
 static Plan env_plan(bk_env* env) {
   PlanInput in{env->R, env->cfg.n_books, env->M, !env->groups.empty(), env->n_mixed, env->pipeline, env->n_parts, env->wave_parts,
-               env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode, env->agent_log};
+               env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode, env->agent_log,
+               !env->table.empty()};
   if (!in.fused_resident && random_books(in)) {
     query_fused_resident(env);
     in.fused_resident = env->fused_resident;

@@ -15,4 +15,9 @@ template __global__ void k_agents_fsm<1>(DevArgs);
 template __global__ void k_agents_fsm<2>(DevArgs);
 template __global__ void k_agents_fsm<4>(DevArgs);
 template __global__ void k_agents_fsm<8>(DevArgs);
+// per-unit parameters (bk_set_random_agents_per_book)
+template __global__ void k_agents_fsm<1, true>(DevArgs, const Group*);
+template __global__ void k_agents_fsm<2, true>(DevArgs, const Group*);
+template __global__ void k_agents_fsm<4, true>(DevArgs, const Group*);
+template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 }  // namespace bkd

@@ -45,6 +45,7 @@ struct PlanInput {                // what the rule reads of an env
   uint32_t stagger_us = ~0u;      // BOURSE_AMD_STAGGER_US, ~0 = the default rule
   bool warming = false, step_decode = false;  // bk_warm's scratch steps; BOURSE_AMD_STEP_DECODE
   bool order_log = false;         // bk_set_agent_order_log: the agents' orders are logged (only the split kinds can)
+  bool per_book = false;          // bk_set_random_agents_per_book: the groups' parameters come from a per-unit table
 };
 
 enum PlanKind {
@@ -72,6 +73,7 @@ struct Plan {  // every choice the launch code makes; the fused kinds leave all 
   bool write_last = false;       // every step writes the latest level-2 record (otherwise only a launch's last one)
   bool step_decode = false;      // k_step_decode<R> takes a part's inner steps: events of step s + decode of step s + 1
   bool step_log = false;         // k_step_batch_log<R, MKT> instead of k_step_batch<R, MKT>: the order log is written
+  bool agents_per_book = false;  // the agents kernel (or k_run_wave) is the <R, PB = true> form that reads the per-unit table
 };
 
 inline bool is_split(PlanKind k) { return k != PL_FUSED_RANDOM && k != PL_FUSED_WAVE && k != PL_MIXED_FUSED; }
@@ -132,6 +134,11 @@ inline Plan make_plan(const PlanInput& in) {
     if (p.kind == PL_FUSED_WAVE) p.kind = PL_SPLIT_WAVE;
     if (p.kind == PL_FUSED_RANDOM) p.kind = PL_SPLIT_LANES;
   }
+  // a per-unit parameter table is read by the PB forms of k_run_wave, k_agents_wave and k_agents_fsm; k_run_random (which
+  // auto picks only on a "fused" request) has none and takes the lane split instead.  k_step_batch reads only the groups'
+  // sizes and assets, which every unit shares.  (bk_warm's scratch steps run the same decoders.)
+  p.agents_per_book = in.per_book && in.groups && !in.n_mixed;
+  if (p.agents_per_book && p.kind == PL_FUSED_RANDOM) p.kind = PL_SPLIT_LANES;
   if (!is_split(p.kind)) return p;
   const bool mixed = p.kind != PL_SPLIT_LANES && p.kind != PL_SPLIT_WAVE;
   const bool wave = p.kind == PL_SPLIT_WAVE || p.kind == PL_MIXED_WAVE;  // (both on independent books only)
@@ -159,7 +166,7 @@ inline Plan make_plan(const PlanInput& in) {
   // launch each - k_step_decode = events of step s + decode of step s + 1)
   // (bk_warm's scratch steps leave the log alone: they run the log-less kernel and the books are put back)
   p.step_log = in.order_log && !in.warming;
-  p.step_decode = in.step_decode && p.kind == PL_SPLIT_WAVE && !in.warming && !p.step_log;
+  p.step_decode = in.step_decode && p.kind == PL_SPLIT_WAVE && !in.warming && !p.step_log && !p.agents_per_book;
   return p;
 }
 

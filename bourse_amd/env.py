@@ -524,6 +524,19 @@ class ManyBookEnv:
         check(self._L.bk_set_random_market_agents(self._h, len(gs), arr, _lib.p32(assets)))
         self.groups = gs
 
+    def set_random_agents_per_book(self, table):
+        """RandomAgents groups whose parameters differ per book (``bk_set_random_agents_per_book``): book ``b`` steps as
+        book ``b`` of an env given ``set_random_agents(table[b])`` does, bit for bit.  ``table`` is a sequence of
+        ``n_books`` group lists shaped like ``set_random_agents``' argument, or a numpy structured array
+        ``(n_books, n_groups)`` of ``RANDOM_AGENTS_DTYPE``.  ``n_agents`` must be the same in every book; tick and
+        volume ranges, tick size and activity rate may differ.  A later ``set_random_agents`` / ``set_agents`` replaces
+        the table."""
+        if self.assets > 1:
+            raise ValueError("markets take set_random_market_agents_per_market")
+        arr = _agents_table(table, self.n_books, lambda g: g.as_tuple() if isinstance(g, RandomAgents) else g)
+        check(self._L.bk_set_random_agents_per_book(self._h, arr.shape[1], arr.ctypes.data_as(C.c_void_p), None))
+        self.groups = None
+
     def set_agents(self, members, assets=None):
         """A ``#[derive(AgentSet)]`` struct: members updated in declaration order (ref crates/macros/src/lib.rs:57-73).
         Each member is a RandomAgents / NoiseAgent / MomentumAgent instance or the equivalent tuple
@@ -931,6 +944,22 @@ class ManyMarketEnv(ManyBookEnv):
         super().modify_order(self.book(market, asset), order_id, new_price, new_vol)
 
 
+    def set_random_market_agents_per_market(self, rows):
+        """RandomMarketAgents groups whose parameters differ per market (``bk_set_random_agents_per_book``): ``rows[m]``
+        is market ``m``'s list of ``(asset, n, tick_range, vol_range, tick_size, rate)`` (or ``RandomMarketAgents``), as
+        ``set_random_market_agents`` takes it; ``asset`` and ``n`` must be the same in every market."""
+        rows = [[g.as_tuple() if isinstance(g, RandomMarketAgents) else tuple(g) for g in row] for row in rows]
+        if len(rows) != self.n_markets:
+            raise ValueError(f"the table needs one row of groups per market: {self.n_markets} rows, got {len(rows)}")
+        if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("every row of the table needs the same number (>= 1) of groups")
+        assets = np.array([int(g[0]) for g in rows[0]], dtype=np.uint32)
+        if any([int(g[0]) for g in r] != list(assets) for r in rows):
+            raise ValueError("the groups' assets must be the same in every market")
+        arr = _agents_table([[g[1:] for g in r] for r in rows], self.n_markets, lambda g: g)
+        check(self._L.bk_set_random_agents_per_book(self._h, arr.shape[1], arr.ctypes.data_as(C.c_void_p), _lib.p32(assets)))
+        self.groups = None
+
     # Market::save_json / load_json (market.rs:367-390): {"order_books": [OrderBook; ASSETS]}
     def market_state(self, market: int, trading: bool = True) -> dict:
         return {"order_books": [self.book_state(self.book(market, a), trading) for a in range(self.assets)]}
@@ -952,6 +981,28 @@ class ManyMarketEnv(ManyBookEnv):
 
         with open(path) as f:
             self.load_market_state(market, json.load(f))
+
+
+def _agents_table(table, n_units: int, as_tuple) -> np.ndarray:
+    """A contiguous (n_units, n_groups) RANDOM_AGENTS_DTYPE array from a structured array or per-unit group lists of
+    ``(n, tick_range, vol_range, tick_size, rate)``; the shape is checked here (ValueError) before the library sees it."""
+    if isinstance(table, np.ndarray) and table.dtype.names is not None:
+        if table.ndim != 2 or table.shape[0] != n_units or table.shape[1] == 0:
+            raise ValueError(f"the table must be (n_units = {n_units}, n_groups >= 1), got {table.shape}")
+        if table.dtype != _lib.RANDOM_AGENTS_DTYPE:
+            table = table.astype(_lib.RANDOM_AGENTS_DTYPE)
+        return np.ascontiguousarray(table)
+    rows = [[as_tuple(g) for g in row] for row in table]
+    if len(rows) != n_units:
+        raise ValueError(f"the table needs one row of groups per unit: {n_units} rows, got {len(rows)}")
+    n_groups = len(rows[0]) if rows else 0
+    if n_groups == 0 or any(len(r) != n_groups for r in rows):
+        raise ValueError("every row of the table needs the same number (>= 1) of groups")
+    arr = np.zeros((n_units, n_groups), dtype=_lib.RANDOM_AGENTS_DTYPE)
+    for u, row in enumerate(rows):
+        for g, (n, tr, vr, ts, rate) in enumerate(row):
+            arr[u, g] = (int(n), int(tr[0]), int(tr[1]), int(vr[0]), int(vr[1]), int(ts), np.float32(rate))
+    return arr
 
 
 def market_sim_runner(env: ManyMarketEnv, agents: Sequence[RandomMarketAgents | tuple], n_steps: int):

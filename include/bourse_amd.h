@@ -260,19 +260,26 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
                  const uint32_t* key_price, const uint64_t* key_time, uint64_t n_trades, const bk_trade* trades);
 
 /* ---------------------------------------------------- on-device order flow */
-/* An AgentSet of RandomAgents groups, identical for every book, updated in declaration order
- * (crates/macros/src/lib.rs:57-73).  Sum of n_agents <= max_live_orders. */
+/* An AgentSet of RandomAgents groups, the same parameters for every book (bk_set_random_agents_per_book: per book),
+ * updated in declaration order (crates/macros/src/lib.rs:57-73).  Sum of n_agents <= max_live_orders. */
 int bk_set_random_agents(bk_env* env, uint32_t n_groups, const bk_random_agents* groups);
 /* Market mode.  Market::new(start_time, tick_size: [Price; ASSETS], trading) — crates/order_book/src/market.rs:74-81:
  * per-asset tick sizes (default: cfg.tick_size for every asset); call before anything else. */
 int bk_set_tick_sizes(bk_env* env, uint32_t n_assets, const uint32_t* tick_sizes);
 /* A MarketAgentSet of RandomMarketAgents groups (RandomMarketAgents::new(asset, n_agents, tick_range, vol_range,
- * tick_size, activity_rate), random_agent.rs:185-201), identical for every market, updated in declaration order with
+ * tick_size, activity_rate), random_agent.rs:185-201), the same for every market (per market: bk_set_random_agents_per_book), updated in declaration order with
  * the market's RNG (market_sim_runner, runner.rs:108-131).  assets[g] = the asset group g trades (NULL: all 0).
  * Sum of n_agents <= max_live_orders.  bk_run() then steps every market; host-driven orders use the per-book calls with
  * book = market * assets + asset (MarketEnv::place_order / cancel_order / modify_order, market_env.rs:163-218). */
 int bk_set_random_market_agents(bk_env* env, uint32_t n_groups, const bk_random_agents* groups,
                                 const uint32_t* assets);
+/* RandomAgents groups whose parameters differ per book (per market when assets > 1): groups[u * n_groups + g] is group g
+ * of unit u, u < n_books / assets.  n_agents (and assets[g]; NULL = all 0) are shared by every unit.  Unit u steps as the
+ * unit of an env given bk_set_random_agents (bk_set_random_market_agents) with row u does, bit for bit.  Every entry is
+ * checked as bk_set_random_market_agents checks one, with the same status codes; the message names the first failing
+ * unit and group; n_agents[g] differing between units is BK_INVALID_ARGUMENT.  On a failure the installed agents stay.
+ * Replaces the installed agent set; a later bk_set_random_agents / bk_set_agents replaces (and frees) the table. */
+int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_random_agents* groups, const uint32_t* assets);
 /* Any mix of built-in members (at most 4 when a Noise/Momentum member is present), identical for every book.
  * Noise/Momentum members price orders with f64 log-normal offsets: their outputs match the CPU oracle bit for bit
  * but only statistically match a Rust build (third-party sampling + libm). */

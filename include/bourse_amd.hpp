@@ -172,6 +172,18 @@ class ManyEnv {
   void set_random_agents(const std::vector<bk_random_agents>& groups) {
     check(bk_set_random_agents(h_, static_cast<uint32_t>(groups.size()), groups.data()));
   }
+  // the same with parameters per book: table[b] is book b's groups (n_agents shared by every book; bk_set_random_agents_per_book)
+  void set_random_agents_per_book(const std::vector<std::vector<bk_random_agents>>& table) {
+    const size_t n_groups = table.empty() ? 0 : table[0].size();
+    if (table.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the table needs one row of groups per book");
+    std::vector<bk_random_agents> flat;
+    flat.reserve(table.size() * n_groups);
+    for (const auto& row : table) {
+      if (row.size() != n_groups) throw Error(BK_INVALID_ARGUMENT, "every row of the table needs the same number of groups");
+      flat.insert(flat.end(), row.begin(), row.end());
+    }
+    check(bk_set_random_agents_per_book(h_, static_cast<uint32_t>(n_groups), flat.data(), nullptr));
+  }
   // record the agents' orders (bk_set_agent_order_log; before the first run): env(b).get_orders() answers after run
   void enable_agent_order_log() { check(bk_set_agent_order_log(h_, 1)); }
   void run(uint64_t n_steps) {
