@@ -133,6 +133,7 @@ SIGNATURES = {
     "bk_set_random_market_agents": (_i32, [_vp, _u32, C.POINTER(RandomAgentsCfg), _p32]),
     "bk_set_random_agents_per_book": (_i32, [_vp, _u32, _vp, _p32]),
     "bk_set_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc)]),
+    "bk_set_agents_per_book": (_i32, [_vp, _u32, C.POINTER(AgentDesc), _p32]),
     "bk_set_market_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc), _p32]),
     "bk_run": (_i32, [_vp, _u64]),
     "bk_l2_width": (_u32, [_vp]),

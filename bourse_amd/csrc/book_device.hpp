@@ -51,7 +51,7 @@ enum Hdr : int {
 constexpr int HDR_SCALARS = 20;  // header dwords 0 .. 19: every scalar field a step reads (Hdr, up to H_TRADE_BASE_HI)
 constexpr int POOL_FIELDS = 5;  // price, vol, id, seq, meta(bit0 live, bit1 bid, bit2 pending New, bits 8..15 owner tag)
 constexpr int MAX_GROUPS = 8;
-constexpr int MAX_ASSETS = 8;  // books per market (MarketEnv<ASSETS>)
+// (MAX_ASSETS: agent_table.hpp)
 
 constexpr uint32_t FLAG_POOL_OVERFLOW = 1u, FLAG_TRADE_OVERFLOW = 2u, FLAG_STEP_SIZE = 4u,
                    FLAG_ORDER_LOG_FULL = 8u, FLAG_UNKNOWN_ORDER = 16u, FLAG_HIST_OVERFLOW = 32u, FLAG_PRICE_TICK = 64u,

@@ -66,12 +66,6 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-uint64_t fnv1a(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
-  const unsigned char* c = static_cast<const unsigned char*>(p);
-  for (size_t i = 0; i < n; ++i) h = (h ^ c[i]) * 1099511628211ull;
-  return h;
-}
-
 #define HIPCHK(expr)                                                                              \
   do {                                                                                            \
     hipError_t _e = (expr);                                                                       \
@@ -156,6 +150,11 @@ struct bk_env {
   DevBuf<unsigned long long> tr_off;
   uint64_t tr_total = 0;
   DevBuf<MixedDesc> mixed_descs;  // AgentSets with Noise/Momentum members (k_run_mixed)
+  // bk_set_agents_per_book: the per-unit table of the members (unit u = book u, or market u), mtable[u * n_mixed + i], on
+  // the host (the hash) and on the device (the PB kernels); mixed_descs then holds unit 0's row, whose kinds, sizes and
+  // assets every unit shares (what k_mixed_lists_rebuild / k_wave_lists_rebuild read)
+  std::vector<MixedDesc> mtable;
+  DevBuf<MixedDesc> dmtable;
   uint32_t n_mixed = 0, n_fixed = 0;
   // lane-per-book members' update (k_agents_mixed_lanes): the members' order lists, [member][entry][book]
   DevBuf<uint16_t> ml_list;
@@ -555,6 +554,10 @@ int prepare_launch(bk_env* env, const Plan& pl, const DevArgs& a0, WaveArgs* wva
                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, true))));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_lds_bytes(R, false))));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, true, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_pb_lds_bytes(R, true))));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_lanes<R, false, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_lanes_pb_lds_bytes(R, false))));
         env->lds_attr_set = true;
       }
       if (!env->ml_valid) {
@@ -576,6 +579,8 @@ int prepare_launch(bk_env* env, const Plan& pl, const DevArgs& a0, WaveArgs* wva
       if (!env->mw_attr_set) {  // > 64 KB of dynamic LDS at R = 8 (160 KB per workgroup on MI355X); per device
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_wave<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(mixed_wave_lds_bytes(R))));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agents_mixed_wave<R, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(mixed_wave_lds_bytes(R))));
         env->mw_attr_set = true;
       }
       if (!env->wl_list.p) {
@@ -617,7 +622,10 @@ int launch_fused(bk_env* env, const Plan& pl, const DevArgs& a, const WaveArgs& 
   const uint32_t nb = env->cfg.n_books;
   env->prof_now = env->profile > 0;
   ProfScope ps(env, 0);
-  if (pl.kind == PL_MIXED_FUSED)
+  if (pl.kind == PL_MIXED_FUSED && pl.members_per_book)
+    hipLaunchKernelGGL((k_run_mixed<R, true>), dim3((nb + 3) / 4), dim3(256), 0, env->stream, a, env->margs(), first_step, n_steps,
+                       static_cast<const MixedDesc*>(env->dmtable.p));
+  else if (pl.kind == PL_MIXED_FUSED)
     hipLaunchKernelGGL(k_run_mixed<R>, dim3((nb + 3) / 4), dim3(256), 0, env->stream, a, env->margs(), first_step, n_steps);
   else if (pl.kind == PL_FUSED_WAVE && pl.agents_per_book)
     hipLaunchKernelGGL((k_run_wave<R, true>), dim3((nb + 7) / 8), dim3(512), 0, env->stream, a, wva, first_step, n_steps,
@@ -638,6 +646,7 @@ int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs&
   const uint32_t M = env->M;
   const uint32_t B = env->cfg.n_books / M;  // units the parts are cut in: books, or markets of M books
   const Group* table = env->dtable.p;        // (pl.agents_per_book: the per-unit table)
+  const MixedDesc* mtable = env->dmtable.p;  // (pl.members_per_book: the members' per-unit table)
   const int P = pl.parts;  // (small batches: one part on the caller's stream)
   if (P > 1) {
     if (int rc = prepare_parts(env)) return rc;
@@ -661,10 +670,22 @@ int launch_split(bk_env* env, const Plan& pl, const DevArgs& a0, const WaveArgs&
           HIPCHK(hipStreamWaitEvent(st, env->ev_first[i - 1], 0));
       }
       const uint64_t step_no = first_step + s;
-      if (pl.agents == AG_MIXED_WAVE)
+      if (pl.agents == AG_MIXED_WAVE && pl.members_per_book)
+        launch_timed(env, 1, &k_agents_mixed_wave<R, true>, dim3((nb + MW_WPB - 1) / MW_WPB), dim3(64 * MW_WPB),
+                     static_cast<uint32_t>(mixed_wave_lds_bytes(R)), st, a, ma, wva,
+                     WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u}, mtable);
+      else if (pl.agents == AG_MIXED_WAVE)
         launch_timed(env, 1, &k_agents_mixed_wave<R>, dim3((nb + MW_WPB - 1) / MW_WPB), dim3(64 * MW_WPB),
                      static_cast<uint32_t>(mixed_wave_lds_bytes(R)), st, a, ma, wva,
                      WaveLists{env->wl_list.p, env->wl_len.p, static_cast<uint32_t>(R) * 64u});
+      else if (pl.agents == AG_MIXED_LANES_MKT && pl.members_per_book)
+        launch_timed(env, 1, &k_agents_mixed_lanes<R, true, true>, dim3((nb + 63) / 64), dim3(64), mixed_lanes_pb_lds_bytes(R, true),
+                     st, a, ma, ml, mtable);
+      else if (pl.agents == AG_MIXED_LANES && pl.members_per_book)
+        launch_timed(env, 1, &k_agents_mixed_lanes<R, false, true>, dim3((nb + 63) / 64), dim3(64),
+                     mixed_lanes_pb_lds_bytes(R, false), st, a, ma, ml, mtable);
+      else if (pl.agents == AG_MIXED_WPB && pl.members_per_book)
+        launch_timed(env, 1, &k_agents_mixed<R, true>, dim3((nb + 3) / 4), dim3(256), 0u, st, a, ma, mtable);
       else if (pl.agents == AG_MIXED_LANES_MKT)
         launch_timed(env, 1, &k_agents_mixed_lanes<R, true>, dim3((nb + 63) / 64), dim3(64), mixed_lanes_lds_bytes(R, true), st, a,
                      ma, ml);
@@ -1587,6 +1608,8 @@ int bk_set_random_market_agents(bk_env* env, uint32_t n_groups, const bk_random_
   env->n_mixed = 0;
   env->table.clear();  // (replaces a per-unit table)
   (void)env->dtable.alloc(0);
+  env->mtable.clear();  // (and a members' table)
+  (void)env->dmtable.alloc(0);
   env->agents_hash = gs.empty() ? 0 : groups_hash(gs.data(), gs.size());
   return BK_OK;
 }
@@ -1614,6 +1637,8 @@ int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_rando
   env->table.swap(t);
   env->n_agents_total = static_cast<uint32_t>(total);
   env->n_mixed = 0;
+  env->mtable.clear();
+  (void)env->dmtable.alloc(0);
   env->agents_hash = groups_hash(env->table.data(), env->table.size());
   return BK_OK;
 }
@@ -1635,6 +1660,8 @@ int bk_set_tick_sizes(bk_env* env, uint32_t n, const uint32_t* tick_sizes) {
 }
 
 static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets);
+static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32_t n_members, const uint32_t* assets,
+                           const uint32_t* fixed_a, std::vector<MixedDesc> table);
 
 int bk_set_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* members) {
   if (!env || (!members && n_members)) return fail(BK_INVALID_ARGUMENT, "null argument");
@@ -1667,55 +1694,24 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
                                      "a set with Noise / Momentum members cannot be installed on a logging env");
   if (int rc = use_device(env)) return rc;
   std::vector<MixedDesc> ds(n_members);
-  uint32_t fixed_a[MAX_ASSETS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t i = 0; i < n_members; ++i) {
-    const uint32_t as = assets ? assets[i] : 0u;
-    uint32_t& fixed = fixed_a[as];  // fixed RandomAgents slots are counted per book
-    const bk_agent_desc& m = members[i];
-    MixedDesc& D = ds[i];
-    std::memset(&D, 0, sizeof(D));
-    D.type = m.type;
-    D.n = m.n_agents;
-    if (m.tick_size == 0 || m.tick_size % env->asset_tick[as] != 0)
-      return fail(BK_PRICE_NOT_TICK_MULTIPLE, "member tick_size must be a non-zero multiple of the env tick_size");
-    if (m.type == BK_AGENT_RANDOM) {
-      if (m.tick_lo >= m.tick_hi || m.vol_lo >= m.vol_hi || m.tick_lo == 0 ||
-          static_cast<uint64_t>(m.tick_hi - 1) * m.tick_size >= 0xFFFFFFFFull)
-        return fail(BK_INVALID_ARGUMENT, "bad RandomAgents ranges");
-      D.thr = activity_threshold(m.activity_rate);
-      D.tick_lo = m.tick_lo;
-      D.tick_rng = m.tick_hi - m.tick_lo;
-      D.tick_zone = sample_zone(D.tick_rng);
-      D.vol_lo = m.vol_lo;
-      D.vol_rng = m.vol_hi - m.vol_lo;
-      D.vol_zone = sample_zone(D.vol_rng);
-      D.tick_size = m.tick_size;
-      D.slot_base = fixed;
-      fixed += m.n_agents;
-    } else if (m.type == BK_AGENT_NOISE || m.type == BK_AGENT_MOMENTUM) {
-      if (m.n_agents > 0xFFFFu) return fail(BK_INVALID_ARGUMENT, "n_agents is a u16 in the reference");
-      if (!(m.price_dist_sigma >= 0.0) || !std::isfinite(m.price_dist_sigma) || !std::isfinite(m.price_dist_mu))
-        return fail(BK_INVALID_ARGUMENT, "LogNormal::new(mu, sigma) needs finite mu and sigma >= 0");  // .unwrap()
-      D.thr_limit = activity_threshold(m.p_limit);
-      D.thr_market = activity_threshold(m.p_market);
-      D.keep_thr = keep_threshold(m.p_cancel);
-      D.trade_vol = m.trade_vol;
-      D.mu = m.price_dist_mu;
-      D.sigma = m.price_dist_sigma;
-      D.decay = m.decay;
-      D.demand = m.demand;
-      D.scale = m.scale;
-      D.order_ratio = m.order_ratio;
-      D.n_f = static_cast<double>(m.n_agents);
-      D.tick_f = static_cast<double>(m.tick_size);
-    } else {
-      return fail(BK_INVALID_ARGUMENT, "unknown agent type");
-    }
+  uint32_t fixed_a[MAX_ASSETS];
+  std::string msg;
+  if (int rc = make_mixed_descs(members, n_members, assets, env->asset_tick, ds.data(), fixed_a, &msg))  // (agent_table.hpp)
+    return fail(rc, msg);
+  if (!mixed_capacity_ok(fixed_a, env->M, env->cfg.max_live_orders)) return fail(BK_CAPACITY, MIXED_CAPACITY_MSG);
+  return install_members(env, ds, n_members, assets, fixed_a, {});
+}
+
+// The members' records into the env: `ds` = the (shared) row every unit's kernels and the list rebuilds read, `table` =
+// the per-unit table of bk_set_agents_per_book (empty: the uniform set).  Replaces whatever agents were installed.
+static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32_t n_members, const uint32_t* assets,
+                           const uint32_t* fixed_a, std::vector<MixedDesc> table) {
+  DevBuf<MixedDesc> dt;
+  if (!table.empty()) {
+    HIPCHK(dt.alloc(table.size()));
+    HIPCHK(hipMemcpy(dt.p, table.data(), table.size() * sizeof(MixedDesc), hipMemcpyHostToDevice));
   }
   uint32_t fixed = fixed_a[0];
-  for (uint32_t as = 0; as < env->M; ++as)
-    if (fixed_a[as] >= env->cfg.max_live_orders)
-      return fail(BK_CAPACITY, "RandomAgents members leave no pool slots for the other members' orders");
   HIPCHK(env->mixed_descs.alloc(n_members));
   HIPCHK(hipMemcpy(env->mixed_descs.p, ds.data(), ds.size() * sizeof(MixedDesc), hipMemcpyHostToDevice));
   env->n_mixed = n_members;
@@ -1728,8 +1724,49 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
   env->table.clear();
   (void)env->dtable.alloc(0);
   env->n_agents_total = 0;
-  env->agents_hash = fnv1a(env->member_asset, sizeof(env->member_asset), fnv1a(ds.data(), ds.size() * sizeof(MixedDesc)));
+  std::swap(env->dmtable.p, dt.p);  // (the previous table, if any, is freed with `dt`)
+  std::swap(env->dmtable.n, dt.n);
+  env->mtable.swap(table);
+  env->agents_hash = env->mtable.empty() ? mixed_hash(env->member_asset, ds.data(), ds.size())
+                                         : mixed_hash(env->member_asset, env->mtable.data(), env->mtable.size());
   return BK_OK;
+}
+
+// Noise / Momentum (and RandomAgents) members whose parameters differ per unit (book, or market when assets > 1): every
+// row is checked and preprocessed as set_agents_impl does one (agent_table.hpp make_mixed_table); unit 0's row is the
+// env's shared row (the members' kinds, sizes and assets, which every unit shares), the table goes to the device, where
+// the PB forms of k_run_mixed / k_agents_mixed / k_agents_mixed_wave / k_agents_mixed_lanes read unit u's row.  An
+// all-RandomAgents table is bk_set_random_agents_per_book's.  Nothing changes on a failure.
+int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets) {
+  if (!env || (!members && n_members)) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (n_members == 0) return fail(BK_INVALID_ARGUMENT, "a per-unit table needs at least one member");
+  if (env->M > 1 && !assets) return fail(BK_INVALID_ARGUMENT, "markets (assets > 1) need the members' assets");
+  for (uint32_t i = 0; assets && i < n_members; ++i)
+    if (assets[i] >= env->M) return fail(BK_INVALID_ARGUMENT, "member asset index out of range");
+  const uint32_t n_units = env->cfg.n_books / env->M;
+  const size_t n = static_cast<size_t>(n_units) * n_members;
+  bool all_random = true;
+  for (size_t k = 0; k < n; ++k) all_random = all_random && members[k].type == BK_AGENT_RANDOM;
+  if (all_random) {
+    std::vector<bk_random_agents> g(n);
+    for (size_t k = 0; k < n; ++k)
+      g[k] = bk_random_agents{members[k].n_agents, members[k].tick_lo, members[k].tick_hi, members[k].vol_lo,
+                              members[k].vol_hi, members[k].tick_size, members[k].activity_rate};
+    return bk_set_random_agents_per_book(env, n_members, g.data(), assets);
+  }
+  if (n_members > MAX_MEMBERS) return fail(BK_INVALID_ARGUMENT, "at most 4 members in a set with Noise/Momentum agents");
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "the agents' order log (bk_set_agent_order_log) records RandomAgents only: "
+                                     "a set with Noise / Momentum members cannot be installed on a logging env");
+  std::vector<MixedDesc> t;
+  uint32_t fixed_a[MAX_ASSETS];
+  std::string msg;
+  if (int rc = make_mixed_table(members, n_units, n_members, assets, env->M, env->asset_tick, env->cfg.max_live_orders, t,
+                                fixed_a, &msg))
+    return fail(rc, msg);
+  if (int rc = use_device(env)) return rc;
+  const std::vector<MixedDesc> row0(t.begin(), t.begin() + n_members);
+  return install_members(env, row0, n_members, assets, fixed_a, std::move(t));
 }
 
 // books one residency round of the fused wave kernel holds (the auto rule's `wave` limit): asked of the runtime once
@@ -1751,7 +1788,7 @@ static void query_fused_resident(bk_env* env) {
 static Plan env_plan(bk_env* env) {
   PlanInput in{env->R, env->cfg.n_books, env->M, !env->groups.empty(), env->n_mixed, env->pipeline, env->n_parts, env->wave_parts,
                env->min_part, env->fused_resident, env->stagger_us, env->warming, env->step_decode, env->agent_log,
-               !env->table.empty()};
+               !env->table.empty(), !env->mtable.empty()};
   if (!in.fused_resident && random_books(in)) {
     query_fused_resident(env);
     in.fused_resident = env->fused_resident;

@@ -46,6 +46,7 @@ struct PlanInput {                // what the rule reads of an env
   bool warming = false, step_decode = false;  // bk_warm's scratch steps; BOURSE_AMD_STEP_DECODE
   bool order_log = false;         // bk_set_agent_order_log: the agents' orders are logged (only the split kinds can)
   bool per_book = false;          // bk_set_random_agents_per_book: the groups' parameters come from a per-unit table
+  bool members_per_book = false;  // bk_set_agents_per_book: the AgentSet members' parameters come from a per-unit table
 };
 
 enum PlanKind {
@@ -74,6 +75,8 @@ struct Plan {  // every choice the launch code makes; the fused kinds leave all 
   bool step_decode = false;      // k_step_decode<R> takes a part's inner steps: events of step s + decode of step s + 1
   bool step_log = false;         // k_step_batch_log<R, MKT> instead of k_step_batch<R, MKT>: the order log is written
   bool agents_per_book = false;  // the agents kernel (or k_run_wave) is the <R, PB = true> form that reads the per-unit table
+  bool members_per_book = false;  // the members' kernel (k_run_mixed or a mixed agents kernel) is its PB form that reads
+                                  // the members' per-unit table
 };
 
 inline bool is_split(PlanKind k) { return k != PL_FUSED_RANDOM && k != PL_FUSED_WAVE && k != PL_MIXED_FUSED; }
@@ -139,6 +142,8 @@ inline Plan make_plan(const PlanInput& in) {
   // sizes and assets, which every unit shares.  (bk_warm's scratch steps run the same decoders.)
   p.agents_per_book = in.per_book && in.groups && !in.n_mixed;
   if (p.agents_per_book && p.kind == PL_FUSED_RANDOM) p.kind = PL_SPLIT_LANES;
+  // the members' per-unit table: every mixed kind has a PB form, so nothing else of the plan changes
+  p.members_per_book = in.members_per_book && in.n_mixed > 0;
   if (!is_split(p.kind)) return p;
   const bool mixed = p.kind != PL_SPLIT_LANES && p.kind != PL_SPLIT_WAVE;
   const bool wave = p.kind == PL_SPLIT_WAVE || p.kind == PL_MIXED_WAVE;  // (both on independent books only)

@@ -541,38 +541,41 @@ class ManyBookEnv:
         """A ``#[derive(AgentSet)]`` struct: members updated in declaration order (ref crates/macros/src/lib.rs:57-73).
         Each member is a RandomAgents / NoiseAgent / MomentumAgent instance or the equivalent tuple
         ``("random", n, tick_range, vol_range, tick_size, rate)`` / ``("noise"|"momentum", id_start, n, params_dict)``."""
-        ms = []
-        for m in members:
-            if isinstance(m, RandomAgents):
-                ms.append(("random",) + m.as_tuple())
-            elif isinstance(m, (NoiseAgent, MomentumAgent)):
-                ms.append(m.as_tuple())
-            else:
-                ms.append(tuple(m))
+        ms = [_member_tuple(m) for m in members]
         arr = (AgentDesc * max(len(ms), 1))()
         for i, m in enumerate(ms):
-            d = arr[i]
-            if m[0] == "random":
-                _, n, tr, vr, ts, rate = m
-                d.type, d.n_agents, d.tick_size, d.activity_rate = 0, int(n), int(ts), float(np.float32(rate))
-                d.tick_lo, d.tick_hi, d.vol_lo, d.vol_hi = int(tr[0]), int(tr[1]), int(vr[0]), int(vr[1])
-            else:
-                kind, start, n, p = m
-                d.type = 1 if kind == "noise" else 2
-                d.agent_id_start, d.n_agents, d.tick_size = int(start), int(n), int(p["tick_size"])
-                d.p_cancel, d.trade_vol = float(np.float32(p["p_cancel"])), int(p["trade_vol"])
-                d.price_dist_mu, d.price_dist_sigma = float(p["price_dist_mu"]), float(p["price_dist_sigma"])
-                if kind == "noise":
-                    d.p_limit, d.p_market = float(np.float32(p["p_limit"])), float(np.float32(p["p_market"]))
-                else:
-                    d.decay, d.demand = float(p["decay"]), float(p["demand"])
-                    d.scale, d.order_ratio = float(p["scale"]), float(p["order_ratio"])
+            _fill_agent_desc(arr[i], m)
         if assets is not None:
             as_arr = np.asarray(list(assets), dtype=np.uint32)
             check(self._L.bk_set_market_agents(self._h, len(ms), arr, _lib.p32(as_arr)))
         else:
             check(self._L.bk_set_agents(self._h, len(ms), arr))
         self.members = ms
+
+    def set_agents_per_book(self, table):
+        """AgentSet members whose parameters differ per book (``bk_set_agents_per_book``): book ``b`` steps as book ``b``
+        of an env given ``set_agents(table[b])`` does, bit for bit.  ``table`` holds ``n_books`` member lists in
+        ``set_agents``' tuple or instance format.  The members' kinds and ``n`` must be the same in every book; every
+        other parameter may differ.  A later ``set_agents`` / ``set_random_agents`` / ``set_random_agents_per_book``
+        replaces the table."""
+        if self.assets > 1:
+            raise ValueError("markets take set_market_agents_per_market")
+        self._set_members_table(table, self.n_books, None)
+
+    def _set_members_table(self, table, n_units: int, assets):
+        rows = [[_member_tuple(m) for m in row] for row in table]
+        if len(rows) != n_units:
+            raise ValueError(f"the table needs one row of members per unit: {n_units} rows, got {len(rows)}")
+        n = len(rows[0]) if rows else 0
+        if n == 0 or any(len(r) != n for r in rows):
+            raise ValueError("every row of the table needs the same number (>= 1) of members")
+        arr = (AgentDesc * (n_units * n))()
+        for u, row in enumerate(rows):
+            for i, m in enumerate(row):
+                _fill_agent_desc(arr[u * n + i], m)
+        as_arr = None if assets is None else np.asarray(assets, dtype=np.uint32)
+        check(self._L.bk_set_agents_per_book(self._h, n, arr, None if as_arr is None else _lib.p32(as_arr)))
+        self.members = None
 
     def set_market_agents(self, members):
         """A ``#[derive(MarketAgentSet)]`` struct: ``[(asset, member), ...]`` with members as in ``set_agents`` — the
@@ -960,6 +963,20 @@ class ManyMarketEnv(ManyBookEnv):
         check(self._L.bk_set_random_agents_per_book(self._h, arr.shape[1], arr.ctypes.data_as(C.c_void_p), _lib.p32(assets)))
         self.groups = None
 
+    def set_market_agents_per_market(self, rows):
+        """MarketAgentSet members whose parameters differ per market (``bk_set_agents_per_book``): ``rows[m]`` is market
+        ``m``'s ``[(asset, member), ...]`` list as ``set_market_agents`` takes it; each member's asset, kind and ``n`` must
+        be the same in every market."""
+        rows = [list(r) for r in rows]
+        if len(rows) != self.n_markets:
+            raise ValueError(f"the table needs one row of members per market: {self.n_markets} rows, got {len(rows)}")
+        if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("every row of the table needs the same number (>= 1) of members")
+        assets = [int(a) for a, _ in rows[0]]
+        if any([int(a) for a, _ in r] != assets for r in rows):
+            raise ValueError("the members' assets must be the same in every market")
+        self._set_members_table([[m for _, m in r] for r in rows], self.n_markets, assets)
+
     # Market::save_json / load_json (market.rs:367-390): {"order_books": [OrderBook; ASSETS]}
     def market_state(self, market: int, trading: bool = True) -> dict:
         return {"order_books": [self.book_state(self.book(market, a), trading) for a in range(self.assets)]}
@@ -981,6 +998,34 @@ class ManyMarketEnv(ManyBookEnv):
 
         with open(path) as f:
             self.load_market_state(market, json.load(f))
+
+
+def _member_tuple(m) -> tuple:
+    """An AgentSet member in ``set_agents``' tuple format: ``("random", n, tick_range, vol_range, tick_size, rate)`` or
+    ``("noise"|"momentum", id_start, n, params_dict)``."""
+    if isinstance(m, RandomAgents):
+        return ("random",) + m.as_tuple()
+    if isinstance(m, (NoiseAgent, MomentumAgent)):
+        return m.as_tuple()
+    return tuple(m)
+
+
+def _fill_agent_desc(d, m: tuple):
+    if m[0] == "random":
+        _, n, tr, vr, ts, rate = m
+        d.type, d.n_agents, d.tick_size, d.activity_rate = 0, int(n), int(ts), float(np.float32(rate))
+        d.tick_lo, d.tick_hi, d.vol_lo, d.vol_hi = int(tr[0]), int(tr[1]), int(vr[0]), int(vr[1])
+    else:
+        kind, start, n, p = m
+        d.type = 1 if kind == "noise" else 2
+        d.agent_id_start, d.n_agents, d.tick_size = int(start), int(n), int(p["tick_size"])
+        d.p_cancel, d.trade_vol = float(np.float32(p["p_cancel"])), int(p["trade_vol"])
+        d.price_dist_mu, d.price_dist_sigma = float(p["price_dist_mu"]), float(p["price_dist_sigma"])
+        if kind == "noise":
+            d.p_limit, d.p_market = float(np.float32(p["p_limit"])), float(np.float32(p["p_market"]))
+        else:
+            d.decay, d.demand = float(p["decay"]), float(p["demand"])
+            d.scale, d.order_ratio = float(p["scale"]), float(p["order_ratio"])
 
 
 def _agents_table(table, n_units: int, as_tuple) -> np.ndarray:

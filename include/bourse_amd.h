@@ -288,6 +288,15 @@ int bk_set_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* members)
  * (random_agent.rs:164-247, noise_agent.rs:226-340, momentum_agent.rs:282-397); member i trades asset assets[i] of every
  * market and draws from the market's RNG in declaration order. */
 int bk_set_market_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets);
+/* AgentSet (MarketAgentSet) members whose parameters differ per book (per market when assets > 1): members[u * n_members
+ * + i] is member i of unit u, u < n_books / assets.  assets[i] as in bk_set_market_agents: NULL on independent books,
+ * required on markets.  type, n_agents and assets[i] are shared by every unit; every other field may differ.  Unit u
+ * steps as the unit of an env given bk_set_agents (bk_set_market_agents) with row u does, bit for bit.  Every entry is
+ * checked as bk_set_agents checks one, with the same status codes; the message names the first failing unit and member;
+ * type or n_agents differing between units is BK_INVALID_ARGUMENT.  An all-RandomAgents table is
+ * bk_set_random_agents_per_book's.  On a failure the installed agents stay.  Replaces the installed agent set; a later
+ * bk_set_agents / bk_set_random_agents / bk_set_random_agents_per_book replaces (and frees) the table. */
+int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets);
 /* sim_runner's loop body n_steps times for every book: agents.update(env, rng); env.step(rng)
  * (crates/step_sim/src/runner.rs:53-68), sharing each book's RNG between agents and shuffle. */
 int bk_run(bk_env* env, uint64_t n_steps);

@@ -184,6 +184,19 @@ class ManyEnv {
     }
     check(bk_set_random_agents_per_book(h_, static_cast<uint32_t>(n_groups), flat.data(), nullptr));
   }
+  // AgentSet members with parameters per book: table[b] is book b's members (kinds and n_agents shared by every book;
+  // bk_set_agents_per_book)
+  void set_agents_per_book(const std::vector<std::vector<bk_agent_desc>>& table) {
+    const size_t n_members = table.empty() ? 0 : table[0].size();
+    if (table.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the table needs one row of members per book");
+    std::vector<bk_agent_desc> flat;
+    flat.reserve(table.size() * n_members);
+    for (const auto& row : table) {
+      if (row.size() != n_members) throw Error(BK_INVALID_ARGUMENT, "every row of the table needs the same number of members");
+      flat.insert(flat.end(), row.begin(), row.end());
+    }
+    check(bk_set_agents_per_book(h_, static_cast<uint32_t>(n_members), flat.data(), nullptr));
+  }
   // record the agents' orders (bk_set_agent_order_log; before the first run): env(b).get_orders() answers after run
   void enable_agent_order_log() { check(bk_set_agent_order_log(h_, 1)); }
   void run(uint64_t n_steps) {
