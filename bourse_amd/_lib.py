@@ -119,6 +119,7 @@ SIGNATURES = {
     "bk_device_ingress_enable": (_i32, [_vp, _u32]),
     "bk_submit_instructions_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bk_step_async": (_i32, [_vp]),
+    "bk_update_agents": (_i32, [_vp]),
     "bk_ingress_staging": (_i32, [_vp, _u64, C.POINTER(IngressArrays)]),
     "bk_submit_instructions_host": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _p64]),
     "bk_submit_result": (_i32, [_vp, _u64, _vp, _vp, _p32]),

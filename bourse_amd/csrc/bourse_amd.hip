@@ -46,6 +46,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "wave_agents.hpp"
 #include "wave_mixed.hpp"
 #include "step_events.hpp"
+#include "agents_ingress.hpp"
 
 using namespace bkd;
 
@@ -201,6 +202,11 @@ struct bk_env {
   DevBuf<uint4> dq, dorders;       // [n_markets][qcap] event records; [n_books][max_orders][2] immutable halves
   DevBuf<uint32_t> dqlen;          // [n_markets] queue lengths
   uint64_t ingest_epoch = 0;       // bumped by every submit / step: invalidates the readers' mirrors
+  // bk_update_agents: the RandomAgents' held order ids [n_books][n_agents_total] and, for the uniform set, its groups on the
+  // device; re-made (all None) at the first bk_update_agents after a bk_set_random_agents* call
+  DevBuf<uint32_t> agent_held;
+  DevBuf<Group> agent_groups;
+  bool agent_held_stale = true;
   // bk_set_agent_order_log: bk_run's RandomAgents record their orders in dorders / order_log (k_step_batch_log); the
   // readers mirror them like the device ingress's
   bool agent_log = false;
@@ -1554,6 +1560,55 @@ int bk_step_async(bk_env* env) {
   return BK_OK;
 }
 
+// agents.update(env, rng) (random_agent.rs:85-119) of the installed RandomAgents for every book, into the device-resident
+// queues at this point of the book's stream (agents_ingress.hpp k_update_agents), asynchronous on the env's stream.  The
+// agents only place and cancel: they never queue a modification, so k_ingest's hint for k_step_events stays as it is.
+int bk_update_agents(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_agents queues the agents' orders in the device-resident queues: call "
+                                     "bk_device_ingress_enable first");
+  if (env->M > 1) return fail(BK_INVALID_ARGUMENT, "bk_update_agents runs RandomAgents on independent books (assets == 1)");
+  if (env->n_mixed)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_agents runs RandomAgents only: this env has an AgentSet with Noise / "
+                                     "Momentum members");
+  if (env->groups.empty()) return fail(BK_INVALID_ARGUMENT, "no RandomAgents groups installed (bk_set_random_agents)");
+  if (int rc = use_device(env)) return rc;
+  const uint32_t B = env->cfg.n_books, NA = env->n_agents_total;
+  if (env->agent_held_stale) {  // agents (re)installed: every agent holds None; the old orders stay on the books, unowned
+    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
+    HIPCHK(env->agent_held.alloc(static_cast<size_t>(B) * NA));
+    if (NA) HIPCHK(hipMemset(env->agent_held.p, 0xFF, static_cast<size_t>(B) * NA * 4));
+    if (env->table.empty()) {
+      HIPCHK(env->agent_groups.alloc(env->groups.size()));
+      HIPCHK(hipMemcpy(env->agent_groups.p, env->groups.data(), env->groups.size() * sizeof(Group), hipMemcpyHostToDevice));
+    } else {
+      HIPCHK(env->agent_groups.alloc(0));
+    }
+    env->agent_held_stale = false;
+  }
+  AgentsIngressArgs g{};
+  g.state = env->state.p;
+  g.state_stride = env->stride;
+  g.n_agents = NA;
+  g.log_cap = env->cfg.max_orders;
+  g.qcap = env->qcap;
+  g.groups = env->table.empty() ? env->agent_groups.p : env->dtable.p;
+  g.g_stride = env->table.empty() ? 0u : static_cast<uint32_t>(env->groups.size());
+  g.held = env->agent_held.p;
+  g.q = env->dq.p;
+  g.qlen = env->dqlen.p;
+  g.dorders = env->dorders.p;
+  g.order_log = env->order_log.p;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(k_update_agents<decltype(r)::value>, dim3(B), dim3(64), 0, env->stream, g);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;
+  return BK_OK;
+}
+
 int bk_order_status(bk_env* env, uint32_t book, uint64_t order_id, uint8_t* out_status) {
   if (int rc = check_book(env, book)) return rc;
   if (int rc = mirror_orders(env, book)) return rc;
@@ -1611,6 +1666,7 @@ int bk_set_random_market_agents(bk_env* env, uint32_t n_groups, const bk_random_
   env->mtable.clear();  // (and a members' table)
   (void)env->dmtable.alloc(0);
   env->agents_hash = gs.empty() ? 0 : groups_hash(gs.data(), gs.size());
+  env->agent_held_stale = true;  // (a new RandomAgents::new: the agents hold nothing)
   return BK_OK;
 }
 
@@ -1640,6 +1696,7 @@ int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_rando
   env->mtable.clear();
   (void)env->dmtable.alloc(0);
   env->agents_hash = groups_hash(env->table.data(), env->table.size());
+  env->agent_held_stale = true;
   return BK_OK;
 }
 

@@ -314,6 +314,18 @@ class ManyBookEnv:
         if self.strict:
             self.raise_on_flags()
 
+    def update_agents(self, sync: bool = True):
+        """``agents.update(env, rng)`` (random_agent.rs:85-119) of the installed RandomAgents for every book into the
+        device-resident queues (``bk_update_agents``): the agents' placements and cancellations join the submitted
+        instructions in call order, drawn from the book's own RNG, and the next ``step()`` trades all of it.  Needs
+        ``enable_device_ingress()`` first, then ``set_random_agents`` / ``set_random_agents_per_book``.  ``sync=False``:
+        queue it on the env's stream and return (no flag check), like ``step(sync=False)``."""
+        check(self._L.bk_update_agents(self._h))
+        if sync:
+            self.sync()
+            if self.strict:
+                self.raise_on_flags()
+
     # ------------------------------------------------------------ device-resident instruction ingress
     def enable_device_ingress(self, queue_capacity: int = 256):
         """Switch this (fresh) env to instructions submitted FROM DEVICE MEMORY (``bk_device_ingress_enable``): at most

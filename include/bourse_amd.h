@@ -212,6 +212,18 @@ int bk_submit_instructions_device(bk_env* env, const uint64_t* book_offsets_dev,
                                   const uint32_t* price_dev, const uint64_t* order_id_dev, uint64_t* out_ids_dev,
                                   uint32_t* status_dev);
 int bk_step_async(bk_env* env);
+/* bk_update_agents: agents.update(env, rng) of the installed RandomAgents groups for every book (random_agent.rs:85-119) on
+ * an env with the device ingress, so that background agents and submitted instructions trade in one env as in the
+ * reference.  For each agent, in declaration order, with the book's own RNG (the one the step shuffles with): draw
+ * gen::<f32>(); if active and its held order is Active (resting in the book right now), queue its cancellation and hold
+ * nothing; else if active, draw side, tick and volume, create the order (next id of the book, trader id = the agent's
+ * index in its group) and queue it.  The events are appended to the same queues as bk_submit_instructions_device's, in
+ * call order: update-then-submit and submit-then-update are both valid and each equals the reference called in that
+ * order (as do two bk_update_agents in one step).  Every bk_set_random_agents* call resets the held orders to None (the
+ * old orders stay on the books, unowned).  A full queue or an exhausted id space drops the event and sets
+ * BK_FLAG_EVENT_OVERFLOW.  Asynchronous on the env's stream.  Order: bk_device_ingress_enable, then the agents.
+ * BK_INVALID_ARGUMENT (env unchanged): no device ingress, no RandomAgents groups, Noise / Momentum members, assets > 1. */
+int bk_update_agents(bk_env* env);
 /* HOST arrays through the device ingress (a BaseNumpyAgent-style caller: src/bourse/step_sim/agents/base_agent.py:67-116
  * returns host numpy arrays, runner.py:103-112 passes them to submit_instructions, rust/src/step_sim_numpy.rs:233-275).
  * Same arrays, same per-book semantics as bk_submit_instructions_device, but the pointers are HOST memory: the library

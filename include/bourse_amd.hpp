@@ -197,6 +197,10 @@ class ManyEnv {
     }
     check(bk_set_agents_per_book(h_, static_cast<uint32_t>(n_members), flat.data(), nullptr));
   }
+  // agents.update(env, rng) of the RandomAgents into the device-resident queues (bk_update_agents; the env has the device
+  // ingress, bk_device_ingress_enable(handle(), ..), then the agents): the next step() trades them with the submitted
+  // instructions.  Asynchronous on the env's stream.
+  void update_agents() { check(bk_update_agents(h_)); }
   // record the agents' orders (bk_set_agent_order_log; before the first run): env(b).get_orders() answers after run
   void enable_agent_order_log() { check(bk_set_agent_order_log(h_, 1)); }
   void run(uint64_t n_steps) {
