@@ -675,7 +675,7 @@ __device__ __forceinline__ void snapshot(const Book<R>& B, const DevArgs& a, uin
     const bool is_live = lane_bit(B.live[r]);
     const bool is_bid = lane_bit(B.bid[r]);
     if (is_live) {
-      // level i of a side holds the orders priced touch -/+ i*tick (wrapping arithmetic never matches)
+      // bin q of a side holds the orders priced touch -/+ q*tick, q*tick < 2^32 (an order is never binned twice here)
       const uint32_t d = is_bid ? (bid_best - B.price[r]) : (B.price[r] - ask_best);
       const uint32_t q = udiv(d, tick);
       if (q * tick.d == d && q < L) {
@@ -686,6 +686,19 @@ __device__ __forceinline__ void snapshot(const Book<R>& B, const DevArgs& a, uin
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+  // Level i is the price touch -/+ (i * tick mod 2^32): the reference's u32 multiply wraps in its release build
+  // (orderbook.rs:229-264).  While (L - 1) * tick < 2^32 (wave-uniform, the common case) level i is bin i.  A huge tick
+  // wraps: level i >= 2^32 / tick then names the price of bin q = (i * tick mod 2^32) / tick when tick divides the
+  // wrapped multiple (q < i: several levels may alias one bin), and an off-grid price otherwise, where no order rests
+  // (prices are tick multiples: place / modify check them, agents draw them; only a loaded snapshot could hold others).
+  if (__builtin_expect(__umulhi(L - 1u, tick.d) != 0u, 0)) {
+    for (uint32_t i = 1; i < L; ++i) {
+      const uint32_t m = i * tick.d, q = udiv(m, tick);
+      if (q != i && q * tick.d == m && lane < 4) bins[4 * i + lane] = bins[4 * q + lane];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
 
   const uint32_t W = a.l2_width;
   uint32_t* last = a.l2_last + (size_t)book * W;

@@ -2275,12 +2275,15 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   l2[2] = ask_best;
   l2[3] = ask_vol;
   l2[4] = bid_vol;
+  // (level q is the price touch -/+ q * tick with a wrapping u32 multiply: with a huge tick several levels may alias)
   for (uint64_t i : act) {
     const bk_order& o = orders[i];
     const uint32_t d = o.side_is_bid ? bid_best - o.price : o.price - ask_best;
-    if (d % tick == 0 && d / tick < L) {
-      l2[5 + 4 * (d / tick) + (o.side_is_bid ? 0 : 2)] += o.vol;
-      l2[5 + 4 * (d / tick) + (o.side_is_bid ? 1 : 3)] += 1;
+    for (uint32_t q = 0; q < L; ++q) {
+      if (q * tick == d) {
+        l2[5 + 4 * q + (o.side_is_bid ? 0 : 2)] += o.vol;
+        l2[5 + 4 * q + (o.side_is_bid ? 1 : 3)] += 1;
+      }
     }
   }
   std::vector<DevOrderLog> log(n_orders);

@@ -18,6 +18,9 @@
 // (doubly linked through the order pool, so a cancellation unlinks in O(1)) with its (volume, count) aggregate, plus one
 // non-empty-level bitmap per side (best price = first / last set bit).  An agent holds at most one resting order
 // (SURVEY App. A.15), so the pool slot IS the agent index.
+// Not restated: the level ladder when (levels - 1) * tick >= 2^32.  The reference's u32 multiply then wraps and several
+// levels may alias one price (the oracle and the library follow it); this baseline reads its ladder without a wrap and
+// is only used on bench shapes, whose ticks are small.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>

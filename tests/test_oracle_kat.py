@@ -487,3 +487,57 @@ def test_native_submit_instructions_equals_the_python_loop(oracle):
         assert np.array_equal(a.level_2_data(), b.level_2_data())
     assert np.array_equal(a.book.trades_array(), b.book.trades_array()) and np.array_equal(a.book.orders_array(), b.book.orders_array())
     assert a.book.n_trades() > 20
+
+
+# ----------------------------------------------------------------- level 2 at huge ticks (orderbook.rs:229-264)
+def _wrapped_levels(resting, touch, is_bid, tick, levels):
+    """Level i of a side is the price touch -/+ i * tick with u32 wrapping arithmetic (the reference's release build):
+    (vol, count) of the resting orders {(price, vol)} at that price.  Several levels may name one price."""
+    out = []
+    for i in range(levels):
+        target = (touch - i * tick if is_bid else touch + i * tick) % 2**32
+        at = [v for p, v in resting if p == target]
+        out.append((sum(at) % 2**32, len(at)))
+    return out
+
+
+def test_level2_levels_alias_when_the_tick_multiple_wraps(oracle):
+    """(levels - 1) * tick >= 2^32: level i's price wraps, so a level may alias the touch (tick 2^31: levels 0, 2, 4)."""
+    env = oracle.StepEnv(1, 0, 2**31, 1000, True, 5)
+    env.place_order(True, 7, 0, 2**31)
+    env.place_order(True, 3, 0, 0)
+    env.place_order(False, 11, 0, 2**31)
+    env.step()
+    bids, asks = [(0, 3)], [(2**31, 4)]  # the bid at 2^31 fills; 3 rest at 0, 4 of the ask rest at 2^31
+    assert _wrapped_levels(bids, 0, True, 2**31, 5) == [(3, 1), (0, 0), (3, 1), (0, 0), (3, 1)]
+    l2 = env.level_2_data_array()
+    assert l2[:5].tolist() == [7, 0, 2**31, 4, 3]
+    lv = l2[5:].reshape(5, 4)
+    assert [tuple(x) for x in lv[:, :2].tolist()] == _wrapped_levels(bids, 0, True, 2**31, 5)
+    assert [tuple(x) for x in lv[:, 2:].tolist()] == _wrapped_levels(asks, 2**31, False, 2**31, 5)
+    assert [tuple(x) for x in lv[:, 2:].tolist()] == [(4, 1), (0, 0), (4, 1), (0, 0), (4, 1)]
+
+
+@pytest.mark.parametrize("levels", [5, 9])
+def test_level2_random_agents_at_tick_2_pow_30(oracle, levels):
+    """RandomAgents at an env / agent tick of 2^30 (tick range (1, 4): prices 2^30 .. 2^32) reach the wrapped levels:
+    every step's L2 is the rule above applied to the book's resting orders."""
+    tick = 2**30
+    ref = oracle.ManyBooks(3, 17, 0, tick, 1000, True, levels, [(12, (1, 3), (1, 40), tick, 0.7)])
+    aliased = 0
+    for _ in range(12):
+        ref.run(1)
+        for b in range(3):
+            o = ref.book(b).orders_array()
+            act = o[o["status"] == 1]
+            bids = [(int(x["price"]), int(x["vol"])) for x in act if x["side"] == 1]
+            asks = [(int(x["price"]), int(x["vol"])) for x in act if x["side"] == 0]
+            bb = max((p for p, _ in bids), default=0)
+            ba = min((p for p, _ in asks), default=2**32 - 1)
+            l2 = ref.history(ref.n_steps() - 1, 1)[0, b]
+            assert l2[1:5].tolist() == [bb, ba, sum(v for _, v in asks) % 2**32, sum(v for _, v in bids) % 2**32]
+            lv = l2[5:].reshape(levels, 4)
+            assert [tuple(x) for x in lv[:, :2].tolist()] == _wrapped_levels(bids, bb, True, tick, levels)
+            assert [tuple(x) for x in lv[:, 2:].tolist()] == _wrapped_levels(asks, ba, False, tick, levels)
+            aliased += int(lv[4, 1] > 0 or lv[4, 3] > 0)
+    assert aliased > 0  # level 4 = touch -/+ 2^32 = the touch itself
