@@ -9,9 +9,9 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libbourse_amd.so")
-SOURCES = ["bourse_amd.hip", "fsm_unit.hip", "book_device.hpp", "event_asm.hpp", "event_asm_gen.hpp", "wave_agents.hpp", "mixed_agents.hpp", "mixed_lanes_body.inc", "wave_mixed.hpp", "wave_mixed_body.inc", "step_events.hpp", "agents_ingress.hpp", "pm_math.hpp",
-           "host_pool.hpp", "host_math.hpp", "pipeline_plan.hpp", "agent_table.hpp",
-           os.path.join("..", "..", "include", "bourse_amd.h")]
+# every file the two translation units can include: an edit to any of them makes the library stale
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".inc"))) + [
+    os.path.join("..", "..", "include", "bourse_amd.h")]
 
 
 def hipcc_path() -> str:

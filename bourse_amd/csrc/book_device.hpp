@@ -1509,177 +1509,6 @@ enum Phase : uint32_t { PH_ACT = 0, PH_SIDE = 1, PH_TICK = 2, PH_VOL = 3, PH_SHU
 
 constexpr uint32_t fsm_lds_bytes(int R) { return 64u * R * 32u * 4u; }
 
-template <int R>
-__global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
-  // LDS is DYNAMIC (fsm_lds_bytes(R) at launch) so that the kernel's register footprint is the one chosen below: with a
-  // static size the compiler derives "at most 2 waves per SIMD" from it and pads the kernel descriptor's register request
-  // up to that occupancy's budget (R = 2: 169 VGPRs + 102 SGPRs for a kernel using 34 + 46; 257 VGPRs for R = 4, 8).
-  extern __shared__ uint32_t fsm_lds[];
-  uint16_t* list = reinterpret_cast<uint16_t*>(fsm_lds);  // event list of lane l: list[k * 64 + l], 64 * R * 64 entries
-  // (which agents place, and on which side, is not tracked here: the event words say it - bit 15 New, bit 14 bid - and
-  // k_step_batch rebuilds the masks from them with four LDS atomics per book instead of two per new order in this loop)
-  const int lane = threadIdx.x;
-  // This kernel is a dependent chain of ~600 iterations on ONE wave per SIMD, co-resident with up to 7 waves of the
-  // issue-bound event kernel of another part: top issue priority lets the chain run at its lone-wave pace (the part's
-  // next k_step_batch cannot start before it ends) at no cost to the event kernel's throughput
-  __builtin_amdgcn_s_setprio(3);
-  // ... and it CLAIMS far more VGPRs than it uses (34): the chain is VALU-latency bound, and every k_step_batch wave
-  // sharing its SIMD's VALU stretches it (151 us alone, 185-194 us under 8 event waves).  A 232-VGPR footprint leaves
-  // room for 7 event waves beside one of these waves and 1 beside two of them, instead of 8 and 8; measured on C3
-  // (profiles/r02/fsm_vgpr_sweep.txt): no pad 184 M, 104: 198, 168: 214, 200-264: 215-220 (plateau), 296: 169 M
-  // book-steps/s (from 296 up the dispatcher cannot place these waves until a whole SIMD drains).
-#if BOURSE_AMD_FSM_TOP_VGPR > 0
-  asm volatile("" ::: "v" BK_STR(BOURSE_AMD_FSM_TOP_VGPR));
-#endif
-  // MarketEnv mode (assets = M > 1): the lane owns a MARKET = books [b*M, b*M + M) with one RNG stream and one event
-  // queue (market_env.rs:110-121, runner.rs:108-131); RandomMarketAgents::update is RandomAgents::update addressed to
-  // the group's asset (random_agent.rs:204-247), so the state machine below is unchanged.
-  const uint32_t M = a.assets;
-  const uint32_t b = a.book_begin + blockIdx.x * 64 + lane;
-  if (b >= a.book_end) return;
-  uint32_t* st = a.state + (size_t)b * M * a.state_stride;
-  uint32_t* bt = a.batch + (size_t)b * M * a.batch_stride;
-
-  RngLane rng;
-  {
-    const uint2 x0 = *reinterpret_cast<const uint2*>(st + H_S0_LO);
-    const uint2 x1 = *reinterpret_cast<const uint2*>(st + H_S1_LO);
-    rng.a0 = x0.x, rng.a1 = x0.y, rng.b0 = x1.x, rng.b1 = x1.y;
-  }
-  uint64_t live[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    uint2 x = *reinterpret_cast<const uint2*>(st + H_LIVE0 + 2 * r);
-    for (uint32_t as = 1; as < M; ++as) {  // slot = agent index in every book of the market: the masks are disjoint
-      const uint2 y = *reinterpret_cast<const uint2*>(st + (size_t)as * a.state_stride + H_LIVE0 + 2 * r);
-      x.x |= y.x;
-      x.y |= y.y;
-    }
-    live[r] = mk64(x.x, x.y);
-  }
-  uint2* pv = reinterpret_cast<uint2*>(bt + BT_EV + 32 * R);
-
-  // ---- loop 1: agents.update, group by group (declaration order).  Inside a group every lane runs a state
-  // machine that performs exactly ONE next_u32() draw per iteration (a lane never waits for another lane's rejection
-  // loop); the group's parameters are wave-uniform (SGPRs).  Lanes re-converge at each group boundary.
-  // Select-style body (v_cndmask) with three short predicated blocks: list append, new-order store, next agent.
-  const uint32_t five = RngLane::opaque5();
-  uint32_t n = 0, n_ev = 0, gbase = 0;
-  for (uint32_t g = 0; g < a.n_groups; ++g) {
-    const Group G = a.groups[g];
-    const uint32_t gend = gbase + G.n;
-    gbase = gend;
-    if (G.n == 0) continue;
-    // complete the scalar loads of the group's parameters HERE: a wait parked inside the loop would be
-    // s_waitcnt lgkmcnt(0), which also waits for the iteration's own LDS writes (list append, ds_or) to drain
-    asm volatile("" ::"s"(G.thr), "s"(G.tick_lo), "s"(G.tick_rng), "s"(G.tick_zone));
-    asm volatile("" ::"s"(G.vol_lo), "s"(G.vol_rng), "s"(G.vol_zone), "s"(G.tick_size));
-    // Every predicate of a draw is taken as a WAVE MASK first (v_cmp into an SGPR pair), then the generator's state
-    // update runs (11 vector instructions that depend on none of them), and only then does the scalar unit combine the
-    // masks: an SALU instruction that reads an SGPR a vector compare has JUST written stalls the wave ~16 clocks
-    // (scripts/micro/lone_wave_latency.hip), and the straightforward form - `bool` predicates combined where they are
-    // used - had five of those per draw (k_agents_fsm 161 -> 141 us per launch under load).  Same instructions, same
-    // counts: the two fences only fix their order.
-    // the group's ranges and zones as VECTOR registers for the loop: a select under an SGPR mask cannot also read an
-    // SGPR source (one scalar operand per VOP3), so the compiler copied each of the four into a VGPR on every draw
-    uint32_t v_trng = G.tick_rng, v_vrng = G.vol_rng, v_tzone = G.tick_zone, v_vzone = G.vol_zone;
-    asm volatile("" : "+v"(v_trng), "+v"(v_vrng), "+v"(v_tzone), "+v"(v_vzone));
-    const uint64_t thr8 = (uint64_t)G.thr << 8;
-    // price = (tick_lo + val) * tick_size as one multiply-add: val * tick_size + tick_lo * tick_size (mod 2^32)
-    uint64_t price0 = (uint64_t)(G.tick_lo * G.tick_size);
-    asm volatile("" : "+v"(price0));  // (kept in a VGPR pair: the addend of the multiply-add below)
-    // The group is walked in SEGMENTS that stay inside one 64-slot pool register, so that the live word of the agent
-    // at hand is one register pair per segment, not a per-draw select over the pool's registers (lanes re-converge at
-    // a segment's end as they do at a group's; the benchmark groups are 64-aligned: no extra boundary there).
-    for (uint32_t sbeg = gend - G.n; sbeg < gend;) {
-      const uint32_t send = gend < (sbeg | 63u) + 1u ? gend : (sbeg | 63u) + 1u;
-      uint64_t w = live[0];
-#pragma unroll
-      for (int r = 1; r < R; ++r) w = ((sbeg >> 6) == (uint32_t)r) ? live[r] : w;
-      uint32_t cur_side = 0, cur_price = 0;
-      // The phase of every lane lives in four WAVE MASKS carried across the iterations in scalar registers (one-hot per
-      // lane) and is advanced by scalar mask algebra at the end of the iteration - round 3 kept it in a vector register:
-      // four compares to get the masks and four selects to write the next phase, every draw.  Bits of lanes that have
-      // left the loop go stale, harmlessly: every predicate they are combined with is a ballot of the lanes still in it.
-      uint64_t P_ACT = ~0ull, P_SIDE = 0, P_TICK = 0, P_VOL = 0;
-      while (n < send) {
-        const uint32_t x = rng.output(five);
-        // range and zone of the phase at hand, from its masks (two selects each; no loop-carried copies)
-        const uint32_t range = sel(P_SIDE, 2u, sel(P_TICK, v_trng, v_vrng));
-        const uint32_t zone = sel(P_SIDE, 0x7FFFFFFFu, sel(P_TICK, v_tzone, v_vzone));
-        const uint64_t m = (uint64_t)x * range;  // sample_single step of the current phase: accept iff lo <= zone
-        const uint32_t val = (uint32_t)(m >> 32);
-        // gen::<f32>() < activity_rate (:91-93): (x >> 8) < thr as ONE 64-bit compare x < thr << 8 (thr <= 2^24)
-        uint64_t C_HIT = __builtin_amdgcn_ballot_w64((uint64_t)x < thr8);
-        uint64_t C_ACC = __builtin_amdgcn_ballot_w64((uint32_t)m <= zone);
-        uint64_t C_LIVE = __builtin_amdgcn_ballot_w64(((w >> (n & 63)) & 1ull) != 0);  // Active order held (:95-97)
-        asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1)
-                     : "s"(P_ACT), "s"(P_SIDE), "s"(P_TICK), "s"(P_VOL), "s"(C_HIT), "s"(C_ACC), "s"(C_LIVE));
-        rng.advance();
-        asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1), "+s"(P_ACT), "+s"(P_SIDE), "+s"(P_TICK),
-                       "+s"(P_VOL), "+s"(C_HIT), "+s"(C_ACC), "+s"(C_LIVE));
-        const uint64_t HIT = P_ACT & C_HIT, CANCEL = HIT & C_LIVE, TO_SIDE = HIT & ~C_LIVE;
-        const uint64_t A_SIDE = C_ACC & P_SIDE, A_TICK = C_ACC & P_TICK, A_VOL = C_ACC & P_VOL;
-        const uint64_t QUEUE = CANCEL | A_VOL, ADV = (P_ACT & ~C_HIT) | QUEUE;
-        cur_side = sel(A_SIDE, val, cur_side);                                    // 0 = Ask, 1 = Bid ([Ask, Bid].choose, :99)
-        {  // tick * tick_size (:100,:107)
-          uint64_t pr, cy;
-          asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(pr), "=s"(cy) : "v"(val), "s"(G.tick_size), "v"(price0));
-          cur_price = sel(A_TICK, (uint32_t)pr, cur_price);
-        }
-        // the agent's event, queued once its kind is known (agent order): bit 15 = New, bit 14 = bid
-        if (lane_bit(QUEUE)) list[n_ev * 64 + lane] = (uint16_t)sel(A_VOL, n | EV_NEW | (cur_side << 14), n);
-        asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n_ev) : "s"(QUEUE) : "vcc");  // n_ev += lane_bit(QUEUE)
-        if (lane_bit(A_VOL)) pv[n] = make_uint2(cur_price, G.vol_lo + val);       // vol drawn last (:101): the order is complete
-        // next phase; an agent that is done (inactive, cancelled or placed) hands over to the next one
-        P_SIDE = TO_SIDE | (P_SIDE & ~C_ACC);
-        P_TICK = A_SIDE | (P_TICK & ~C_ACC);
-        P_VOL = A_TICK | (P_VOL & ~C_ACC);
-        P_ACT = ADV;
-        asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n) : "s"(ADV) : "vcc");  // n += lane_bit(ADV)
-      }
-      sbeg = send;
-    }
-  }
-
-  // ---- loop 2: transactions.shuffle(rng) (env.rs:121): for i in (1..n_ev).rev() { swap(i, gen_index(i + 1)) }
-  // (rand SliceRandom::shuffle), again one draw per iteration per lane.
-  {
-    uint32_t i = n_ev > 1 ? n_ev - 1 : 0;
-    uint32_t rg = i + 1;
-    uint32_t zn = (rg << __builtin_clz(rg)) - 1u;
-    while (i != 0) {
-      const uint32_t x = rng.output(five);
-      const uint64_t m = (uint64_t)x * rg;
-      uint64_t ACC = __builtin_amdgcn_ballot_w64((uint32_t)m <= zn);  // (same ordering as in loop 1)
-      asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1) : "s"(ACC));
-      rng.advance();
-      asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1), "+s"(ACC));
-      if (lane_bit(ACC)) {
-        const uint32_t j = (uint32_t)(m >> 32);
-        const uint16_t ai = list[i * 64 + lane], aj = list[j * 64 + lane];
-        list[i * 64 + lane] = aj;
-        list[j * 64 + lane] = ai;
-        --i;
-        rg = i + 1;
-        zn = (rg << __builtin_clz(rg)) - 1u;
-      }
-    }
-  }
-
-  // publish: RNG state back to the book header, the step batch for k_step_batch
-  for (uint32_t as = 0; as < M; ++as) {  // every book of a market carries a copy of the market's RNG state
-    *reinterpret_cast<uint2*>(st + (size_t)as * a.state_stride + H_S0_LO) = make_uint2(rng.a0, rng.a1);
-    *reinterpret_cast<uint2*>(st + (size_t)as * a.state_stride + H_S1_LO) = make_uint2(rng.b0, rng.b1);
-  }
-  bt[BT_NEV] = n_ev;
-  for (uint32_t k = 0; k < n_ev; k += 2) {
-    const uint32_t lo = list[k * 64 + lane];
-    const uint32_t hi = (k + 1 < n_ev) ? list[(k + 1) * 64 + lane] : 0u;
-    bt[BT_EV + (k >> 1)] = lo | (hi << 16);
-  }
-}
-
 // PB (bk_set_random_agents_per_book): a lane's groups come from its unit's row of the per-unit table, as three vector
 // loads per group (dwords 0..3, 4..7 and 8 of the 48-byte record); only the group sizes stay wave-uniform (DevArgs::groups)
 struct LaneGroup {
@@ -1691,205 +1520,30 @@ __device__ __forceinline__ LaneGroup load_lane_group(const Group* g) {
   return LaneGroup{q[0], q[1], g->tick_size};
 }
 
-// The body of k_agents_fsm<R, true>: k_agents_fsm<R> above with the groups' parameters per lane (PB = false is that kernel's
-// body again).  The uniform kernel keeps its own text: compiled through this shared inline function instead, its code
-// changed (the compiler simplifies the callee before inlining it) - with PB = false the two are the same source.
-template <int R, bool PB>
-__device__ __forceinline__ void agents_fsm(const DevArgs& a, const Group* table, uint32_t* fsm_lds) {
-  uint16_t* list = reinterpret_cast<uint16_t*>(fsm_lds);  // event list of lane l: list[k * 64 + l], 64 * R * 64 entries
-  // (which agents place, and on which side, is not tracked here: the event words say it - bit 15 New, bit 14 bid - and
-  // k_step_batch rebuilds the masks from them with four LDS atomics per book instead of two per new order in this loop)
-  const int lane = threadIdx.x;
-  // This kernel is a dependent chain of ~600 iterations on ONE wave per SIMD, co-resident with up to 7 waves of the
-  // issue-bound event kernel of another part: top issue priority lets the chain run at its lone-wave pace (the part's
-  // next k_step_batch cannot start before it ends) at no cost to the event kernel's throughput
-  __builtin_amdgcn_s_setprio(3);
-  // ... and it CLAIMS far more VGPRs than it uses (34): the chain is VALU-latency bound, and every k_step_batch wave
-  // sharing its SIMD's VALU stretches it (151 us alone, 185-194 us under 8 event waves).  A 232-VGPR footprint leaves
-  // room for 7 event waves beside one of these waves and 1 beside two of them, instead of 8 and 8; measured on C3
-  // (profiles/r02/fsm_vgpr_sweep.txt): no pad 184 M, 104: 198, 168: 214, 200-264: 215-220 (plateau), 296: 169 M
-  // book-steps/s (from 296 up the dispatcher cannot place these waves until a whole SIMD drains).
-#if BOURSE_AMD_FSM_TOP_VGPR > 0
-  asm volatile("" ::: "v" BK_STR(BOURSE_AMD_FSM_TOP_VGPR));
-#endif
-  // MarketEnv mode (assets = M > 1): the lane owns a MARKET = books [b*M, b*M + M) with one RNG stream and one event
-  // queue (market_env.rs:110-121, runner.rs:108-131); RandomMarketAgents::update is RandomAgents::update addressed to
-  // the group's asset (random_agent.rs:204-247), so the state machine below is unchanged.
-  const uint32_t M = a.assets;
-  const uint32_t b = a.book_begin + blockIdx.x * 64 + lane;
-  if (b >= a.book_end) return;
-  uint32_t* st = a.state + (size_t)b * M * a.state_stride;
-  uint32_t* bt = a.batch + (size_t)b * M * a.batch_stride;
-  // PB: the unit's row; group g + 1's loads are issued before group g's walk (the first ones before the state loads), so
-  // only the first group's round trip is not hidden under a walk
-  const Group* row = PB ? table + (size_t)b * a.n_groups : nullptr;
-  LaneGroup nxt{};
-  if constexpr (PB) {
-    if (a.n_groups) nxt = load_lane_group(row);
-  }
-
-  RngLane rng;
-  {
-    const uint2 x0 = *reinterpret_cast<const uint2*>(st + H_S0_LO);
-    const uint2 x1 = *reinterpret_cast<const uint2*>(st + H_S1_LO);
-    rng.a0 = x0.x, rng.a1 = x0.y, rng.b0 = x1.x, rng.b1 = x1.y;
-  }
-  uint64_t live[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    uint2 x = *reinterpret_cast<const uint2*>(st + H_LIVE0 + 2 * r);
-    for (uint32_t as = 1; as < M; ++as) {  // slot = agent index in every book of the market: the masks are disjoint
-      const uint2 y = *reinterpret_cast<const uint2*>(st + (size_t)as * a.state_stride + H_LIVE0 + 2 * r);
-      x.x |= y.x;
-      x.y |= y.y;
-    }
-    live[r] = mk64(x.x, x.y);
-  }
-  uint2* pv = reinterpret_cast<uint2*>(bt + BT_EV + 32 * R);
-
-  // ---- loop 1: agents.update, group by group (declaration order).  Inside a group every lane runs a state
-  // machine that performs exactly ONE next_u32() draw per iteration (a lane never waits for another lane's rejection
-  // loop); the group's parameters are wave-uniform (SGPRs).  Lanes re-converge at each group boundary.
-  // Select-style body (v_cndmask) with three short predicated blocks: list append, new-order store, next agent.
-  const uint32_t five = RngLane::opaque5();
-  uint32_t n = 0, n_ev = 0, gbase = 0;
-  for (uint32_t g = 0; g < a.n_groups; ++g) {
-    const Group G = a.groups[g];
-    const uint32_t gend = gbase + G.n;
-    gbase = gend;
-    LaneGroup L{};
-    if constexpr (PB) {
-      L = nxt;
-      if (g + 1 < a.n_groups) nxt = load_lane_group(row + g + 1);
-    }
-    if (G.n == 0) continue;
-    // complete the scalar loads of the group's parameters HERE: a wait parked inside the loop would be
-    // s_waitcnt lgkmcnt(0), which also waits for the iteration's own LDS writes (list append, ds_or) to drain
-    // (PB: the lane's parameters are vector registers, made ready by the "v" fences below - a wait for vmcnt here)
-    if constexpr (!PB) {
-      asm volatile("" ::"s"(G.thr), "s"(G.tick_lo), "s"(G.tick_rng), "s"(G.tick_zone));
-      asm volatile("" ::"s"(G.vol_lo), "s"(G.vol_rng), "s"(G.vol_zone), "s"(G.tick_size));
-    }
-    const uint32_t g_thr = PB ? L.a.y : G.thr, g_tick_lo = PB ? L.a.z : G.tick_lo, g_vol_lo = PB ? L.b.y : G.vol_lo;
-    uint32_t g_tick_size = PB ? L.tick_size : G.tick_size;
-    if constexpr (PB) asm volatile("" : "+v"(g_tick_size));
-    // Every predicate of a draw is taken as a WAVE MASK first (v_cmp into an SGPR pair), then the generator's state
-    // update runs (11 vector instructions that depend on none of them), and only then does the scalar unit combine the
-    // masks: an SALU instruction that reads an SGPR a vector compare has JUST written stalls the wave ~16 clocks
-    // (scripts/micro/lone_wave_latency.hip), and the straightforward form - `bool` predicates combined where they are
-    // used - had five of those per draw (k_agents_fsm 161 -> 141 us per launch under load).  Same instructions, same
-    // counts: the two fences only fix their order.
-    // the group's ranges and zones as VECTOR registers for the loop: a select under an SGPR mask cannot also read an
-    // SGPR source (one scalar operand per VOP3), so the compiler copied each of the four into a VGPR on every draw
-    uint32_t v_trng = PB ? L.a.w : G.tick_rng, v_vrng = PB ? L.b.z : G.vol_rng, v_tzone = PB ? L.b.x : G.tick_zone,
-             v_vzone = PB ? L.b.w : G.vol_zone;
-    asm volatile("" : "+v"(v_trng), "+v"(v_vrng), "+v"(v_tzone), "+v"(v_vzone));
-    // (PB: thr8 and tick_size are per lane - vector operands of the compare and of the multiply-add)
-    const uint64_t thr8 = (uint64_t)g_thr << 8;
-    // price = (tick_lo + val) * tick_size as one multiply-add: val * tick_size + tick_lo * tick_size (mod 2^32)
-    uint64_t price0 = (uint64_t)(g_tick_lo * g_tick_size);
-    asm volatile("" : "+v"(price0));  // (kept in a VGPR pair: the addend of the multiply-add below)
-    // The group is walked in SEGMENTS that stay inside one 64-slot pool register, so that the live word of the agent
-    // at hand is one register pair per segment, not a per-draw select over the pool's registers (lanes re-converge at
-    // a segment's end as they do at a group's; the benchmark groups are 64-aligned: no extra boundary there).
-    for (uint32_t sbeg = gend - G.n; sbeg < gend;) {
-      const uint32_t send = gend < (sbeg | 63u) + 1u ? gend : (sbeg | 63u) + 1u;
-      uint64_t w = live[0];
-#pragma unroll
-      for (int r = 1; r < R; ++r) w = ((sbeg >> 6) == (uint32_t)r) ? live[r] : w;
-      uint32_t cur_side = 0, cur_price = 0;
-      // The phase of every lane lives in four WAVE MASKS carried across the iterations in scalar registers (one-hot per
-      // lane) and is advanced by scalar mask algebra at the end of the iteration - round 3 kept it in a vector register:
-      // four compares to get the masks and four selects to write the next phase, every draw.  Bits of lanes that have
-      // left the loop go stale, harmlessly: every predicate they are combined with is a ballot of the lanes still in it.
-      uint64_t P_ACT = ~0ull, P_SIDE = 0, P_TICK = 0, P_VOL = 0;
-      while (n < send) {
-        const uint32_t x = rng.output(five);
-        // range and zone of the phase at hand, from its masks (two selects each; no loop-carried copies)
-        const uint32_t range = sel(P_SIDE, 2u, sel(P_TICK, v_trng, v_vrng));
-        const uint32_t zone = sel(P_SIDE, 0x7FFFFFFFu, sel(P_TICK, v_tzone, v_vzone));
-        const uint64_t m = (uint64_t)x * range;  // sample_single step of the current phase: accept iff lo <= zone
-        const uint32_t val = (uint32_t)(m >> 32);
-        // gen::<f32>() < activity_rate (:91-93): (x >> 8) < thr as ONE 64-bit compare x < thr << 8 (thr <= 2^24)
-        uint64_t C_HIT = __builtin_amdgcn_ballot_w64((uint64_t)x < thr8);
-        uint64_t C_ACC = __builtin_amdgcn_ballot_w64((uint32_t)m <= zone);
-        uint64_t C_LIVE = __builtin_amdgcn_ballot_w64(((w >> (n & 63)) & 1ull) != 0);  // Active order held (:95-97)
-        asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1)
-                     : "s"(P_ACT), "s"(P_SIDE), "s"(P_TICK), "s"(P_VOL), "s"(C_HIT), "s"(C_ACC), "s"(C_LIVE));
-        rng.advance();
-        asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1), "+s"(P_ACT), "+s"(P_SIDE), "+s"(P_TICK),
-                       "+s"(P_VOL), "+s"(C_HIT), "+s"(C_ACC), "+s"(C_LIVE));
-        const uint64_t HIT = P_ACT & C_HIT, CANCEL = HIT & C_LIVE, TO_SIDE = HIT & ~C_LIVE;
-        const uint64_t A_SIDE = C_ACC & P_SIDE, A_TICK = C_ACC & P_TICK, A_VOL = C_ACC & P_VOL;
-        const uint64_t QUEUE = CANCEL | A_VOL, ADV = (P_ACT & ~C_HIT) | QUEUE;
-        cur_side = sel(A_SIDE, val, cur_side);                                    // 0 = Ask, 1 = Bid ([Ask, Bid].choose, :99)
-        {  // tick * tick_size (:100,:107)
-          uint64_t pr, cy;
-          if constexpr (PB)
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(pr), "=s"(cy) : "v"(val), "v"(g_tick_size), "v"(price0));
-          else
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(pr), "=s"(cy) : "v"(val), "s"(G.tick_size), "v"(price0));
-          cur_price = sel(A_TICK, (uint32_t)pr, cur_price);
-        }
-        // the agent's event, queued once its kind is known (agent order): bit 15 = New, bit 14 = bid
-        if (lane_bit(QUEUE)) list[n_ev * 64 + lane] = (uint16_t)sel(A_VOL, n | EV_NEW | (cur_side << 14), n);
-        asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n_ev) : "s"(QUEUE) : "vcc");  // n_ev += lane_bit(QUEUE)
-        if (lane_bit(A_VOL)) pv[n] = make_uint2(cur_price, g_vol_lo + val);       // vol drawn last (:101): the order is complete
-        // next phase; an agent that is done (inactive, cancelled or placed) hands over to the next one
-        P_SIDE = TO_SIDE | (P_SIDE & ~C_ACC);
-        P_TICK = A_SIDE | (P_TICK & ~C_ACC);
-        P_VOL = A_TICK | (P_VOL & ~C_ACC);
-        P_ACT = ADV;
-        asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n) : "s"(ADV) : "vcc");  // n += lane_bit(ADV)
-      }
-      sbeg = send;
-    }
-  }
-
-  // ---- loop 2: transactions.shuffle(rng) (env.rs:121): for i in (1..n_ev).rev() { swap(i, gen_index(i + 1)) }
-  // (rand SliceRandom::shuffle), again one draw per iteration per lane.
-  {
-    uint32_t i = n_ev > 1 ? n_ev - 1 : 0;
-    uint32_t rg = i + 1;
-    uint32_t zn = (rg << __builtin_clz(rg)) - 1u;
-    while (i != 0) {
-      const uint32_t x = rng.output(five);
-      const uint64_t m = (uint64_t)x * rg;
-      uint64_t ACC = __builtin_amdgcn_ballot_w64((uint32_t)m <= zn);  // (same ordering as in loop 1)
-      asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1) : "s"(ACC));
-      rng.advance();
-      asm volatile("" : "+v"(rng.a0), "+v"(rng.a1), "+v"(rng.b0), "+v"(rng.b1), "+s"(ACC));
-      if (lane_bit(ACC)) {
-        const uint32_t j = (uint32_t)(m >> 32);
-        const uint16_t ai = list[i * 64 + lane], aj = list[j * 64 + lane];
-        list[i * 64 + lane] = aj;
-        list[j * 64 + lane] = ai;
-        --i;
-        rg = i + 1;
-        zn = (rg << __builtin_clz(rg)) - 1u;
-      }
-    }
-  }
-
-  // publish: RNG state back to the book header, the step batch for k_step_batch
-  for (uint32_t as = 0; as < M; ++as) {  // every book of a market carries a copy of the market's RNG state
-    *reinterpret_cast<uint2*>(st + (size_t)as * a.state_stride + H_S0_LO) = make_uint2(rng.a0, rng.a1);
-    *reinterpret_cast<uint2*>(st + (size_t)as * a.state_stride + H_S1_LO) = make_uint2(rng.b0, rng.b1);
-  }
-  bt[BT_NEV] = n_ev;
-  for (uint32_t k = 0; k < n_ev; k += 2) {
-    const uint32_t lo = list[k * 64 + lane];
-    const uint32_t hi = (k + 1 < n_ev) ? list[(k + 1) * 64 + lane] : 0u;
-    bt[BT_EV + (k >> 1)] = lo | (hi << 16);
-  }
+template <int R>
+__global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
+  // LDS is DYNAMIC (fsm_lds_bytes(R) at launch) so that the kernel's register footprint is the body's own claim: with a
+  // static size the compiler derives "at most 2 waves per SIMD" from it and pads the kernel descriptor's register request
+  // up to that occupancy's budget (R = 2: 169 VGPRs + 102 SGPRs for a kernel using 34 + 46; 257 VGPRs for R = 4, 8).
+  extern __shared__ uint32_t fsm_lds[];
+#define BK_PB 0
+#include "agents_fsm_body.inc"
+#undef BK_PB
 }
 
-// per-unit parameters (bk_set_random_agents_per_book): table[u * n_groups + g] is group g of unit u (book, or market)
+// per-unit parameters (bk_set_random_agents_per_book): table[u * n_groups + g] is group g of unit u (book, or market).
+// The body runs in an inline function, as it always has: included straight into the kernel it gets other registers.
+template <int R>
+__device__ __forceinline__ void agents_fsm_pb(const DevArgs& a, const Group* table, uint32_t* fsm_lds) {
+#define BK_PB 1
+#include "agents_fsm_body.inc"
+#undef BK_PB
+}
 template <int R, bool PB>
 __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a, const Group* table) {
   static_assert(PB, "the uniform form is k_agents_fsm<R>(DevArgs)");
   extern __shared__ uint32_t fsm_lds[];
-  agents_fsm<R, true>(a, table, fsm_lds);
+  agents_fsm_pb<R>(a, table, fsm_lds);
 }
 
 template <int R, bool MKT, bool POOLPEND, bool LOG = false>

@@ -364,119 +364,36 @@ __device__ __forceinline__ void mixed_update_and_shuffle(Book<R>& B, MixedCtx<R>
 // fused: n_steps x { members' update + shuffle; event loop + snapshot } with the book in registers (small batches)
 template <int R>
 __global__ __launch_bounds__(256) void k_run_mixed(DevArgs a, MixedArgs ma, uint64_t first_step, uint32_t n_steps) {
-  __shared__ uint32_t lds[4][LDS_DW_PER_WAVE];
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  const uint32_t book = rfl(blockIdx.x * 4 + wv);
-  if (book >= a.n_books) return;
-  uint32_t* st = a.state + (size_t)book * a.state_stride;
-
-  Book<R> B;
-  Rng rng;
-  load_book<R>(B, rng, st, lane);
-  MixedCtx<R> C;
-  MixedState S;
-  mixed_load_state(S, st, lane);
-  mixed_load_ctx<R>(C, st, ma, lane);
-  C.tick = a.tick_size;
-  uint32_t last_ntr = 0, last_nev = 0;
-  for (uint32_t s = 0; s < n_steps; ++s) {
-    mixed_update_and_shuffle<R>(B, C, rng, ma, S, lane);
-    last_ntr = step_from_list<R>(B, a, book, lane, C.ev, C.n_ev, lds[wv],
-                                 a.hist_cap ? (a.hist_slot0 + s) % a.hist_cap : 0u, s + 1 == n_steps || a.hist_cap == 0,
-                                 a.tick_div, B.pend, last_nev);
-  }
-  store_book<R>(B, rng, st, lane, first_step + n_steps, last_ntr, last_nev);
-  mixed_store_state<R>(S, B, C, st, lane);
+#define BK_PB 0
+#include "run_mixed_body.inc"
+#undef BK_PB
 }
 
 // split: one step's members' update + shuffle per book; the new orders stay parked in the pool (pend bit in the
 // stored meta word), the shuffled event list goes to the book's step batch for k_step_batch<R, false, true>.
 template <int R>
 __global__ __launch_bounds__(256) void k_agents_mixed(DevArgs a, MixedArgs ma) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t book = rfl(a.book_begin + blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (book >= a.book_end) return;
-  uint32_t* st = a.state + (size_t)book * a.state_stride;
-  uint32_t* bt = a.batch + (size_t)book * a.batch_stride;
-  Book<R> B;
-  Rng rng;
-  load_book<R>(B, rng, st, lane);
-  MixedCtx<R> C;
-  MixedState S;
-  mixed_load_state(S, st, lane);
-  mixed_load_ctx<R>(C, st, ma, lane);
-  C.tick = a.tick_size;
-  mixed_update_and_shuffle<R>(B, C, rng, ma, S, lane);
-  // the step counter / last-step figures are k_step_batch's to write: keep the header's values
-  const uint32_t hdr = st[lane];
-  store_book<R>(B, rng, st, lane, mk64(rdl(hdr, H_STEPS_LO), rdl(hdr, H_STEPS_HI)), rdl(hdr, H_LAST_NTRADES),
-                rdl(hdr, H_LAST_NEVENTS));
-  mixed_store_state<R>(S, B, C, st, lane);
-  if (lane == 0) bt[BT_NEV] = C.n_ev;
-#pragma unroll
-  for (int r = 0; r < R; ++r) reinterpret_cast<uint16_t*>(bt + BT_EV)[r * 64 + lane] = (uint16_t)C.ev[r];
+#define BK_PB 0
+#include "agents_mixed_body.inc"
+#undef BK_PB
 }
 
 // PB (bk_set_agents_per_book): the members' parameters are the book's row of the per-unit table, table[book * n_desc + j]
-// - a wave-uniform address, so the member's record is the same scalar load as ma.descs[j] in the uniform kernels above,
-// whose source these repeat (the uniform kernels keep their own source so that their compiled code cannot change).
 template <int R, bool PB>
 __global__ __launch_bounds__(256) void k_run_mixed(DevArgs a, MixedArgs ma, uint64_t first_step, uint32_t n_steps,
                                                    const MixedDesc* table) {
   static_assert(PB, "the uniform form is k_run_mixed<R>(DevArgs, MixedArgs, uint64_t, uint32_t)");
-  __shared__ uint32_t lds[4][LDS_DW_PER_WAVE];
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  const uint32_t book = rfl(blockIdx.x * 4 + wv);
-  if (book >= a.n_books) return;
-  uint32_t* st = a.state + (size_t)book * a.state_stride;
-  ma.descs = table + (size_t)book * ma.n_desc;
-
-  Book<R> B;
-  Rng rng;
-  load_book<R>(B, rng, st, lane);
-  MixedCtx<R> C;
-  MixedState S;
-  mixed_load_state(S, st, lane);
-  mixed_load_ctx<R>(C, st, ma, lane);
-  C.tick = a.tick_size;
-  uint32_t last_ntr = 0, last_nev = 0;
-  for (uint32_t s = 0; s < n_steps; ++s) {
-    mixed_update_and_shuffle<R>(B, C, rng, ma, S, lane);
-    last_ntr = step_from_list<R>(B, a, book, lane, C.ev, C.n_ev, lds[wv],
-                                 a.hist_cap ? (a.hist_slot0 + s) % a.hist_cap : 0u, s + 1 == n_steps || a.hist_cap == 0,
-                                 a.tick_div, B.pend, last_nev);
-  }
-  store_book<R>(B, rng, st, lane, first_step + n_steps, last_ntr, last_nev);
-  mixed_store_state<R>(S, B, C, st, lane);
+#define BK_PB 1
+#include "run_mixed_body.inc"
+#undef BK_PB
 }
 
 template <int R, bool PB>
 __global__ __launch_bounds__(256) void k_agents_mixed(DevArgs a, MixedArgs ma, const MixedDesc* table) {
   static_assert(PB, "the uniform form is k_agents_mixed<R>(DevArgs, MixedArgs)");
-  const int lane = threadIdx.x & 63;
-  const uint32_t book = rfl(a.book_begin + blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (book >= a.book_end) return;
-  uint32_t* st = a.state + (size_t)book * a.state_stride;
-  uint32_t* bt = a.batch + (size_t)book * a.batch_stride;
-  ma.descs = table + (size_t)book * ma.n_desc;
-  Book<R> B;
-  Rng rng;
-  load_book<R>(B, rng, st, lane);
-  MixedCtx<R> C;
-  MixedState S;
-  mixed_load_state(S, st, lane);
-  mixed_load_ctx<R>(C, st, ma, lane);
-  C.tick = a.tick_size;
-  mixed_update_and_shuffle<R>(B, C, rng, ma, S, lane);
-  const uint32_t hdr = st[lane];
-  store_book<R>(B, rng, st, lane, mk64(rdl(hdr, H_STEPS_LO), rdl(hdr, H_STEPS_HI)), rdl(hdr, H_LAST_NTRADES),
-                rdl(hdr, H_LAST_NEVENTS));
-  mixed_store_state<R>(S, B, C, st, lane);
-  if (lane == 0) bt[BT_NEV] = C.n_ev;
-#pragma unroll
-  for (int r = 0; r < R; ++r) reinterpret_cast<uint16_t*>(bt + BT_EV)[r * 64 + lane] = (uint16_t)C.ev[r];
+#define BK_PB 1
+#include "agents_mixed_body.inc"
+#undef BK_PB
 }
 
 // ==================================================================================
@@ -561,9 +478,9 @@ constexpr size_t mixed_lanes_lds_bytes(int R, bool mkt) {
 
 template <int R, bool MKT>
 __global__ __launch_bounds__(64) void k_agents_mixed_lanes(DevArgs a, MixedArgs ma, MixedLists ml) {
-#define MIXED_PB 0
+#define BK_PB 0
 #include "mixed_lanes_body.inc"
-#undef MIXED_PB
+#undef BK_PB
 }
 
 // PB (bk_set_agents_per_book): one member's record of the lane's unit, the fields its kind reads - D holds the shared ones
@@ -602,9 +519,9 @@ static_assert(2 * mixed_lanes_pb_lds_bytes(8, false) <= 160 * 1024, "two workgro
 template <int R, bool MKT, bool PB>
 __global__ __launch_bounds__(64) void k_agents_mixed_lanes(DevArgs a, MixedArgs ma, MixedLists ml, const MixedDesc* table) {
   static_assert(PB, "the uniform form is k_agents_mixed_lanes<R, MKT>(DevArgs, MixedArgs, MixedLists)");
-#define MIXED_PB 1
+#define BK_PB 1
 #include "mixed_lanes_body.inc"
-#undef MIXED_PB
+#undef BK_PB
 }
 
 // (Re)build the members' lists from the pool after the wave-per-book kernels (or a restore) have run: live slots

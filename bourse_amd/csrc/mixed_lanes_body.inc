@@ -1,8 +1,8 @@
 // mixed_lanes_body.inc - the body of k_agents_mixed_lanes (mixed_agents.hpp), included by the uniform kernel with
-// MIXED_PB = 0 and by its per-unit form (bk_set_agents_per_book) with MIXED_PB = 1.  The text is shared so that the two
+// BK_PB = 0 and by its per-unit form (bk_set_agents_per_book) with BK_PB = 1.  The text is shared so that the two
 // cannot drift apart, and included rather than called so that the uniform kernel compiles exactly as it did when this was
 // its own source (an inlined shared body changes the compiled code: the callee is simplified before it is inlined).
-// MIXED_PB = 1: the member's parameters are per lane (the lane's book or market u = b: table[u * n_desc + j]), loaded
+// BK_PB = 1: the member's parameters are per lane (the lane's book or market u = b: table[u * n_desc + j]), loaded
 // for the fields its kind uses (lane_desc), and the deferred-price queue rounds each entry with its own book's tick.
   // dynamic LDS (up to ~82 KB at R = 8; MI355X allows 160 KB per workgroup), see mixed_lanes_lds_bytes():
   //   event list of lane l: list[k * 64 + l] (u16) | live / listed masks of the open book, word w of lane l at
@@ -25,7 +25,7 @@
   double* q_arg = zf + 257;
   double* q_mid = q_arg + MLQ_CAP;
   uint32_t* q_info = reinterpret_cast<uint32_t*>(q_mid + MLQ_CAP);
-#if MIXED_PB
+#if BK_PB
   // PB: a queued price is rounded with its own book's tick - the member's tick_f of each lane, written at the member's start
   double* q_tick = reinterpret_cast<double*>(q_info + MLQ_CAP);
 #endif
@@ -193,7 +193,7 @@
         const double arg = q_arg[base + e], mid_e = q_mid[base + e];
         const uint32_t info = q_info[base + e], slot = (info >> 6) & 0x1FFu;
         const double dist = pm::fabs_(pm::exp(arg));
-#if MIXED_PB
+#if BK_PB
         const double tick_e = q_tick[info & 63u];
         (void)tick_f;
         const uint32_t price = (info & 0x8000u) ? round_price_down(mid_e - dist, tick_e) : round_price_up(mid_e + dist, tick_e);
@@ -230,7 +230,7 @@
   };
 
   for (uint32_t j = 0; j < ma.n_desc; ++j) {  // members in declaration order (crates/macros/src/lib.rs:57-73)
-#if MIXED_PB
+#if BK_PB
     // the shared fields (type, n, slot_base, n_f) of unit 0's row, the rest from this lane's unit's row
     MixedDesc D = ma.descs[j];
     lane_desc(D, table + ((size_t)b * ma.n_desc + j));

@@ -200,9 +200,9 @@ __device__ __forceinline__ double zig_from_stream(const Stream64& S, const doubl
 
 template <int R>
 __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixed_wave(DevArgs a, MixedArgs ma, WaveArgs wa, WaveLists wl) {
-#define MIXED_PB 0
+#define BK_PB 0
 #include "wave_mixed_body.inc"
-#undef MIXED_PB
+#undef BK_PB
 }
 
 // PB (bk_set_agents_per_book): the members' records come from the book's row of the per-unit table
@@ -210,9 +210,9 @@ template <int R, bool PB>
 __global__ __launch_bounds__(64 * MW_WPB, MW_WPB > 8 ? 5 : 4) void k_agents_mixed_wave(DevArgs a, MixedArgs ma, WaveArgs wa, WaveLists wl,
                                                                                   const MixedDesc* table) {
   static_assert(PB, "the uniform form is k_agents_mixed_wave<R>(DevArgs, MixedArgs, WaveArgs, WaveLists)");
-#define MIXED_PB 1
+#define BK_PB 1
 #include "wave_mixed_body.inc"
-#undef MIXED_PB
+#undef BK_PB
 }
 
 // (Re)build the wave-per-book lists from the pool after another pipeline (or a restore / a fresh set of agents): live

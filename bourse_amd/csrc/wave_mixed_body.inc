@@ -1,5 +1,5 @@
-// wave_mixed_body.inc - the body of k_agents_mixed_wave (wave_mixed.hpp), included by the uniform kernel with MIXED_PB = 0
-// and by its per-unit form (bk_set_agents_per_book) with MIXED_PB = 1, which reads member j of the book's row of the table,
+// wave_mixed_body.inc - the body of k_agents_mixed_wave (wave_mixed.hpp), included by the uniform kernel with BK_PB = 0
+// and by its per-unit form (bk_set_agents_per_book) with BK_PB = 1, which reads member j of the book's row of the table,
 // table[book * n_desc + j].  Included rather than called so that the uniform kernel compiles exactly as it did when this
 // was its own source (see mixed_lanes_body.inc).
   extern __shared__ uint32_t mw_lds[];
@@ -34,7 +34,7 @@
   uint32_t* st = a.state + (size_t)book * a.state_stride;
   uint32_t* bt = a.batch + (size_t)book * a.batch_stride;
   uint32_t* wc = wa.wcache + (size_t)book * WC_STRIDE;
-#if MIXED_PB
+#if BK_PB
   const MixedDesc* row = table + (size_t)book * ma.n_desc;  // the book's row (wave-uniform: scalar loads, as ma.descs[j])
 #endif
   const uint32_t hdr = st[lane];
@@ -80,7 +80,7 @@
   uint32_t id_extra = 0;             // ids consumed by RandomAgents members (fixed slots): id = next_id + both counters
 
   for (uint32_t j = 0; j < ma.n_desc; ++j) {  // members in declaration order (crates/macros/src/lib.rs:57-73)
-#if MIXED_PB
+#if BK_PB
     const MixedDesc D = row[j];
 #else
     const MixedDesc D = ma.descs[j];
