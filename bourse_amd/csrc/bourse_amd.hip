@@ -47,6 +47,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "wave_mixed.hpp"
 #include "step_events.hpp"
 #include "agents_ingress.hpp"
+#include "members_ingress.hpp"
 
 using namespace bkd;
 
@@ -207,6 +208,16 @@ struct bk_env {
   DevBuf<uint32_t> agent_held;
   DevBuf<Group> agent_groups;
   bool agent_held_stale = true;
+  // bk_update_members: the members' `orders` lists [n_books][n_mixed][member_list_cap] (a RandomAgents member's row holds its
+  // agents' held ids) with their lengths, MomentumAgent's momentum / last_price [n_books][n_mixed][2] and "has a last
+  // price" bits [n_books], the members' first trader ids as the kernel reads them; re-made (empty lists, no momentum
+  // state) at the first bk_update_members after a bk_set_agents* call
+  DevBuf<uint32_t> member_lists, member_lens, member_flags, member_id0_dev;
+  DevBuf<uint64_t> member_state;
+  std::vector<uint32_t> member_id0;    // [units or 1][n_mixed] agent_id_start, as installed
+  std::vector<uint32_t> member_type, member_n;  // [n_mixed] kinds and sizes (every unit shares them)
+  uint32_t member_list_cap = 0;
+  bool member_lists_stale = true;
   // bk_set_agent_order_log: bk_run's RandomAgents record their orders in dorders / order_log (k_step_batch_log); the
   // readers mirror them like the device ingress's
   bool agent_log = false;
@@ -1609,6 +1620,95 @@ int bk_update_agents(bk_env* env) {
   return BK_OK;
 }
 
+// agents.update(env, rng) of the installed AgentSet - NoiseAgent / MomentumAgent members (noise_agent.rs:127-176,
+// momentum_agent.rs:146-208, common.rs:56-75), with or without RandomAgents members, in declaration order - for every book
+// into the device-resident queues at this point of the book's stream (members_ingress.hpp k_update_members), asynchronous
+// on the env's stream.  The members only place and cancel: k_ingest's hint for k_step_events stays as it is.
+int bk_update_members(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_members queues the members' orders in the device-resident queues: call "
+                                     "bk_device_ingress_enable first");
+  if (env->M > 1) return fail(BK_INVALID_ARGUMENT, "bk_update_members runs an AgentSet on independent books (assets == 1)");
+  if (!env->n_mixed) {
+    if (!env->groups.empty())
+      return fail(BK_INVALID_ARGUMENT, "this env has RandomAgents groups only (bk_set_random_agents*): they are run by "
+                                       "bk_update_agents");
+    return fail(BK_INVALID_ARGUMENT, "no AgentSet installed (bk_set_agents / bk_set_agents_per_book)");
+  }
+  if (int rc = use_device(env)) return rc;
+  const uint32_t B = env->cfg.n_books, NM = env->n_mixed;
+  if (env->member_lists_stale) {  // members (re)installed: empty lists, no momentum state; the old orders stay, unowned
+    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
+    uint32_t max_n = 0;
+    for (uint32_t n : env->member_n) max_n = std::max(max_n, n);
+    env->member_list_cap = bkd::ingress::members_list_cap(static_cast<uint32_t>(env->R), max_n);
+    const size_t rows = static_cast<size_t>(B) * NM;
+    HIPCHK(env->member_lists.alloc(rows * env->member_list_cap));
+    HIPCHK(env->member_lens.alloc(rows));
+    HIPCHK(env->member_state.alloc(rows * 2));
+    HIPCHK(env->member_flags.alloc(B));
+    HIPCHK(env->member_id0_dev.alloc(env->member_id0.size()));
+    HIPCHK(hipMemset(env->member_lists.p, 0xFF, rows * env->member_list_cap * 4));  // (a RandomAgents member's agents hold None)
+    HIPCHK(hipMemset(env->member_lens.p, 0, rows * 4));
+    HIPCHK(hipMemset(env->member_state.p, 0, rows * 16));
+    HIPCHK(hipMemset(env->member_flags.p, 0, static_cast<size_t>(B) * 4));
+    HIPCHK(hipMemcpy(env->member_id0_dev.p, env->member_id0.data(), env->member_id0.size() * 4, hipMemcpyHostToDevice));
+    env->member_lists_stale = false;
+  }
+  bkd::ingress::MembersIngressArgs g{};
+  g.state = env->state.p;
+  g.state_stride = env->stride;
+  g.n_members = NM;
+  g.log_cap = env->cfg.max_orders;
+  g.qcap = env->qcap;
+  g.tick = env->cfg.tick_size;
+  g.descs = env->mtable.empty() ? env->mixed_descs.p : env->dmtable.p;
+  g.id_start = env->member_id0_dev.p;
+  g.d_stride = env->mtable.empty() ? 0u : NM;
+  g.list_cap = env->member_list_cap;
+  g.lists = env->member_lists.p;
+  g.lens = env->member_lens.p;
+  g.mstate = env->member_state.p;
+  g.mflags = env->member_flags.p;
+  g.q = env->dq.p;
+  g.qlen = env->dqlen.p;
+  g.dorders = env->dorders.p;
+  g.order_log = env->order_log.p;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(bkd::ingress::k_update_members<decltype(r)::value>, dim3(B), dim3(64), 0, env->stream, g);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;
+  return BK_OK;
+}
+
+// Member `member`'s `orders` vector of one book as the device holds it after the last bk_update_members (the ids a
+// RandomAgents member's agents hold, u64::MAX for None): *n_out = its length, the first min(cap, length) ids in out_ids.
+int bk_member_orders(bk_env* env, uint32_t book, uint32_t member, uint32_t cap, uint64_t* out_ids, uint32_t* n_out) {
+  if (int rc = check_book(env, book)) return rc;
+  if (!env->device_ingress || !env->n_mixed)
+    return fail(BK_INVALID_ARGUMENT, "bk_member_orders reads the lists of bk_update_members: no AgentSet on a device-ingress env");
+  if (member >= env->n_mixed) return fail(BK_INVALID_ARGUMENT, "member index out of range");
+  if (cap && !out_ids) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  const bool random = env->member_type[member] == BK_AGENT_RANDOM;
+  uint32_t n = random ? env->member_n[member] : 0u;
+  std::vector<uint32_t> ids(n, AGENT_HELD_NONE);
+  if (!env->member_lists_stale) {  // (stale: installed and not yet updated - empty lists, every agent holds None)
+    HIPCHK(hipStreamSynchronize(env->stream));
+    const size_t row = static_cast<size_t>(book) * env->n_mixed + member;
+    if (!random) HIPCHK(hipMemcpy(&n, env->member_lens.p + row, 4, hipMemcpyDeviceToHost));
+    n = std::min(n, env->member_list_cap);
+    ids.resize(n);
+    if (n) HIPCHK(hipMemcpy(ids.data(), env->member_lists.p + row * env->member_list_cap, n * 4ull, hipMemcpyDeviceToHost));
+  }
+  for (uint32_t i = 0; i < n && i < cap; ++i) out_ids[i] = ids[i] == AGENT_HELD_NONE ? ~0ull : ids[i];
+  if (n_out) *n_out = n;
+  return BK_OK;
+}
+
 int bk_order_status(bk_env* env, uint32_t book, uint64_t order_id, uint8_t* out_status) {
   if (int rc = check_book(env, book)) return rc;
   if (int rc = mirror_orders(env, book)) return rc;
@@ -1756,7 +1856,10 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
   if (int rc = make_mixed_descs(members, n_members, assets, env->asset_tick, ds.data(), fixed_a, &msg))  // (agent_table.hpp)
     return fail(rc, msg);
   if (!mixed_capacity_ok(fixed_a, env->M, env->cfg.max_live_orders)) return fail(BK_CAPACITY, MIXED_CAPACITY_MSG);
-  return install_members(env, ds, n_members, assets, fixed_a, {});
+  if (int rc = install_members(env, ds, n_members, assets, fixed_a, {})) return rc;
+  env->member_id0.resize(n_members);
+  for (uint32_t i = 0; i < n_members; ++i) env->member_id0[i] = members[i].agent_id_start;
+  return BK_OK;
 }
 
 // The members' records into the env: `ds` = the (shared) row every unit's kernels and the list rebuilds read, `table` =
@@ -1773,6 +1876,10 @@ static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32
   HIPCHK(hipMemcpy(env->mixed_descs.p, ds.data(), ds.size() * sizeof(MixedDesc), hipMemcpyHostToDevice));
   env->n_mixed = n_members;
   env->n_fixed = fixed;
+  env->member_type.resize(n_members);
+  env->member_n.resize(n_members);
+  for (uint32_t i = 0; i < n_members; ++i) env->member_type[i] = ds[i].type, env->member_n[i] = ds[i].n;
+  env->member_lists_stale = true;  // (a new AgentSet: empty lists, no momentum state; bk_update_members)
   env->wl_valid = false;
   for (uint32_t i = 0; i < MAX_MEMBERS; ++i) env->member_asset[i] = (assets && i < n_members) ? assets[i] : 0u;
   for (uint32_t as = 0; as < MAX_ASSETS; ++as) env->n_fixed_a[as] = fixed_a[as];
@@ -1823,7 +1930,10 @@ int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc*
     return fail(rc, msg);
   if (int rc = use_device(env)) return rc;
   const std::vector<MixedDesc> row0(t.begin(), t.begin() + n_members);
-  return install_members(env, row0, n_members, assets, fixed_a, std::move(t));
+  if (int rc = install_members(env, row0, n_members, assets, fixed_a, std::move(t))) return rc;
+  env->member_id0.resize(n);
+  for (size_t k = 0; k < n; ++k) env->member_id0[k] = members[k].agent_id_start;
+  return BK_OK;
 }
 
 // books one residency round of the fused wave kernel holds (the auto rule's `wave` limit): asked of the runtime once

@@ -1,0 +1,388 @@
+// members_ingress.hpp - agents.update(env, rng) of an AgentSet with NoiseAgent / MomentumAgent members (with or without
+// RandomAgents members, in declaration order: crates/macros/src/lib.rs:57-73) into the device-resident ingress queues
+// (bk_update_members).  The members and the submitted instructions of one env share every book's queue, its id counter and
+// its RNG, as the reference's background agents and a user's own agent share one `Env` and one `rng` (env.rs:116-219,
+// runner.rs:53-68).  The step itself is k_step_events' over that queue, unchanged.
+//
+// Restated semantics (paths relative to the reference repo):
+//   common::cancel_live_orders            crates/step_sim/src/agents/common.rs:56-75
+//   NoiseAgent::update                    crates/step_sim/src/agents/noise_agent.rs:127-176
+//   MomentumAgent::update                 crates/step_sim/src/agents/momentum_agent.rs:146-208
+//   RandomAgents::update                  crates/step_sim/src/agents/random_agent.rs:85-119
+// with the draws, thresholds and f64 routines of mixed_update_and_shuffle (mixed_agents.hpp:256-352) - the same MixedDesc
+// records, the same pm_math.hpp functions, no FMA contraction.
+//
+// One wave per book.  The walk over a member's list and its traders is the book's serial RNG stream - wave-uniform, the RNG
+// in scalar registers; everything else is lane-parallel:
+//   * a member's `orders` vector is a row of ids in device memory, in insertion (= ascending id) order.  The filter of
+//     cancel_live_orders takes 64 entries per pass into lanes.  Status::Active of an entry = its id rests in the book's pool
+//     right now: ONE SWEEP over the pool's ids per pass - every live register's 64 ids are broadcast in turn (v_readlane)
+//     and compared with all 64 entries at once.  That is 3 instructions per pool slot and pass whatever the list holds;
+//     R ballots per entry cost the same at a full pass but sit inside the serial walk, and an LDS table of the live ids
+//     needs the same 64 R compares per pass behind an LDS round trip.  Registers of the pool that hold nothing live are
+//     skipped.  An order queued earlier in the same step is New (not yet in the pool), a filled or cancelled one has left
+//     it: both are dropped without a draw - the order log is not read;
+//   * the draws that follow are one next_u32 per Active entry, in list order; the kept ids go back compacted (mbcnt), the
+//     cancellation records to the queue in list order;
+//   * the traders' loop collects its New orders in lanes (v_writelane), 64 at a time, and writes their records, their
+//     `dorders` halves, their first order-log entries (k_ingest's, book_device.hpp:1838-1858) and the list's new entries
+//     lane-parallel in event order;
+//   * a RandomAgents member keeps its agents' held ids (AGENT_HELD_NONE = None) in the same row and walks them exactly as
+//     k_update_agents does (agents_ingress.hpp:69-112);
+//   * MomentumAgent's momentum / last_price / "has a last price" live in an array of their own (the header's H_GST words
+//     belong to bk_run's kernels); the RNG words, H_NEXT_ID, the flags and the queue length are written once per book.
+// Capacity: an event beyond the queue's room, or a New order once the u32 id space is exhausted, is dropped and the book
+// flagged FLAG_EVENT_OVERFLOW (the draws are taken all the same; a dropped New consumes no id and enters no list).  A list
+// row has 64 R + max n_agents entries: after the filter it holds Active orders only (at most the pool's slots), and one
+// update pushes at most n_agents more.
+#pragma once
+#include "agents_ingress.hpp"
+#include "mixed_agents.hpp"
+
+#pragma clang fp contract(off)
+
+namespace bkd {
+namespace ingress {
+
+struct MembersIngressArgs {
+  uint32_t* state;
+  uint32_t state_stride, n_members, log_cap, qcap;
+  uint32_t tick;            // the book's tick size (create_order's check)
+  const MixedDesc* descs;   // member j of book b: descs[b * d_stride + j] (the per-book table; d_stride 0 = one row for all)
+  const uint32_t* id_start; // ... and its first trader id, id_start[b * d_stride + j]
+  uint32_t d_stride;
+  uint32_t list_cap;        // entries per row
+  uint32_t* lists;          // [n_books][n_members][list_cap] order ids
+  uint32_t* lens;           // [n_books][n_members]
+  uint64_t* mstate;         // [n_books][n_members][2] momentum, last_price (f64 bits)
+  uint32_t* mflags;         // [n_books] bit j: member j has a last price
+  uint4* q;                 // [n_books][qcap] event records (k_ingest's layout)
+  uint32_t* qlen;           // [n_books]
+  uint4* dorders;           // [n_books][log_cap][2] immutable halves
+  DevOrderLog* order_log;
+};
+
+// rows this size never overflow (see above); the host sizes them with it
+constexpr uint32_t members_list_cap(uint32_t R, uint32_t max_n_agents) { return 64u * R + max_n_agents; }
+static_assert(members_list_cap(8, 0xFFFFu) == 512u + 65535u, "a row holds the pool's slots and one update's pushes");
+
+// one MixedDesc record (128 bytes) through the scalar cache: a wave-uniform address, written by the host only
+__device__ __forceinline__ MixedDesc sload_desc(const MixedDesc* p) {
+  bk_u32x16 a, b;
+  asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b)
+               : "s"(p));
+  MixedDesc D;
+  D.type = a[0], D.n = a[1], D.thr = a[2], D.tick_lo = a[3], D.tick_rng = a[4], D.tick_zone = a[5], D.vol_lo = a[6];
+  D.vol_rng = a[7], D.vol_zone = a[8], D.tick_size = a[9], D.thr_limit = a[10], D.thr_market = a[11];
+  D.keep_thr = (int32_t)a[12], D.trade_vol = a[13], D.slot_base = a[14], D.pad = a[15];
+  D.mu = pm::from_bits(mk64(b[0], b[1])), D.sigma = pm::from_bits(mk64(b[2], b[3]));
+  D.decay = pm::from_bits(mk64(b[4], b[5])), D.demand = pm::from_bits(mk64(b[6], b[7]));
+  D.scale = pm::from_bits(mk64(b[8], b[9])), D.order_ratio = pm::from_bits(mk64(b[10], b[11]));
+  D.n_f = pm::from_bits(mk64(b[12], b[13])), D.tick_f = pm::from_bits(mk64(b[14], b[15]));
+  return D;
+}
+
+// what one book's update carries from member to member
+struct Walk {
+  uint32_t next_id, flags, n_ev, room, q0, t_lo, t_hi, log_cap;
+  uint32_t book;
+  uint4* q;
+  uint4* dorders;
+  DevOrderLog* order_log;
+};
+
+// New orders collected in lanes, in event order: lane k holds the k-th of the batch (ids id0 + k)
+struct NewBatch {
+  uint32_t price, trader;  // per lane
+  uint64_t bidm, limm;     // bid side; limit orders (they enter the member's list)
+  uint32_t cnt, id0, ev0;
+};
+
+// the batch's records, dorders halves and first log entries (k_ingest's), and the limit orders' ids onto the list
+__device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t vol, uint32_t* list, uint32_t& len,
+                                          uint32_t list_cap, int lane) {
+  if (N.cnt == 0) return;
+  const bool mine = (uint32_t)lane < N.cnt;
+  const uint32_t id = N.id0 + (uint32_t)lane;
+  const uint32_t bid = lane_bit(N.bidm) ? 1u : 0u;
+  if (mine) {
+    W.q[W.q0 + N.ev0 + (uint32_t)lane] = make_uint4(bid << 8, id, N.price, vol);
+    if (id < W.log_cap) {
+      uint4* d = W.dorders + ((size_t)W.book * W.log_cap + id) * 2;
+      d[0] = make_uint4(vol, N.trader, N.price, bid);
+      d[1] = make_uint4(W.t_lo, W.t_hi, 0u, 0u);
+      // initial order-log entry: status New, nothing traded, provisional key (price, 0) (orderbook.rs:388-391)
+      uint4* lg = reinterpret_cast<uint4*>(W.order_log + (size_t)W.book * W.log_cap + id);
+      lg[0] = make_uint4(0u, vol, N.price, N.price);
+      lg[1] = make_uint4(W.t_lo, W.t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
+      lg[2] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(N.limm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)N.limm, 0u));
+  if (lane_bit(N.limm) && len + rank < list_cap) list[len + rank] = id;
+  len += (uint32_t)__builtin_popcountll(N.limm);
+  N.cnt = 0;
+  N.bidm = N.limm = 0;
+}
+
+// Env::place_order from a Noise / Momentum trader: the id and the New event (dropped and flagged beyond the queue's room
+// or the id space); a limit price off the book's tick grid is flagged and creates nothing (mixed_create,
+// mixed_agents.hpp:134-140); a market order carries the extreme price of its side (orderbook.rs:595) and takes no check
+__device__ __forceinline__ void place_new(Walk& W, NewBatch& N, bool limit, bool is_bid, uint32_t price, uint32_t trader,
+                                          uint32_t tick, uint32_t vol, uint32_t* list, uint32_t& len, uint32_t list_cap,
+                                          int lane) {
+  if (limit && price % tick != 0) {
+    W.flags |= FLAG_PRICE_TICK;
+    return;
+  }
+  if (!(W.n_ev < W.room && W.next_id < AGENT_HELD_NONE - 1u)) {
+    W.flags |= FLAG_EVENT_OVERFLOW;
+    return;
+  }
+  if (N.cnt == 64u) flush_new(W, N, vol, list, len, list_cap, lane);
+  if (N.cnt == 0) {
+    N.id0 = W.next_id;
+    N.ev0 = W.n_ev;
+  }
+  const uint64_t bit = 1ull << N.cnt;
+  N.price = wrl(price, N.cnt, N.price);
+  N.trader = wrl(trader, N.cnt, N.trader);
+  N.bidm |= is_bid ? bit : 0ull;
+  N.limm |= limit ? bit : 0ull;
+  N.cnt += 1;
+  W.n_ev += 1;
+  W.next_id += 1;
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
+  const int lane = threadIdx.x;
+  const uint32_t book = blockIdx.x;
+  uint32_t* st = g.state + (size_t)book * g.state_stride;
+  const uint32_t hdr = st[lane];
+  uint64_t live[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) live[r] = mk64(rdl(hdr, H_LIVE0 + 2 * r), rdl(hdr, H_LIVE0 + 2 * r + 1));
+  uint32_t pid[R];  // the pool's ids; AGENT_HELD_NONE where nothing rests (no order has that id)
+  double mid;       // OrderBook::mid_price (orderbook.rs:272-276) of the book as it stands: updates only queue events
+  {
+    uint32_t mb = 0u, mk = 0xFFFFFFFFu;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint32_t* p = st + HDR_DW + r * POOL_FIELDS * 64;
+      const uint32_t price = p[0 * 64 + lane], meta = p[4 * 64 + lane];
+      pid[r] = sel(live[r], p[2 * 64 + lane], AGENT_HELD_NONE);
+      const bool is_bid = (meta & 2u) != 0;
+      mb = max(mb, (lane_bit(live[r]) && is_bid) ? price : 0u);
+      mk = min(mk, (lane_bit(live[r]) && !is_bid) ? price : 0xFFFFFFFFu);
+    }
+    const uint32_t bid = wave_umax(mb), ask = wave_umin(mk);
+    mid = static_cast<double>(bid) + 0.5 * static_cast<double>(ask - bid);
+  }
+  Rng rng;
+  rng.s0 = mk64(rdl(hdr, H_S0_LO), rdl(hdr, H_S0_HI));
+  rng.s1 = mk64(rdl(hdr, H_S1_LO), rdl(hdr, H_S1_HI));
+  Walk W;
+  W.next_id = rdl(hdr, H_NEXT_ID), W.flags = rdl(hdr, H_FLAGS);
+  W.t_lo = rdl(hdr, H_T_LO), W.t_hi = rdl(hdr, H_T_HI);
+  W.q0 = rfl(g.qlen[book]);
+  W.room = g.qcap > W.q0 ? g.qcap - W.q0 : 0u;
+  W.n_ev = 0;
+  W.log_cap = g.log_cap;
+  W.book = book;
+  W.q = g.q + (size_t)book * g.qcap;
+  W.dorders = g.dorders;
+  W.order_log = g.order_log;
+  const MixedDesc* row = g.descs + (size_t)book * g.d_stride;
+  const uint32_t* id_start = g.id_start + (size_t)book * g.d_stride;
+  uint32_t mflags = rfl(g.mflags[book]);
+
+  for (uint32_t j = 0; j < g.n_members; ++j) {
+    const MixedDesc D = sload_desc(row + j);
+    uint32_t* list = g.lists + ((size_t)book * g.n_members + j) * g.list_cap;
+    if (D.type == 0) {
+      // ---- RandomAgents::update (random_agent.rs:85-119): k_update_agents' walk over the member's held ids
+      const uint32_t n_agents = min(D.n, g.list_cap);
+      for (uint32_t base = 0; base < n_agents; base += 64) {
+        const uint32_t n_here = min(64u, n_agents - base);
+        const bool in = (uint32_t)lane < n_here;
+        const uint32_t h = in ? list[base + lane] : AGENT_HELD_NONE;
+        const uint32_t ev0 = W.n_ev, id0 = W.next_id;
+        uint64_t canm = 0, newm = 0, bidm = 0, dropm = 0;
+        uint32_t e_price = 0, e_vol = 0, e_trader = 0;
+        for (uint32_t l = 0; l < n_here; ++l) {
+          const uint32_t x = rng.next_u32();  // p = gen::<f32>()  (random_agent.rs:91)
+          if ((x >> 8) >= D.thr) continue;    // inactive: keeps what it holds
+          const uint64_t bit = 1ull << l;
+          const uint32_t hl = rdl(h, l);
+          uint64_t act = 0;
+          if (hl != AGENT_HELD_NONE) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) act |= __ballot(pid[r] == hl);
+          }
+          if (act) {  // holds an Active order: env.cancel_order (:95-97)
+            if (W.n_ev < W.room) {
+              canm |= bit;
+              W.n_ev += 1;
+            } else {
+              dropm |= bit;
+              W.flags |= FLAG_EVENT_OVERFLOW;
+            }
+            continue;
+          }
+          // env.place_order with side, tick, vol drawn in this order (:99-111)
+          const uint32_t side = rng.below(2u, 0x7FFFFFFFu);  // [Ask, Bid].choose: 0 = Ask, 1 = Bid
+          const uint32_t tick = D.tick_lo + rng.below(D.tick_rng, D.tick_zone);
+          const uint32_t vol = D.vol_lo + rng.below(D.vol_rng, D.vol_zone);
+          if (W.n_ev < W.room && W.next_id < AGENT_HELD_NONE - 1u) {
+            newm |= bit;
+            bidm |= side ? bit : 0ull;
+            e_price = wrl(tick * D.tick_size, l, e_price);
+            e_vol = wrl(vol, l, e_vol);
+            e_trader = wrl(base + l, l, e_trader);  // TraderId = the agent's index in its member
+            W.n_ev += 1;
+            W.next_id += 1;
+          } else {
+            dropm |= bit;
+            W.flags |= FLAG_EVENT_OVERFLOW;
+          }
+        }
+        // the pass's records, in agent order
+        const uint64_t evm = canm | newm;
+        const uint32_t rank_ev = __builtin_amdgcn_mbcnt_hi((uint32_t)(evm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)evm, 0u));
+        const uint32_t rank_new = __builtin_amdgcn_mbcnt_hi((uint32_t)(newm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)newm, 0u));
+        const bool is_new = lane_bit(newm), is_can = lane_bit(canm);
+        const uint32_t id = id0 + rank_new;
+        const uint32_t bid = lane_bit(bidm) ? 1u : 0u;
+        if (is_can) W.q[W.q0 + ev0 + rank_ev] = make_uint4(1u, h, 0u, 0u);
+        if (is_new) {
+          W.q[W.q0 + ev0 + rank_ev] = make_uint4(bid << 8, id, e_price, e_vol);
+          if (id < g.log_cap) {
+            uint4* d = g.dorders + ((size_t)book * g.log_cap + id) * 2;
+            d[0] = make_uint4(e_vol, e_trader, e_price, bid);
+            d[1] = make_uint4(W.t_lo, W.t_hi, 0u, 0u);
+            uint4* lg = reinterpret_cast<uint4*>(g.order_log + (size_t)book * g.log_cap + id);
+            lg[0] = make_uint4(0u, e_vol, e_price, e_price);
+            lg[1] = make_uint4(W.t_lo, W.t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
+            lg[2] = make_uint4(0u, 0u, 0u, 0u);
+          }
+        }
+        if (in) list[base + lane] = is_new ? id : (is_can || lane_bit(dropm)) ? AGENT_HELD_NONE : h;
+      }
+      continue;
+    }
+    // ---- common::cancel_live_orders (common.rs:56-75): the Active entries in list order, one f32 draw each;
+    // `draw > p_cancel` keeps the entry, otherwise its cancellation is queued and it leaves the list
+    const uint32_t len0 = min(rfl(g.lens[(size_t)book * g.n_members + j]), g.list_cap);
+    uint32_t len = 0;
+    for (uint32_t base = 0; base < len0; base += 64) {
+      const bool in = base + (uint32_t)lane < len0;
+      const uint32_t e = in ? list[base + lane] : AGENT_HELD_NONE;
+      uint64_t actm = 0;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (live[r] == 0) continue;
+        for (uint32_t k = 0; k < 64; ++k) actm |= __ballot(e == rdl(pid[r], k));
+      }
+      // (an entry beyond the list, or a pool lane with nothing live, is AGENT_HELD_NONE on both sides)
+      actm &= __ballot(in);
+      const uint32_t ev0 = W.n_ev;
+      uint64_t keepm = 0, canm = 0;
+      for (uint64_t m = actm; m; m &= m - 1ull) {
+        const uint64_t bit = m & (~m + 1ull);
+        const uint32_t x = rng.next_u32();
+        if ((int32_t)(x >> 8) > D.keep_thr) {
+          keepm |= bit;
+        } else if (W.n_ev < W.room) {  // env.cancel_order(id)
+          canm |= bit;
+          W.n_ev += 1;
+        } else {
+          W.flags |= FLAG_EVENT_OVERFLOW;
+        }
+      }
+      const uint32_t rank_can = __builtin_amdgcn_mbcnt_hi((uint32_t)(canm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)canm, 0u));
+      const uint32_t rank_keep = __builtin_amdgcn_mbcnt_hi((uint32_t)(keepm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keepm, 0u));
+      if (lane_bit(canm)) W.q[W.q0 + ev0 + rank_can] = make_uint4(1u, e, 0u, 0u);
+      if (lane_bit(keepm)) list[len + rank_keep] = e;  // (len + rank <= base + lane: behind every entry still to be read)
+      len += (uint32_t)__builtin_popcountll(keepm);
+    }
+    // ---- the traders' loops (mixed_agents.hpp:294-352)
+    const uint32_t trader0 = rfl(id_start[j]);
+    NewBatch N;
+    N.price = N.trader = 0;
+    N.bidm = N.limm = 0;
+    N.cnt = N.id0 = N.ev0 = 0;
+    if (D.type == 1) {
+      // ---- NoiseAgent::update (noise_agent.rs:127-176)
+      for (uint32_t t = 0; t < D.n; ++t) {
+        if ((rng.next_u32() >> 8) < D.thr_limit) {                 // gen::<f32>() < p_limit
+          const bool buy = next_u64(rng) < 0x8000000000000000ull;  // gen_bool(0.5)
+          const double dist = pm::fabs_(uni(pm::exp(D.mu + D.sigma * sample_standard_normal(rng))));
+          const uint32_t price = rfl(buy ? round_price_down(mid - dist, D.tick_f) : round_price_up(mid + dist, D.tick_f));
+          place_new(W, N, true, buy, price, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
+        }
+        if ((rng.next_u32() >> 8) < D.thr_market) {                // gen::<f32>() < p_market
+          const bool buy = next_u64(rng) < 0x8000000000000000ull;
+          place_new(W, N, false, buy, buy ? 0xFFFFFFFFu : 0u, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
+        }
+      }
+    } else {
+      // ---- MomentumAgent::update (momentum_agent.rs:146-208)
+      uint64_t* ms = g.mstate + ((size_t)book * g.n_members + j) * 2;
+      double m = 0.0, p_market = 0.0;
+      if ((mflags >> j) & 1u) {
+        const double gm = uni(pm::from_bits(ms[0])), gl = uni(pm::from_bits(ms[1]));
+        m = uni(gm * (1.0 - D.decay) + D.decay * (mid - gl));
+        p_market = uni(D.demand * pm::tanh(D.scale * m) / D.n_f);
+      }
+      uint64_t thr_l, thr_m;
+      {
+        const double p_limit = D.order_ratio * p_market;
+        thr_l = thr53(p_limit);
+        thr_m = thr53(p_market);
+        thr_l = mk64(rfl((uint32_t)thr_l), rfl((uint32_t)(thr_l >> 32)));
+        thr_m = mk64(rfl((uint32_t)thr_m), rfl((uint32_t)(thr_m >> 32)));
+      }
+      const int sgn = (m > 0.0) ? 1 : ((m < 0.0) ? -1 : 0);
+      for (uint32_t t = 0; t < D.n; ++t) {
+        if ((next_u64(rng) >> 11) < thr_l) {  // gen::<f64>() < p_limit
+          if (sgn != 0) {
+            const double dist = pm::fabs_(uni(pm::exp(D.mu + D.sigma * sample_standard_normal(rng))));
+            const uint32_t price =
+                rfl(sgn > 0 ? round_price_down(mid - dist, D.tick_f) : round_price_up(mid + dist, D.tick_f));
+            place_new(W, N, true, sgn > 0, price, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
+          }
+        }
+        if ((next_u64(rng) >> 11) < thr_m) {  // gen::<f64>() < p_market
+          if (sgn != 0)
+            place_new(W, N, false, sgn > 0, sgn > 0 ? 0xFFFFFFFFu : 0u, trader0 + t, g.tick, D.trade_vol, list, len,
+                      g.list_cap, lane);
+        }
+      }
+      if (lane == 0) {  // momentum, last_price, once per update
+        ms[0] = pm::to_bits(m);
+        ms[1] = pm::to_bits(mid);
+      }
+      mflags |= 1u << j;
+    }
+    flush_new(W, N, D.trade_vol, list, len, g.list_cap, lane);
+    if (lane == 0) g.lens[(size_t)book * g.n_members + j] = min(len, g.list_cap);
+  }
+  // the header words this call changed: the RNG, the id counter, the flags; then the members' flags and the queue's length
+  uint32_t w = hdr;
+  w = wrl((uint32_t)rng.s0, H_S0_LO, w);
+  w = wrl((uint32_t)(rng.s0 >> 32), H_S0_HI, w);
+  w = wrl((uint32_t)rng.s1, H_S1_LO, w);
+  w = wrl((uint32_t)(rng.s1 >> 32), H_S1_HI, w);
+  w = wrl(W.next_id, H_NEXT_ID, w);
+  w = wrl(W.flags, H_FLAGS, w);
+  if ((lane >= H_S0_LO && lane <= H_NEXT_ID) || lane == H_FLAGS) st[lane] = w;
+  if (lane == 0) {
+    g.mflags[book] = mflags;
+    g.qlen[book] = W.q0 + W.n_ev;
+  }
+}
+
+}  // namespace ingress
+}  // namespace bkd

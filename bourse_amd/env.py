@@ -326,6 +326,28 @@ class ManyBookEnv:
             if self.strict:
                 self.raise_on_flags()
 
+    def update_members(self, sync: bool = True):
+        """``agents.update(env, rng)`` of the installed AgentSet - NoiseAgent / MomentumAgent members (noise_agent.rs:127-176,
+        momentum_agent.rs:146-208), with or without RandomAgents members, in declaration order - for every book into the
+        device-resident queues (``bk_update_members``): the members' placements and cancellations join the submitted
+        instructions in call order, drawn from the book's own RNG, and the next ``step()`` trades all of it.  Needs
+        ``enable_device_ingress()`` first, then ``set_agents`` / ``set_agents_per_book`` (an all-RandomAgents set is
+        ``update_agents``').  ``sync=False``: queue it on the env's stream and return (no flag check)."""
+        check(self._L.bk_update_members(self._h))
+        if sync:
+            self.sync()
+            if self.strict:
+                self.raise_on_flags()
+
+    def member_orders(self, book: int, member: int) -> np.ndarray:
+        """Member ``member``'s ``orders`` vector of one book after the last ``update_members`` (``bk_member_orders``), u64
+        in list order; for a RandomAgents member the ids its agents hold, ``2**64 - 1`` for None."""
+        n = C.c_uint32(0)
+        check(self._L.bk_member_orders(self._h, int(book), int(member), 0, None, C.byref(n)))
+        out = np.zeros(max(int(n.value), 1), dtype=np.uint64)
+        check(self._L.bk_member_orders(self._h, int(book), int(member), int(n.value), _lib.p64(out), C.byref(n)))
+        return out[:int(n.value)]
+
     # ------------------------------------------------------------ device-resident instruction ingress
     def enable_device_ingress(self, queue_capacity: int = 256):
         """Switch this (fresh) env to instructions submitted FROM DEVICE MEMORY (``bk_device_ingress_enable``): at most

@@ -224,6 +224,27 @@ int bk_step_async(bk_env* env);
  * BK_FLAG_EVENT_OVERFLOW.  Asynchronous on the env's stream.  Order: bk_device_ingress_enable, then the agents.
  * BK_INVALID_ARGUMENT (env unchanged): no device ingress, no RandomAgents groups, Noise / Momentum members, assets > 1. */
 int bk_update_agents(bk_env* env);
+/* bk_update_members: agents.update(env, rng) of the installed AgentSet (bk_set_agents / bk_set_agents_per_book:
+ * NoiseAgent and MomentumAgent members, with or without RandomAgents members) for every book on an env with the device
+ * ingress - replaces NoiseAgent::update (noise_agent.rs:127-176), MomentumAgent::update (momentum_agent.rs:146-208) with
+ * common::cancel_live_orders (common.rs:56-75), and RandomAgents::update (random_agent.rs:85-119), called member by member
+ * in declaration order (crates/macros/src/lib.rs:57-73) with the book's own RNG.  A Noise / Momentum member first walks
+ * its `orders` list: entries that are not Active (not resting in the book right now) are dropped without a draw, every
+ * Active one takes gen::<f32>() and is kept when the draw exceeds p_cancel, else its cancellation is queued; then every
+ * trader draws and places its limit order (around the mid price of the book as it stands, next id of the book, trader
+ * id agent_id_start + t, remembered in the list) and its market order (price u32::MAX for a bid, 0 for an ask).  A limit
+ * price off the book's tick grid sets BK_FLAG_PRICE_TICK and creates nothing.  The events are appended to the same queues
+ * as bk_submit_instructions_device's, in call order; a full queue or an exhausted id space drops the event and sets
+ * BK_FLAG_EVENT_OVERFLOW.  Every bk_set_agents* call empties the lists and clears the momentum state (the old orders
+ * stay on the books, unowned).  Asynchronous on the env's stream.
+ * BK_INVALID_ARGUMENT (env unchanged): no device ingress, no AgentSet installed (an all-RandomAgents set is
+ * bk_update_agents'), assets > 1. */
+int bk_update_members(bk_env* env);
+/* bk_member_orders: member `member`'s `orders` vector of one book as the device holds it after the last
+ * bk_update_members (NoiseAgent.orders / MomentumAgent.orders, noise_agent.rs:104, momentum_agent.rs:114), in list order;
+ * for a RandomAgents member the ids its agents hold (RandomAgents.orders, random_agent.rs:49), UINT64_MAX for None.
+ * *n_out = the vector's length; the first min(cap, length) ids go to out_ids.  Waits for the env's stream. */
+int bk_member_orders(bk_env* env, uint32_t book, uint32_t member, uint32_t cap, uint64_t* out_ids, uint32_t* n_out);
 /* HOST arrays through the device ingress (a BaseNumpyAgent-style caller: src/bourse/step_sim/agents/base_agent.py:67-116
  * returns host numpy arrays, runner.py:103-112 passes them to submit_instructions, rust/src/step_sim_numpy.rs:233-275).
  * Same arrays, same per-book semantics as bk_submit_instructions_device, but the pointers are HOST memory: the library

@@ -201,6 +201,16 @@ class ManyEnv {
   // ingress, bk_device_ingress_enable(handle(), ..), then the agents): the next step() trades them with the submitted
   // instructions.  Asynchronous on the env's stream.
   void update_agents() { check(bk_update_agents(h_)); }
+  // agents.update(env, rng) of an AgentSet with Noise / Momentum members into the same queues (bk_update_members)
+  void update_members() { check(bk_update_members(h_)); }
+  // member j's `orders` vector of book b after the last update_members (bk_member_orders; UINT64_MAX = None)
+  std::vector<uint64_t> member_orders(uint32_t book, uint32_t member) {
+    uint32_t n = 0;
+    check(bk_member_orders(h_, book, member, 0, nullptr, &n));
+    std::vector<uint64_t> ids(n);
+    check(bk_member_orders(h_, book, member, n, ids.data(), &n));
+    return ids;
+  }
   // record the agents' orders (bk_set_agent_order_log; before the first run): env(b).get_orders() answers after run
   void enable_agent_order_log() { check(bk_set_agent_order_log(h_, 1)); }
   void run(uint64_t n_steps) {
