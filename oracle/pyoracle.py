@@ -361,6 +361,15 @@ class _BookView:
             lib().orc_book_get_trades(self._b, a.ctypes.data_as(C.c_void_p), 0, n)
         return a
 
+    def keys(self):
+        """The priority key of every order (orderbook.rs:34-39) as (side, price, time) arrays, by order id.  A bid's key
+        price is MAX_PRICE - price."""
+        n = self.n_orders()
+        kb, kp, kt = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
+        if n:
+            lib().orc_book_get_keys(self._b, 0, n, kb.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(kp), _p64(kt))
+        return kb[:n], kp[:n], kt[:n]
+
     def get_orders(self):
         # PyOrder tuples, ref rust/src/types.rs:17-31
         return [
@@ -440,10 +449,7 @@ class OrderBook(_BookView):
         side = {1: "Bid", 0: "Ask"}
         status = ["New", "Active", "Filled", "Cancelled", "Rejected"]
         o = self.orders_array()
-        n = len(o)
-        kb, kp, kt = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
-        if n:
-            lib().orc_book_get_keys(self._b, 0, n, kb.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(kp), _p64(kt))
+        kb, kp, kt = self.keys()
         orders = [{
             "order": {"side": side[int(r["side"])], "status": status[int(r["status"])], "arr_time": int(r["arr_time"]),
                       "end_time": int(r["end_time"]), "vol": int(r["vol"]), "start_vol": int(r["start_vol"]),

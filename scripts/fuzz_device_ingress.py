@@ -5,9 +5,10 @@ same flow (bk_submit_instructions_host as tickets, two in flight, results fetche
 per-order host entries (themselves fuzzed against the oracle by scripts/fuzz_host.py).  GPU box.  FUZZ_LO / FUZZ_HI."""
 import os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import bourse_amd as bk
+import oracle_parity as P
 import test_gpu_device_ingress as D
 
 U64MAX = 2**64 - 1
@@ -77,12 +78,9 @@ for seed in range(lo, hi):
         assert np.array_equal(dev.history(), host.history()), (seed, "history")
         assert np.array_equal(dev.trade_counts(), host.trade_counts()), (seed, "trade counts")
         for b in sorted(set(int(x) for x in rng.integers(0, B, size=4))):
-            gd, gh, ga = dev.trades(b, first=0), host.trades(b, first=0), hst.trades(b, first=0)
-            od, oh, oa = dev.orders(b), host.orders(b), hst.orders(b)
-            for f in gd.dtype.names:
-                assert np.array_equal(gd[f], gh[f]) and np.array_equal(ga[f], gh[f]), (seed, b, f)
-            for f in od.dtype.names:
-                assert np.array_equal(od[f], oh[f]) and np.array_equal(oa[f], oh[f]), (seed, b, f)
+            for name, e in (("device", dev), ("host-array", hst)):
+                P.same_records(e.trades(b, first=0), host.trades(b, first=0), (seed, name, b), "trade")
+                P.same_records(e.orders(b), host.orders(b), (seed, name, b), "order")
         n += 1
         dev.close(); host.close(); hst.close()
     except AssertionError as e:

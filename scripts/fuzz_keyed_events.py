@@ -1,5 +1,6 @@
 """Fuzz the host-driven step on the keyed loop (step_events.hpp step_events_keyed) over fresh seeds: every book of small
-batches against its own oracle env - level 2 of every step, every trade, the whole order log - on random mixes of clean
+batches against its own oracle env - level 2 of every step, every trade, the live orders, the whole order log
+(tests/oracle_parity.py) - on random mixes of clean
 steps (new / cancel / modify / market orders: the keyed form) and steps that must fall back (volume 0, more events
 than pool slots, prices outside the key window, full pools), all four pool sizes, three tick sizes, narrow and wide price
 ranges, ordinary and extreme volumes.  Prints how many book-steps ran keyed.  GPU box.  FUZZ_LO / FUZZ_HI."""

@@ -1,7 +1,8 @@
 """Fuzz MarketEnv with RandomMarketAgents (ref crates/step_sim/src/market_env.rs:110-132, agents/random_agent.rs:122-220) over fresh
 seeds against the oracle's ManyMarkets: 1-4 assets with random tick sizes, 1-6 groups on random assets (some assets nobody trades),
 agent counts that land on every pool size (64 .. 512 slots), small and multi-part batches, launches in random chunks - L2 history of
-every step and book, RNG states, trades and live orders of sample books (tests/test_gpu_parity.py _compare_markets).  Since round 5
+every step and book, RNG states, trades and live orders in priority order of sample books (tests/test_gpu_parity.py
+_compare_markets, on the checks of tests/oracle_parity.py).  Since round 5
 the markets' step batches run on the keyed / assembly event loops (the other assets' events as events that do nothing).  GPU box."""
 import os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")

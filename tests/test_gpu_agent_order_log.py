@@ -5,6 +5,8 @@ one an env without the log runs."""
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 
 SEED, STEP, LEVELS = 101, 100_000, 10
@@ -23,35 +25,8 @@ def bk():
     return bourse_amd
 
 
-def oracle_state(oracle, view):
-    view._trading = True  # (OrderBook.state reads the book through the same queries a _BookView has)
-    return oracle.OrderBook.state(view)
-
-
-def oracle_keys(oracle, view, n):
-    import ctypes as C
-
-    kb, kp, kt = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
-    if n:
-        oracle.lib().orc_book_get_keys(view._b, 0, n, kb.ctypes.data_as(C.POINTER(C.c_uint8)), oracle._p32(kp),
-                                       oracle._p64(kt))
-    return kb[:n], kp[:n], kt[:n]
-
-
-def check_book(bk, oracle, env, b, view, state=True):
-    got, want = env.orders(b), view.orders_array()
-    assert len(got) == len(want) == env.order_count(b), (b, len(got), len(want))
-    for f in want.dtype.names:
-        assert np.array_equal(got[f], want[f]), (b, f)
-    kp, kt = env.order_keys(b)
-    wb, wp, wt = oracle_keys(oracle, view, len(want))
-    assert np.array_equal(np.where(wb == 1, bk.env.MAX_PRICE - kp.astype(np.uint64), kp), wp), b
-    assert np.array_equal(kt, wt), b
-    if len(want):
-        i = len(want) // 2
-        assert env.order_status(b, int(want["order_id"][i])) == int(want["status"][i])
-    if state:
-        assert env.book_state(b) == oracle_state(oracle, view), b
+def check_book(env, b, view, state=True):
+    P.same_book(env, b, view, orders=True, keys=True, state=state)
 
 
 _refs = {}
@@ -86,13 +61,13 @@ def test_agent_orders_match_the_oracle(bk, oracle, pool, mode):
     env.run(15)
     env.run(25)
     ref = ref_books(oracle, B, pool)
-    assert not env.flags().any()
-    assert np.array_equal(env.history(), ref.history())
+    P.no_flags(env)
+    P.same_history(env.history(), ref.history())
     assert np.array_equal(env.order_counts(), ref.order_counts())
     # book_state builds one dict per order: every book on the smaller pools, a spread of books on the larger ones
     full = set(range(B)) if pool <= 128 or mode == "split" else set(range(0, B, 37)) | {B - 1}
     for b in range(B):
-        check_book(bk, oracle, env, b, ref.book(b), state=b in full)
+        check_book(env, b, ref.book(b), state=b in full)
     env.close()
 
 
@@ -108,29 +83,12 @@ def test_market_agent_orders_match_the_oracle(bk, oracle):
     env.run(25)
     ref = oracle.ManyMarkets(NM, SEED, 0, ticks, STEP, True, LEVELS, groups)
     ref.run(n_steps, n_threads=8)
-    assert not env.flags().any()
-    assert np.array_equal(env.history(), ref.history())
+    P.no_flags(env)
+    P.same_history(env.history(), ref.history())
     for m in range(NM):
         for a in range(len(ticks)):
-            check_book(bk, oracle, env, env.book(m, a), ref.book(m, a), state=m % 7 == 0)
+            check_book(env, env.book(m, a), ref.book(m, a), state=m % 7 == 0)
     env.close()
-
-
-def outputs(env):
-    B = env.n_books
-    return {"history": env.history(), "counts": env.order_counts(), "trade_counts": env.trade_counts(),
-            "trades": [env.trades(b, first=0) for b in range(B)], "live": [env.live_orders(b) for b in range(B)],
-            "rng": [env.rng_state(b) for b in range(B)], "flags": env.flags()}
-
-
-def assert_same(x, y):
-    for k in x:
-        if isinstance(x[k], list):
-            assert len(x[k]) == len(y[k])
-            for i, (u, v) in enumerate(zip(x[k], y[k])):
-                assert (np.array_equal(u, v) if isinstance(u, np.ndarray) else u == v), (k, i)
-        else:
-            assert np.array_equal(x[k], y[k]), k
 
 
 @pytest.mark.parametrize("pool,mode", [(64, "auto"), (128, "split"), (256, "wave_split"), (512, "auto")])
@@ -142,9 +100,9 @@ def test_logging_changes_nothing_else(bk, pool, mode):
         env.set_pipeline(mode)
         env.run(17)
         env.run(23)
-        outs.append(outputs(env))
+        outs.append(P.snapshot(env))
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 def test_markets_logging_changes_nothing_else(bk):
@@ -157,9 +115,9 @@ def test_markets_logging_changes_nothing_else(bk):
         if log:
             env.enable_agent_order_log()
         env.run(30)
-        outs.append(outputs(env))
+        outs.append(P.snapshot(env))
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 def test_agent_orders_at_scale_on_the_lane_split(bk, oracle):
@@ -170,9 +128,9 @@ def test_agent_orders_at_scale_on_the_lane_split(bk, oracle):
     assert env.pipeline()[0] == "split"
     ref = oracle.ManyBooks(B, SEED, 0, 2, STEP, True, LEVELS, groups_for(pool))
     ref.run(n_steps, n_threads=8)
-    assert np.array_equal(env.history(), ref.history())
+    P.same_history(env.history(), ref.history())
     for b in range(B):
-        check_book(bk, oracle, env, b, ref.book(b), state=b % 97 == 0)
+        check_book(env, b, ref.book(b), state=b % 97 == 0)
     env.close()
 
 
@@ -295,9 +253,9 @@ def test_warm_leaves_the_log_alone(bk, mode):
         env.run(20)
         if warm:
             env.warm(9)
-        o = outputs(env)
+        o = P.snapshot(env)
         o["orders"] = [env.orders(b) for b in range(B)]
         o["keys"] = [np.concatenate([k.astype(np.uint64) for k in env.order_keys(b)]) for b in range(B)]
         outs.append(o)
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])

@@ -8,9 +8,10 @@ same order: level-2 history, trades, orders with their statuses, order keys and 
 import numpy as np
 import pytest
 
+import oracle_parity as P
+from ingress_support import MOD, SEED, STEP, apply_oracle, check, ingress_env, submit
+
 pytestmark = pytest.mark.gpu
-MOD = 0x80000003  # BK_ACTION_MODIFY
-SEED, STEP = 31, 100_000
 
 
 @pytest.fixture(scope="module")
@@ -18,53 +19,6 @@ def bk():
     import bourse_amd
 
     return bourse_amd
-
-
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _env(bk, torch, B, T, pool, n_agents, qcap, tick=2, n_ext=0, levels=10, strict=True, n_orders=None):
-    n_orders = n_orders or (2 * n_agents + n_ext) * T + 16
-    env = bk.ManyBookEnv(B, SEED, 0, tick, STEP, levels=levels, max_live_orders=pool, max_orders=n_orders,
-                         trade_capacity=2 * n_orders, history_capacity=T, strict=strict,
-                         stream=torch.cuda.current_stream().cuda_stream)
-    env.enable_device_ingress(queue_capacity=qcap)
-    return env
-
-
-def _oracle_keys(oracle, view, n):
-    import ctypes as C
-
-    kb, kp, kt = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
-    if n:
-        oracle.lib().orc_book_get_keys(view._b, 0, n, kb.ctypes.data_as(C.POINTER(C.c_uint8)), oracle._p32(kp),
-                                       oracle._p64(kt))
-    return kb[:n], kp[:n], kt[:n]
-
-
-def _check(bk, oracle, env, refs, books=None):
-    env.sync()
-    hist = env.history()
-    for b in (range(env.n_books) if books is None else books):
-        ref = refs[b]
-        assert np.array_equal(hist[:, b], ref.history()), b
-        got, want = env.trades(b, first=0), ref.book.trades_array()
-        assert len(got) == len(want), (b, len(got), len(want))
-        for f in want.dtype.names:
-            assert np.array_equal(got[f], want[f]), (b, f)
-        got, want = env.orders(b), ref.book.orders_array()
-        assert len(got) == len(want), (b, len(got), len(want))
-        for f in want.dtype.names:
-            assert np.array_equal(got[f], want[f]), (b, f)
-        kp, kt = env.order_keys(b)
-        wb, wp, wt = _oracle_keys(oracle, ref.book, len(want))
-        assert np.array_equal(np.where(wb == 1, bk.env.MAX_PRICE - kp.astype(np.uint64), kp), wp), b
-        assert np.array_equal(kt, wt), b
-        assert env.rng_state(b) == tuple(int(x) for x in ref.rng_state()), b
-        if len(want):
-            i = len(want) // 2
-            assert env.order_status(b, int(want["order_id"][i])) == int(want["status"][i]), b
 
 
 def _groups(pool):
@@ -78,7 +32,7 @@ def test_agents_only_equal_the_oracle(bk, oracle, pool):
     B, T = 64, 30
     groups = _groups(pool)
     na = sum(g[0] for g in groups)
-    env = _env(bk, torch, B, T, pool, na, na)
+    env = ingress_env(bk, torch, B, T, pool, na, na)
     env.set_random_agents(groups)
     refs = [oracle.StepEnv(SEED + b, 0, 2, STEP) for b in range(B)]
     agents = [oracle.RandomAgentSet(groups) for _ in range(B)]
@@ -88,8 +42,8 @@ def test_agents_only_equal_the_oracle(bk, oracle, pool):
         for r, a in zip(refs, agents):
             a.update(r)
             r.step()
-    assert not env.flags().any()
-    _check(bk, oracle, env, refs)
+    P.no_flags(env)
+    check(env, refs)
     assert int(env.trade_counts().sum()) > B * T
     env.close()
 
@@ -128,24 +82,6 @@ def _external(rng, refs, agents, n0, n_max, tick):
     return off, (action, side, vol, trader, price, order_id)
 
 
-def _apply_oracle(ref, lo, hi, ins):
-    action, side, vol, trader, price, order_id = ins
-    for i in range(lo, hi):
-        a = int(action[i])
-        if a == 1:
-            ref.place_order(bool(side[i] & 1), int(vol[i]), int(trader[i]), price=int(price[i]))
-        elif a == 2:
-            ref.cancel_order(int(order_id[i]))
-        elif a == MOD:
-            ref.modify_order(int(order_id[i]), new_price=int(price[i]) if side[i] & 2 else None,
-                             new_vol=int(vol[i]) if side[i] & 4 else None)
-
-
-def _submit(torch, env, off, ins):
-    if len(ins[0]):
-        env.submit_instructions_device(_dev(torch, off), *[_dev(torch, x) for x in ins])
-
-
 @pytest.mark.parametrize("agents_first", [True, False])
 def test_agents_with_external_instructions_equal_the_oracle(bk, oracle, agents_first):
     import torch
@@ -153,7 +89,7 @@ def test_agents_with_external_instructions_equal_the_oracle(bk, oracle, agents_f
     B, T, pool, NX = 64, 24, 256, 6
     groups = [(64, (32, 64), (10, 20), 2, 0.8), (32, (30, 66), (50, 70), 2, 0.3)]
     na = 96
-    env = _env(bk, torch, B, T, pool, na, na + NX, tick=1, n_ext=NX)
+    env = ingress_env(bk, torch, B, T, pool, na, na + NX, tick=1, n_ext=NX)
     env.set_random_agents(groups)
     refs = [oracle.StepEnv(SEED + b, 0, 1, STEP) for b in range(B)]
     agents = [oracle.RandomAgentSet(groups) for _ in range(B)]
@@ -166,9 +102,9 @@ def test_agents_with_external_instructions_equal_the_oracle(bk, oracle, agents_f
             for r, a in zip(refs, agents):
                 a.update(r)
         off, ins = _external(rng, refs, agents, n0, NX, 1)
-        _submit(torch, env, off, ins)
+        submit(torch, env, off, ins)
         for b, r in enumerate(refs):
-            _apply_oracle(r, int(off[b]), int(off[b + 1]), ins)
+            apply_oracle(r, int(off[b]), int(off[b + 1]), ins)
         if not agents_first:
             env.update_agents(sync=False)
             for r, a in zip(refs, agents):
@@ -178,8 +114,8 @@ def test_agents_with_external_instructions_equal_the_oracle(bk, oracle, agents_f
         for r in refs:
             r.step()
     assert hits > B * T // 2
-    assert not env.flags().any()
-    _check(bk, oracle, env, refs)
+    P.no_flags(env)
+    check(env, refs)
     env.close()
 
 
@@ -193,7 +129,7 @@ def test_two_updates_in_a_step_no_trading_step_and_a_per_book_table(bk, oracle):
              for lo, w, v, rate in zip(rng.integers(20, 40, B), rng.integers(5, 40, B), rng.integers(1, 30, B),
                                        rng.uniform(0.1, 0.95, B))]
     na = 64
-    env = _env(bk, torch, B, T, pool, 2 * na, 2 * na)
+    env = ingress_env(bk, torch, B, T, pool, 2 * na, 2 * na)
     env.set_random_agents_per_book(table)
     refs = [oracle.StepEnv(SEED + b, 0, 2, STEP) for b in range(B)]
     agents = [oracle.RandomAgentSet(table[b]) for b in range(B)]
@@ -213,8 +149,8 @@ def test_two_updates_in_a_step_no_trading_step_and_a_per_book_table(bk, oracle):
         env.step(sync=False)
         for r in refs:
             r.step()
-    assert not env.flags().any()
-    _check(bk, oracle, env, refs)
+    P.no_flags(env)
+    check(env, refs)
     env.close()
 
 
@@ -224,7 +160,7 @@ def test_replaced_agents_forget_their_orders(bk, oracle):
     B, T, pool = 64, 20, 256
     g1 = [(64, (32, 64), (10, 20), 2, 0.6)]
     g2 = [(40, (36, 60), (5, 15), 2, 0.9), (24, (30, 70), (20, 30), 2, 0.4)]
-    env = _env(bk, torch, B, T, pool, 64, 64)
+    env = ingress_env(bk, torch, B, T, pool, 64, 64)
     env.set_random_agents(g1)
     refs = [oracle.StepEnv(SEED + b, 0, 2, STEP) for b in range(B)]
     agents = [oracle.RandomAgentSet(g1) for _ in range(B)]
@@ -238,8 +174,8 @@ def test_replaced_agents_forget_their_orders(bk, oracle):
         env.step(sync=False)
         for r in refs:
             r.step()
-    assert not env.flags().any()
-    _check(bk, oracle, env, refs)
+    P.no_flags(env)
+    check(env, refs)
     env.close()
 
 
@@ -248,7 +184,7 @@ def test_update_agents_equals_bk_run_at_8192_books(bk, oracle):
 
     B, T, pool = 8192, 20, 128
     groups = [(64, (32, 64), (10, 20), 2, 0.8), (64, (32, 64), (50, 70), 2, 0.2)]
-    dev = _env(bk, torch, B, T, pool, 128, 128, levels=16, n_orders=64 * T)
+    dev = ingress_env(bk, torch, B, T, pool, 128, 128, levels=16, n_orders=64 * T)
     dev.set_random_agents(groups)
     run = bk.ManyBookEnv(B, SEED, 0, 2, STEP, levels=16, max_live_orders=pool, max_orders=64 * T,
                          trade_capacity=2 * 64 * T, history_capacity=T)
@@ -260,13 +196,11 @@ def test_update_agents_equals_bk_run_at_8192_books(bk, oracle):
     run.run(T)
     dev.sync()
     assert not dev.flags().any() and not run.flags().any()
-    assert np.array_equal(dev.history(), run.history())
+    P.same_history(dev.history(), run.history())
     assert np.array_equal(dev.trade_counts(), run.trade_counts())
     for b in sorted(set(range(0, B, 509)) | {B - 1}):
-        for got, want in ((dev.trades(b, first=0), run.trades(b, first=0)), (dev.orders(b), run.orders(b))):
-            assert len(got) == len(want), b
-            for f in want.dtype.names:
-                assert np.array_equal(got[f], want[f]), (b, f)
+        P.same_records(dev.trades(b, first=0), run.trades(b, first=0), (b,), "trade")
+        P.same_records(dev.orders(b), run.orders(b), (b,), "order")
         assert dev.rng_state(b) == run.rng_state(b), b
     dev.close()
     run.close()
@@ -288,7 +222,7 @@ def test_refusals_and_capacity_flags(bk, oracle):
     env.run(2)
     env.close()
     # no groups; then Noise members: refused, the queues still step; bk_run and checkpoints stay refused
-    env = _env(bk, torch, B, 4, 64, 32, 32)
+    env = ingress_env(bk, torch, B, 4, 64, 32, 32)
     with pytest.raises(bk.BourseError, match="no RandomAgents"):
         env.update_agents()
     env.set_agents([("noise", 0, 8, NOISE)])
@@ -308,8 +242,8 @@ def test_refusals_and_capacity_flags(bk, oracle):
         r.step()
         a.update(r)
         r.step()
-    assert not env.flags().any()
-    _check(bk, oracle, env, refs)
+    P.no_flags(env)
+    check(env, refs)
     env.close()
     # markets (assets > 1)
     env = bk.ManyBookEnv(2 * B, SEED, 0, 2, STEP, max_live_orders=64, assets=2,
@@ -322,7 +256,7 @@ def test_refusals_and_capacity_flags(bk, oracle):
     env.close()
     # a queue smaller than the agents' events: flagged, never silent; a strict env raises
     for strict in (True, False):
-        env = _env(bk, torch, B, 2, 64, 32, 8, strict=strict)
+        env = ingress_env(bk, torch, B, 2, 64, 32, 8, strict=strict)
         env.set_random_agents(groups)
         if strict:
             with pytest.raises(bk.CapacityError, match="EVENT_OVERFLOW"):

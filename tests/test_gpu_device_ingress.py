@@ -7,6 +7,8 @@ Checked three ways on the same random instruction stream: the device entry == th
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 U64MAX = 2**64 - 1
 
@@ -138,14 +140,8 @@ def test_device_ingress_equals_host_calls_and_oracle_on_8192_books(bk, oracle):
     assert [dev.order_count(b) for b in sample] == [int(counts[b]) for b in sample]
     for b in sample:
         assert np.array_equal(hd[:, b], refs[b].history()), b
-        gd, gh, e = dev.trades(b, first=0), host.trades(b, first=0), refs[b].book.trades_array()
-        od, oh, eo = dev.orders(b), host.orders(b), refs[b].book.orders_array()
-        for f in gd.dtype.names:
-            assert np.array_equal(gd[f], e[f]) and np.array_equal(gh[f], e[f]), (b, f)
-        for f in od.dtype.names:
-            assert np.array_equal(od[f], eo[f]) and np.array_equal(oh[f], eo[f]), (b, f)
-        kd, kh = dev.order_keys(b), host.order_keys(b)
-        assert np.array_equal(kd[0], kh[0]) and np.array_equal(kd[1], kh[1]), b
+        for name, e in (("device ingress", dev), ("host calls", host)):  # (the same keys as the oracle: as each other)
+            P.same_book(e, b, refs[b].book, orders=True, keys=True, tag=(name, b))
     # a second submit before the step appends (one submit per agent and step, ref src/bourse/step_sim/runner.py:108-112)
     off = np.arange(B + 1, dtype=np.int64) * 2
     one = lambda v, dt: _dev(torch, np.full(2 * B, v, dtype=dt))  # noqa: E731
@@ -237,12 +233,7 @@ def test_host_arrays_through_device_ingress_equal_host_calls_and_oracle_on_8192_
         assert np.array_equal(d.trade_counts(), host.trade_counts()), name
         for b in sample:
             assert np.array_equal(hd[:, b], refs[b].history()), (name, b)
-            gd, e = d.trades(b, first=0), refs[b].book.trades_array()
-            od, eo = d.orders(b), refs[b].book.orders_array()
-            for f in gd.dtype.names:
-                assert np.array_equal(gd[f], e[f]), (name, b, f)
-            for f in od.dtype.names:
-                assert np.array_equal(od[f], eo[f]), (name, b, f)
+            P.same_book(d, b, refs[b].book, orders=True, tag=(name, b))
     # an empty step (no element for any book) and a growing batch (the staging is re-allocated mid-flight)
     d = devs["tickets"]
     t0 = d.submit_instructions_all_async(np.zeros(B + 1, np.uint64), tuple(np.zeros(0, dt) for dt in (np.uint32, np.uint8, np.uint32, np.uint32, np.uint32, np.uint64)))
@@ -338,9 +329,7 @@ def test_run_many_numpy_agents_on_many_books_equals_one_oracle_env_per_book(bk, 
             r.step()
     for b, r in enumerate(refs):
         assert np.array_equal(hist[:, b], r.history()), b
-        got, exp = env.trades(b, first=0), r.book.trades_array()
-        for f in got.dtype.names:
-            assert np.array_equal(got[f], exp[f]), (b, f)
+        P.same_trades(env, b, r.book)
     assert int(env.trade_counts().sum()) > 1000
     # the books-vectorised agent: one update_many call per step, 8 192 books
     B2 = 8192
@@ -436,9 +425,7 @@ def test_device_ingress_markets_match_host_calls(bk):
     assert np.array_equal(dev.history(), host.history())
     assert np.array_equal(dev.trade_counts(), host.trade_counts()) and int(host.trade_counts().sum()) > 100
     for b in (0, 1, 7, B - 1):
-        gd, gh = dev.trades(b, first=0), host.trades(b, first=0)
-        for f in gd.dtype.names:
-            assert np.array_equal(gd[f], gh[f]), (b, f)
+        P.same_records(dev.trades(b, first=0), host.trades(b, first=0), (b,), "trade")
 
 
 class _BookView:
@@ -498,8 +485,7 @@ def test_two_envs_on_two_streams_equal_one_env(bk):
     assert np.array_equal(tc[:H], two[0].trade_counts()) and np.array_equal(tc[H:], two[1].trade_counts()) and int(tc.sum()) > 1000
     for b in (0, 77, H - 1):
         for p in (0, 1):
-            a, c = one.trades(p * H + b, first=0), two[p].trades(b, first=0)
-            assert all(np.array_equal(a[f], c[f]) for f in a.dtype.names)
+            P.same_records(one.trades(p * H + b, first=0), two[p].trades(b, first=0), (p, b), "trade")
     for e in [one] + two:
         e.close()
 
@@ -531,17 +517,14 @@ def test_the_rate_scripts_stream_at_full_size_runs_keyed_and_equals_the_oracle(b
             refs[b].submit_instructions_native(tuple(x[b * N:(b + 1) * N] for x in ins))
             refs[b].step()
     env.sync()
-    assert not env.flags().any()
+    P.no_flags(env)
     assert np.array_equal(env.event_steps_keyed(), np.full(B, T, dtype=np.uint64)), "a book-step of this stream left the keyed form"
     h = env.history()
     n_tr = 0
     for b in sample:
         assert np.array_equal(h[:, b], refs[b].history()), b
-        got, want = env.trades(b, first=0), refs[b].book.trades_array()
-        assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), b
-        got, want = env.orders(b), refs[b].book.orders_array()
-        assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), b
-        n_tr += len(want)
+        P.same_book(env, b, refs[b].book, orders=True)
+        n_tr += refs[b].book.n_orders()
     assert n_tr > 100 * len(sample)
     env.close()
 
@@ -593,10 +576,7 @@ def test_the_benchs_external_agents_stream_equals_one_oracle_env_per_book(bk, or
     h = env.history()
     for b, r in enumerate(refs):
         assert np.array_equal(h[:, b], r.history()), b
-        for got, want in ((env.trades(b, first=0), r.book.trades_array()), (env.orders(b), r.book.orders_array())):
-            assert len(got) == len(want), b
-            for f in got.dtype.names:
-                assert np.array_equal(got[f], want[f]), (b, f)
+        P.same_book(env, b, r.book, orders=True)
     keyed = env.event_steps_keyed()
     if pool <= 256:
         assert (keyed == T).all(), keyed[:16]

@@ -7,9 +7,9 @@ keyed-step counter of the host-driven steps."""
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 from kernel_cases import CASES, TICKS, market_members, members, random_groups, random_market_groups
-from test_gpu_agent_order_log import oracle_keys
-from test_gpu_value_range import _hist_equal, _no_flags, _same_book
 
 pytestmark = pytest.mark.gpu
 
@@ -90,14 +90,6 @@ def _launch_counts(env):
     return c
 
 
-def _check_log(bk, oracle, env, b, view):
-    kp, kt = env.order_keys(b)
-    n = len(view.orders_array())
-    wb, wp, wt = oracle_keys(oracle, view, n)
-    assert np.array_equal(np.where(wb == 1, bk.env.MAX_PRICE - kp.astype(np.uint64), kp), wp), (b, "key prices")
-    assert np.array_equal(kt, wt), (b, "key times")
-
-
 def _run_flow(bk, oracle, case):
     R, pool, U, mkt = case["R"], case["pool"], case["units"], case["markets"]
     A = len(TICKS) if mkt else 1
@@ -143,7 +135,7 @@ def _run_flow(bk, oracle, case):
         env.run(n)
         ref.run(n)
         assert _launch_counts(env) == _expected_launches(case, n, case["parts"]), (i, n)
-        _no_flags(env)
+        P.no_flags(env)
         tc, rngs = env.trade_counts(), ref.rngs()
         for b in range(NB):
             view = ref.view(b)
@@ -154,13 +146,11 @@ def _run_flow(bk, oracle, case):
             assert len(env.live_orders(b)) == live, (i, b)
             fill = max(fill, live)
     hist = env.history()
-    _hist_equal(hist, ref.history())
+    P.same_history(hist, ref.history())
     assert np.array_equal(env.level2(), hist[-1])
     for b in range(NB):
         view = ref.view(b)
-        _same_book(env, b, view, orders=case["log"], tag=(b,))
-        if case["log"]:
-            _check_log(bk, oracle, env, b, view)
+        P.same_book(env, b, view, orders=case["log"], keys=case["log"])
     assert int(env.trade_counts().sum()) > 0
     env.close()
     return fill
@@ -247,7 +237,7 @@ def _host_flow(bk, oracle, case):
             s += 1
         # a checked point
         assert _launch_counts(env) == [0, 0, 0, n_steps], i
-        _no_flags(env)
+        P.no_flags(env)
         for b in range(NB):
             live = _live(views[b])
             assert len(env.live_orders(b)) == live, (i, b)
@@ -264,10 +254,10 @@ def _host_flow(bk, oracle, case):
         assert first_mod == case["mods_from"] and max(longest[:first_mod]) <= 64 * R, (first_mod, longest)
     hist = env.history()
     if mkt:
-        _hist_equal(hist, ref.history())
+        P.same_history(hist, ref.history())
     else:
         for b, r in enumerate(refs):
-            _hist_equal(hist[:, b], r.history())
+            P.same_history(hist[:, b], r.history(), f"L2 history of book {b}")
     assert np.array_equal(env.level2(), hist[-1])
     tc = env.trade_counts()
     for b in range(NB):
@@ -276,8 +266,7 @@ def _host_flow(bk, oracle, case):
         assert env.rng_state(b) == want_rng, b
         assert env.time(b) == view.get_time(), b
         assert int(tc[b]) == len(view.trades_array()), b
-        _same_book(env, b, view, orders=True, tag=(b,))
-        _check_log(bk, oracle, env, b, view)
+        P.same_book(env, b, view, orders=True, keys=True)
     assert int(tc.sum()) > 0
     env.close()
     return fill
@@ -310,7 +299,7 @@ def _update_flow(bk, oracle, case):
                 r.step()
         env.sync()
         assert _launch_counts(env) == [0, 0, 0, n], i
-        _no_flags(env)
+        P.no_flags(env)
         for b in range(B):
             live = _live(refs[b].book)
             assert len(env.live_orders(b)) == live, (i, b)
@@ -318,11 +307,10 @@ def _update_flow(bk, oracle, case):
     assert na <= 64 * R  # (the queue's capacity is the longest queue: no chunks)
     hist = env.history()
     for b, r in enumerate(refs):
-        _hist_equal(hist[:, b], r.history())
+        P.same_history(hist[:, b], r.history(), f"L2 history of book {b}")
         assert env.rng_state(b) == tuple(int(x) for x in r.rng_state()), b
         assert env.time(b) == r.book.get_time(), b
-        _same_book(env, b, r.book, orders=True, tag=(b,))
-        _check_log(bk, oracle, env, b, r.book)
+        P.same_book(env, b, r.book, orders=True, keys=True)
     assert np.array_equal(env.level2(), hist[-1])
     assert int(env.trade_counts().sum()) > 0
     env.close()

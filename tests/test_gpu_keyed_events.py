@@ -13,6 +13,8 @@ orders already filled, market orders, orders filled on arrival, partial fills fo
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 
 
@@ -74,20 +76,14 @@ def _drive(bk, oracle, pool, n_max, B, T, seed, p_market, p_mod, p_zero, tick=1,
 def _same_as_oracle(env, refs, allow_flags=False):
     """(allow_flags - the fuzzer's crowded shapes: a book whose pool overflowed dropped an order and is not compared)"""
     flags = env.flags()
-    assert allow_flags or not flags.any(), np.unique(flags)
+    if not allow_flags:
+        P.no_flags(env)
     h = env.history()
     for b, ref in enumerate(refs):
         if flags[b]:
             continue
-        assert np.array_equal(h[:, b], ref.history()), ("level 2", b)
-        got, want = env.trades(b, first=0), ref.book.trades_array()
-        assert len(got) == len(want), ("trades", b, len(got), len(want))
-        for f in got.dtype.names:
-            assert np.array_equal(got[f], want[f]), ("trade", b, f)
-        got, want = env.orders(b), ref.book.orders_array()
-        assert len(got) == len(want), ("orders", b)
-        for f in got.dtype.names:
-            assert np.array_equal(got[f], want[f]), ("order", b, f, np.nonzero(got[f] != want[f])[0][:5])
+        P.same_history(h[:, b], ref.history(), f"L2 history of book {b}")
+        P.same_book(env, b, ref.book, orders=True)
 
 
 # The step's shuffle (env.rs:121) has two forms as well: draw by draw, and - queues of at least max(32, 12 x pool registers)
@@ -225,14 +221,11 @@ def test_markets_books_run_the_keyed_form_on_their_markets_queue(bk, oracle, ass
             clean[s, m] = ok
         env.step()
         ref.step()
-    assert np.array_equal(env.history(), ref.history())
+    P.same_history(env.history(), ref.history())
     for m in range(NM):
         for a in range(assets):
             b = env.book(m, a)
-            got, want = env.trades(b, first=0), ref.book(m, a).trades_array()
-            assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), (m, a)
-            got, want = env.orders(b), ref.book(m, a).orders_array()
-            assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), (m, a)
+            P.same_book(env, b, ref.book(m, a), orders=True, tag=(m, a))
     keyed = env.event_steps_keyed().reshape(NM, assets)
     assert np.all(keyed <= clean.sum(axis=0)) and keyed.sum() >= 0.9 * clean.sum(), (int(keyed.sum()), int(clean.sum()))
     env.close()
@@ -277,7 +270,7 @@ def test_modifications_on_the_keyed_loop_case_by_case(bk, oracle, pool):
             env.step()
             for r in refs:
                 r.step()
-        assert not env.flags().any()
+        P.no_flags(env)
         _same_as_oracle(env, refs)
         keyed = dict(zip(names, env.event_steps_keyed().tolist()))
         assert all(v == sum(1 for st in shifted[k] if st) for k, v in keyed.items()), keyed  # every step with events ran keyed
@@ -381,14 +374,11 @@ def test_512_slot_pools_switch_to_the_kernel_with_modifications_once_one_was_see
         for r in refs:
             r.step()
         keyed_after.append(int(env.event_steps_keyed().sum()))
-    assert not env.flags().any()
+    P.no_flags(env)
     h = env.history()
     for b, r in enumerate(refs):
         assert np.array_equal(h[:, b], r.history()), b
-        got, want = env.trades(b, first=0), r.book.trades_array()
-        assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), b
-        got, want = env.orders(b), r.book.orders_array()
-        assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), b
+        P.same_book(env, b, r.book, orders=True)
     per_step = np.diff([0] + keyed_after)
     assert list(per_step[:3]) == [B, B, B], per_step          # clean steps: keyed on the kernel without the modification code
     assert per_step[3] in (0, B) or per_step[3] < B, per_step   # the first step with modifications may still run on it: event by event
@@ -436,10 +426,7 @@ def test_markets_with_queues_longer_than_the_pool_and_modifications(bk, oracle, 
         for a in range(assets):
             b = env.book(int(m), a)
             assert np.array_equal(h[:, b], hr[:, b]), (m, a)
-            got, want = env.trades(b, first=0), ref.book(int(m), a).trades_array()
-            assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), (m, a)
-            got, want = env.orders(b), ref.book(int(m), a).orders_array()
-            assert len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in got.dtype.names), (m, a)
+            P.same_book(env, b, ref.book(int(m), a), orders=True, tag=(m, a))
     keyed = env.event_steps_keyed().reshape(NM, assets)
     assert keyed[ok_m].sum() >= 0.5 * T * assets * int(ok_m.sum()), (int(keyed[ok_m].sum()), T * assets * int(ok_m.sum()))
     env.close()

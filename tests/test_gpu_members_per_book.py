@@ -7,6 +7,8 @@ with parts, on markets, on a shard, with bk_warm and checkpoints, and refusals l
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 
 SEED, STEP, LEVELS, T, TICK = 101, 1_000_000, 10, 30, 2
@@ -77,23 +79,6 @@ def run_chunks(env, mode, chunks=(7, 1, 13, 9)):
         env.run(c)
 
 
-def outputs(env, books=None):
-    books = range(env.n_books) if books is None else books
-    return {"history": env.history(), "trade_counts": env.trade_counts(), "flags": env.flags(),
-            "trades": [env.trades(b, first=0) for b in books], "live": [env.live_orders(b) for b in books],
-            "rng": [env.rng_state(b) for b in books], "time": [env.time(b) for b in books]}
-
-
-def assert_same(x, y):
-    for k in x:
-        if isinstance(x[k], list):
-            assert len(x[k]) == len(y[k]), k
-            for i, (u, v) in enumerate(zip(x[k], y[k])):
-                assert (np.array_equal(u, v) if isinstance(u, np.ndarray) else u == v), (k, i)
-        else:
-            assert np.array_equal(x[k], y[k]), k
-
-
 _oracle = {}
 
 
@@ -102,11 +87,8 @@ def oracle_book(oracle, b, row, steps=T, seed=SEED):
     if key not in _oracle:
         ref = oracle.ManyBooks(1, seed + b, 0, TICK, STEP, True, LEVELS, members=row)
         ref.run(steps)
-        o = ref.book(0).orders_array()
-        act = o[o["status"] == 1]
         _oracle[key] = (ref.history()[:, 0], int(ref.trade_counts()[0]), tuple(int(x) for x in ref.rng_states()[0]),
-                        ref.book(0).get_time(), ref.book(0).trades_array(),
-                        set(zip(act["order_id"].tolist(), act["price"].tolist(), act["vol"].tolist(), act["side"].tolist())))
+                        ref.book(0).get_time(), ref)
     return _oracle[key]
 
 
@@ -117,17 +99,13 @@ def check_against_oracle(bk, oracle, env, rows, sample, clamp_book=None):
         want_flags[clamp_book] = bk._lib.FLAG_PRICE_TICK
     assert np.array_equal(flags, want_flags), np.flatnonzero(flags)[:8]
     for b, row in enumerate(rows):
-        h, n, rng, t, trades, live = oracle_book(oracle, b, row)
+        h, n, rng, t, ref = oracle_book(oracle, b, row)
         assert np.array_equal(hist[:, b], h), b
         assert int(tc[b]) == n, b
         assert env.rng_state(b) == rng, b
         assert env.time(b) == t, b
         if b in sample:
-            got = env.trades(b, first=0)
-            for f in ("t", "side", "price", "vol", "active_id", "passive_id"):
-                assert np.array_equal(got[f], trades[f]), (b, f)
-            lv = env.live_orders(b)
-            assert set(zip(lv["order_id"].tolist(), lv["price"].tolist(), lv["vol"].tolist(), lv["side"].tolist())) == live, b
+            P.same_book(env, b, ref.book(0))
 
 
 # ------------------------------------------------------------------ 1. identity with the uniform call
@@ -146,10 +124,10 @@ def test_identical_rows_equal_the_uniform_agents(bk, pool, mode):
         else:
             env.set_agents(members)
         run_chunks(env, mode)
-        outs.append(outputs(env))
+        outs.append(P.snapshot(env))
         env.close()
     assert int(outs[0]["trade_counts"].sum()) > 0
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 # ------------------------------------------------------------------ 2. heterogeneous rows against the oracle
@@ -179,7 +157,7 @@ def blocks_env(bk, B, n_blocks, pool=128):
 
 def check_blocks(oracle, env, base, per, steps, blocks):
     hist, tc = env.history(), env.trade_counts()
-    assert not env.flags().any()
+    P.no_flags(env)
     for k in blocks:
         b0 = k * per
         n = 256  # (the first 256 books of the block)
@@ -229,7 +207,7 @@ def test_markets_with_rows_per_market(bk, oracle, ticks):
     env.run(11)
     env.run(T - 11)
     hist = env.history()
-    assert not env.flags().any()
+    P.no_flags(env)
     for m in range(NM):
         ref = oracle.ManyMarkets(1, SEED + m, 0, ticks, STEP, True, LEVELS, members=rows[m])
         ref.run(T)
@@ -269,9 +247,9 @@ def test_warm_changes_nothing(bk, mode):
         if warm:
             env.warm(7)
         env.run(T)
-        outs.append(outputs(env, books=range(0, B, 17)))
+        outs.append(P.snapshot(env, books=range(0, B, 17)))
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 def test_checkpoint_continues_and_refuses_another_table(bk):
@@ -325,7 +303,7 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
     ref = make_env(bk, B, 256)
     ref.set_agents_per_book(rows)
     ref.run(T)
-    want = outputs(ref, books=range(0, B, 11))
+    want = P.snapshot(ref, books=range(0, B, 11))
     ref.close()
     env = make_env(bk, B, 256)
     env.set_agents_per_book(rows)
@@ -335,7 +313,7 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
         assert getattr(ei.value, "code", _lib.BK_PRICE) == code and isinstance(ei.value, bk.BourseError) == (code != _lib.BK_PRICE), msg
         assert msg in str(ei.value), str(ei.value)
     env.run(T)
-    assert_same(want, outputs(env, books=range(0, B, 11)))
+    P.assert_same(want, P.snapshot(env, books=range(0, B, 11)))
     env.close()
     # a logging env refuses the table as set_agents refuses such members
     lg = bk.ManyBookEnv(B, SEED, 0, TICK, STEP, True, levels=LEVELS, max_live_orders=256, max_orders=256 * T,
@@ -353,9 +331,9 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
             e.set_agents_per_book(rows)
         e.set_agents(rows[5])
         e.run(T)
-        outs.append(outputs(e, books=range(0, B, 13)))
+        outs.append(P.snapshot(e, books=range(0, B, 13)))
         e.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 def test_an_all_random_table_is_the_random_table(bk):
@@ -370,6 +348,6 @@ def test_an_all_random_table_is_the_random_table(bk):
         else:
             env.set_random_agents_per_book([[m[1:] for m in row] for row in rows])
         env.run(T)
-        outs.append(outputs(env, books=range(0, B, 7)))
+        outs.append(P.snapshot(env, books=range(0, B, 7)))
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from members_ingress_cases import CASES, MOM, NOISE, member_set
-from test_gpu_agents_with_ingress import MOD, SEED, STEP, _apply_oracle, _check, _env, _submit
+from ingress_support import MOD, SEED, STEP, apply_oracle, check, ingress_env, submit
 
 pytestmark = pytest.mark.gpu
 U64_MAX = 0xFFFFFFFFFFFFFFFF
@@ -100,9 +100,9 @@ class Run:
 
     def submit(self, off, ins):
         if self.env is not None:
-            _submit(self.torch, self.env, off, ins)
+            submit(self.torch, self.env, off, ins)
         for b, r in enumerate(self.refs):
-            _apply_oracle(r, int(off[b]), int(off[b + 1]), ins)
+            apply_oracle(r, int(off[b]), int(off[b + 1]), ins)
 
     def trading(self, on):
         if self.env is not None:
@@ -129,8 +129,8 @@ class Run:
         trades = sum(r.book.n_trades() for r in self.refs)
         assert trades > self.B * self.steps, (trades, self.B * self.steps)
 
-    def check(self, bk, books=None):
-        _check(bk, self.oracle, self.env, self.refs, books)
+    def check(self, books=None):
+        check(self.env, self.refs, books)
         for b in (range(self.B) if books is None else books):
             for j in range(len(self.sets[b].members)):
                 got, want = self.env.member_orders(b, j), _member_ids(self.oracle, self.sets[b], j)
@@ -195,8 +195,8 @@ def _make_env(bk, torch, B, T, pool, members, tick, n_ext=0, updates=1, strict=T
     """an env whose queue takes `updates` updates of the set (every agent's orders, and a cancellation for every order
     that can rest) and n_ext instructions per step, and whose order log takes the run's orders"""
     per_update = sum(m[1] if m[0] == "random" else 2 * m[2] for m in members)
-    return _env(bk, torch, B, T, pool, 0, (per_update + pool) * updates + n_ext, tick=tick, strict=strict,
-                n_orders=(per_update * updates + n_ext) * T + 16)
+    return ingress_env(bk, torch, B, T, pool, 0, (per_update + pool) * updates + n_ext, tick=tick, strict=strict,
+                       n_orders=(per_update * updates + n_ext) * T + 16)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the sets, every pool
@@ -232,7 +232,7 @@ def test_members_equal_the_oracle(bk, oracle, name, which):
     if which.startswith("mixed") and case["R"] >= 2:  # a bug confined to the pool's upper registers cannot pass unseen
         assert run.max_live > 64 * (case["R"] - 1), run.max_live
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     env.close()
 
 
@@ -270,7 +270,7 @@ def test_members_with_external_instructions_equal_the_oracle(bk, oracle, name, w
     run.assert_busy()
     assert targets > case["books"] * case["steps"] // 2 and 3 * listed >= targets, (targets, listed)
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     env.close()
 
 
@@ -298,7 +298,7 @@ def test_update_then_submit_submit_then_update_and_two_updates_in_a_step(bk, ora
         run.step()
     run.assert_busy(momentum_signs=False)
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     env.close()
 
 
@@ -336,7 +336,7 @@ def test_a_per_book_table_equals_the_uniform_set_of_each_row(bk, oracle):
             e.step(sync=False)
     run.assert_busy(momentum_signs=False)
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     hist = env.history()
     for b0, e in zip(uni_books, unis):
         e.sync()
@@ -355,7 +355,7 @@ def test_a_short_queue_and_an_off_tick_price_are_flagged(bk, oracle):
     B = 16
     members = [("noise", 0, 32, dict(NOISE, p_limit=1.0, p_market=1.0))]  # 64 events per update
     for strict in (True, False):
-        env = _env(bk, torch, B, 2, 128, 0, 8, strict=strict, n_orders=256)
+        env = ingress_env(bk, torch, B, 2, 128, 0, 8, strict=strict, n_orders=256)
         env.set_agents(members)
         if strict:
             with pytest.raises(bk.CapacityError, match="EVENT_OVERFLOW"):
@@ -372,7 +372,7 @@ def test_a_short_queue_and_an_off_tick_price_are_flagged(bk, oracle):
     # nothing created); the oracle creates nothing either, and everything else stays equal
     far = [("noise", 0, 16, dict(NOISE, p_limit=1.0, price_dist_mu=25.0, price_dist_sigma=0.0))]
     T = 6
-    env = _env(bk, torch, B, T, 128, 0, 64, strict=False, n_orders=64 * T)
+    env = ingress_env(bk, torch, B, T, 128, 0, 64, strict=False, n_orders=64 * T)
     env.set_agents(far)
     run = Run(oracle, lambda b: far, B, 2, env, torch)
     for _ in range(T):
@@ -385,7 +385,7 @@ def test_a_short_queue_and_an_off_tick_price_are_flagged(bk, oracle):
         o = r.book.orders_array()
         assert not ((o["side"] == 0) & (o["price"] != 0)).any(), b  # no sell limit order exists
         assert env.order_count(b) == len(o), b
-    run.check(bk)
+    run.check()
     env.close()
 
 
@@ -403,7 +403,7 @@ def test_refusals_leave_the_env_stepping(bk, oracle):
     env.run(2)
     env.close()
     # no AgentSet; RandomAgents groups only (bk_update_agents'); then members: bk_update_agents keeps its refusal
-    env = _env(bk, torch, B, 4, 64, 0, 64, n_orders=256)
+    env = ingress_env(bk, torch, B, 4, 64, 0, 64, n_orders=256)
     with pytest.raises(bk.BourseError, match="no AgentSet"):
         env.update_members()
     with pytest.raises(bk.BourseError, match="bk_member_orders"):
@@ -433,7 +433,7 @@ def test_refusals_leave_the_env_stepping(bk, oracle):
     run.step()
     run.env = env
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     env.close()
     # markets (assets > 1)
     env = bk.ManyBookEnv(2 * B, SEED, 0, 2, STEP, max_live_orders=64, assets=2,
@@ -452,7 +452,7 @@ def test_one_install_replaces_the_other(bk, oracle):
     import torch
 
     B = 8
-    env = _env(bk, torch, B, 8, 128, 0, 64, n_orders=512)
+    env = ingress_env(bk, torch, B, 8, 128, 0, 64, n_orders=512)
     groups, members = [(16, (32, 64), (10, 20), 2, 0.9)], [("random", 8, (32, 64), (10, 20), 2, 0.9), ("noise", 8, 8, NOISE)]
     for _ in range(2):
         env.set_random_agents(groups)
@@ -498,5 +498,5 @@ def test_reinstalled_members_forget_their_orders_and_their_momentum(bk, oracle):
         run.step()
     run.assert_busy(momentum_signs=False)
     assert not env.flags().any()
-    run.check(bk)
+    run.check()
     env.close()

@@ -5,6 +5,8 @@ shard, with the order log, bk_warm and checkpoints, and the refusals leave the i
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 
 SEED, STEP, LEVELS, T = 101, 100_000, 10, 30
@@ -49,23 +51,6 @@ def make_env(bk, B, pool, steps=T, **kw):
                           history_capacity=steps, **kw)
 
 
-def outputs(env, books=None):
-    books = range(env.n_books) if books is None else books
-    return {"history": env.history(), "trade_counts": env.trade_counts(), "flags": env.flags(),
-            "trades": [env.trades(b, first=0) for b in books], "live": [env.live_orders(b) for b in books],
-            "rng": [env.rng_state(b) for b in books], "time": [env.time(b) for b in books]}
-
-
-def assert_same(x, y):
-    for k in x:
-        if isinstance(x[k], list):
-            assert len(x[k]) == len(y[k]), k
-            for i, (u, v) in enumerate(zip(x[k], y[k])):
-                assert (np.array_equal(u, v) if isinstance(u, np.ndarray) else u == v), (k, i)
-        else:
-            assert np.array_equal(x[k], y[k]), k
-
-
 def run_split(env, mode):
     env.set_pipeline(mode)
     env.run(13)
@@ -81,23 +66,21 @@ def oracle_book(oracle, b, row, steps=T, seed=SEED):
         ref = oracle.ManyBooks(1, seed + b, 0, 2, STEP, True, LEVELS, row)
         ref.run(steps)
         _oracle[key] = (ref.history()[:, 0], int(ref.trade_counts()[0]), tuple(int(x) for x in ref.rng_states()[0]),
-                        ref.book(0).get_time(), ref.book(0).trades_array(), ref)
+                        ref.book(0).get_time(), ref)
     return _oracle[key]
 
 
 def check_against_oracle(oracle, env, rows, sample):
-    hist, tc, flags = env.history(), env.trade_counts(), env.flags()
-    assert not flags.any(), np.flatnonzero(flags)[:8]
+    hist, tc = env.history(), env.trade_counts()
+    P.no_flags(env)
     for b, row in enumerate(rows):
-        h, n, rng, t, trades, _ = oracle_book(oracle, b, row)
+        h, n, rng, t, ref = oracle_book(oracle, b, row)
         assert np.array_equal(hist[:, b], h), b
         assert int(tc[b]) == n, b
         assert env.rng_state(b) == rng, b
         assert env.time(b) == t, b
         if b in sample:
-            got = env.trades(b, first=0)
-            for f in ("t", "side", "price", "vol", "active_id", "passive_id"):
-                assert np.array_equal(got[f], trades[f]), (b, f)
+            P.same_book(env, b, ref.book(0))
 
 
 # ------------------------------------------------------------------ 1. identity with the uniform call
@@ -118,11 +101,11 @@ def test_identical_rows_equal_the_uniform_agents(bk, pool, mode):
         else:
             env.set_random_agents(rows[0])
         run_split(env, mode)
-        outs.append(outputs(env))
+        outs.append(P.snapshot(env))
         if per_book and mode == "fused":
             assert env.pipeline()[0] == "split"  # (k_run_random has no per-book form)
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 # ------------------------------------------------------------------ 2. heterogeneous rows against the oracle
@@ -157,7 +140,7 @@ def blocks_env(bk, B, pool, n_blocks):
 
 def check_blocks(oracle, env, base, per, steps):
     hist, tc = env.history(), env.trade_counts()
-    assert not env.flags().any()
+    P.no_flags(env)
     for k, row in enumerate(base):
         b0 = k * per
         ref = oracle.ManyBooks(per, SEED + b0, 0, 2, STEP, True, LEVELS, row)
@@ -207,7 +190,7 @@ def test_markets_with_rows_per_market(bk, oracle, ticks):
     env.run(11)
     env.run(T - 11)
     hist = env.history()
-    assert not env.flags().any()
+    P.no_flags(env)
     for m in range(NM):
         ref = oracle.ManyMarkets(1, SEED + m, 0, ticks, STEP, True, LEVELS, rows[m])
         ref.run(T)
@@ -244,11 +227,7 @@ def test_order_log_with_a_table(bk, oracle, mode):
     env.enable_agent_order_log()
     run_split(env, mode)
     for b in (0, 9, 130, B - 1):
-        ref = oracle_book(oracle, b, rows[b])[-1]
-        got, want = env.orders(b), ref.book(0).orders_array()
-        assert len(got) == len(want), b
-        for f in want.dtype.names:
-            assert np.array_equal(got[f], want[f]), (b, f)
+        P.same_orders(env, b, oracle_book(oracle, b, rows[b])[-1].book(0))
     env.close()
 
 
@@ -264,9 +243,9 @@ def test_warm_changes_nothing(bk, pool, mode):
         if warm:
             env.warm(7)
         env.run(T)
-        outs.append(outputs(env, books=range(0, B, 17)))
+        outs.append(P.snapshot(env, books=range(0, B, 17)))
         env.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])
 
 
 def test_checkpoint_continues_and_refuses_another_table(bk):
@@ -323,7 +302,7 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
     ref = make_env(bk, B, pool)
     ref.set_random_agents_per_book(rows)
     ref.run(T)
-    want = outputs(ref, books=range(0, B, 11))
+    want = P.snapshot(ref, books=range(0, B, 11))
     ref.close()
     env = make_env(bk, B, pool, strict=False)
     env.set_random_agents_per_book(rows)
@@ -333,7 +312,7 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
         assert getattr(ei.value, "code", _lib.BK_PRICE) == code and isinstance(ei.value, bk.BourseError) == (code != _lib.BK_PRICE), msg
         assert msg in str(ei.value), str(ei.value)
     env.run(T)
-    assert_same(want, outputs(env, books=range(0, B, 11)))
+    P.assert_same(want, P.snapshot(env, books=range(0, B, 11)))
     env.close()
     # a later set_random_agents replaces the table: the env is uniform again
     outs = []
@@ -345,6 +324,6 @@ def test_refusals_keep_the_installed_agents_and_a_uniform_call_replaces_the_tabl
         e.set_pipeline("fused")
         e.run(T)
         assert e.pipeline()[0] == "fused"
-        outs.append(outputs(e, books=range(0, B, 13)))
+        outs.append(P.snapshot(e, books=range(0, B, 13)))
         e.close()
-    assert_same(outs[0], outs[1])
+    P.assert_same(outs[0], outs[1])

@@ -9,6 +9,8 @@ apply the reference's rule (orderbook.rs:229-264).
 import numpy as np
 import pytest
 
+import oracle_parity as P
+
 pytestmark = pytest.mark.gpu
 
 U32 = 2**32
@@ -58,31 +60,6 @@ def _l2_rule(orders, levels, tick):
     return out.astype(np.uint32)
 
 
-def _no_flags(env):
-    f = env.flags()
-    assert not f.any(), np.unique(f)
-
-
-def _hist_equal(hist, want):
-    assert hist.shape == want.shape, (hist.shape, want.shape)
-    if not np.array_equal(hist, want):
-        bad = np.argwhere(hist != want)[0]
-        raise AssertionError(f"L2 history differs first at {tuple(bad)}: {hist[tuple(bad)]} vs {want[tuple(bad)]}")
-
-
-def _oracle_key_times(view, n):
-    """The time of every order's priority key in an oracle book (orderbook.rs:34-39), by order id."""
-    import ctypes as C
-
-    import pyoracle
-
-    kb, kp, kt = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
-    if n:
-        pyoracle.lib().orc_book_get_keys(view._b, 0, n, kb.ctypes.data_as(C.POINTER(C.c_uint8)), pyoracle._p32(kp),
-                                         pyoracle._p64(kt))
-    return kt[:n]
-
-
 def _carried_in_step0(views, start, step):
     """When the first step straddles 2^32: some order or trade of these books was stamped in step 0 at or above 2^32."""
     if not start < U32 < start + step:
@@ -93,34 +70,6 @@ def _carried_in_step0(views, start, step):
         hits += int(((o["arr_time"] >= U32) & (o["arr_time"] < start + step)).sum())
         hits += int(((t["t"] >= U32) & (t["t"] < start + step)).sum())
     assert hits > 0, "no event of step 0 was stamped past 2^32"
-
-
-def _same_book(env, b, view, orders=False, tag=None):
-    """Trades, live orders (set and priority order) and optionally the order log of device book b vs an oracle view."""
-    tag = (b,) if tag is None else tag
-    got, exp = env.trades(b, first=0), view.trades_array()
-    assert len(got) == len(exp), (tag, len(got), len(exp))
-    for f in ("t", "side", "price", "vol", "active_id", "passive_id"):
-        assert np.array_equal(got[f], exp[f]), (tag, "trade", f)
-    o = view.orders_array()
-    act = o[o["status"] == 1]
-    live = env.live_orders(b)
-    assert len(live) == len(act), (tag, len(live), len(act))
-    assert set(zip(live["order_id"].tolist(), live["price"].tolist(), live["vol"].tolist(), live["side"].tolist())) == \
-        set(zip(act["order_id"].tolist(), act["price"].tolist(), act["vol"].tolist(), act["side"].tolist())), tag
-    key_t = _oracle_key_times(view, len(o))
-    for side in (1, 0):
-        ids = [int(r["order_id"]) for r in live if r["side"] == side]
-        # price-time priority: bids by price desc, asks by price asc, then the key's time (arrival, or the modification
-        # that re-keyed the order: the oracle's key)
-        want = sorted(ids, key=lambda i: (-int(o["price"][i]) if side else int(o["price"][i]), int(key_t[i]), i))
-        assert ids == want, (tag, side, "priority order")
-    if orders:
-        go = env.orders(b)
-        assert len(go) == len(o), (tag, "orders")
-        for f in o.dtype.names:
-            assert np.array_equal(go[f], o[f]), (tag, "order", f)
-    return o
 
 
 # ------------------------------------------------------------------------------------- on-device agents (bk_run)
@@ -144,16 +93,16 @@ def _run_agents(bk, oracle, B, T, *, start=0, step=100_000, tick=2, levels=10, g
         env.run(c)
     ref = oracle.ManyBooks(B, SEED, start, tick, step, True, levels, groups, members=members)
     ref.run(T, n_threads=4)
-    _no_flags(env)
+    P.no_flags(env)
     hist = env.history()
-    _hist_equal(hist, ref.history())
+    P.same_history(hist, ref.history())
     assert np.array_equal(env.level2(), hist[-1])
     assert np.array_equal(env.trade_counts(), ref.trade_counts())
     want_rng = ref.rng_states()
     for b in range(B):
         assert env.rng_state(b) == (int(want_rng[b, 0]), int(want_rng[b, 1])), b
         assert env.time(b) == start + T * step, b
-        _same_book(env, b, ref.book(b), orders=log)
+        P.same_book(env, b, ref.book(b), orders=log)
         if check_rule:
             assert np.array_equal(hist[-1, b, 1:], _l2_rule(ref.book(b).orders_array(), levels, tick)), b
     assert int(ref.trade_counts().sum()) > 0
@@ -221,15 +170,15 @@ def test_random_market_agents_at_64_bit_times(bk, oracle, times):
     env.run(T)
     ref = oracle.ManyMarkets(NM, SEED, start, ticks, step, True, 10, groups)
     ref.run(T, n_threads=4)
-    _no_flags(env)
-    _hist_equal(env.history(), ref.history())
+    P.no_flags(env)
+    P.same_history(env.history(), ref.history())
     want_rng = ref.rng_states()
     for m in range(NM):
         for a in range(2):
             b = env.book(m, a)
             assert env.rng_state(b) == (int(want_rng[m, 0]), int(want_rng[m, 1]))
             assert env.time(b) == start + T * step
-            _same_book(env, b, ref.book(m, a), tag=(m, a))
+            P.same_book(env, b, ref.book(m, a), tag=(m, a))
     _carried_in_step0([ref.book(m, a) for m in range(NM) for a in range(2)], start, step)
     env.close()
 
@@ -273,11 +222,11 @@ def _apply(env, refs, b, ops):
 
 
 def _check_host(env, refs, start=None, step=None, T=None, rule=None):
-    _no_flags(env)
+    P.no_flags(env)
     h = env.history()
     for b, r in enumerate(refs):
-        _hist_equal(h[:, b], r.history())
-        _same_book(env, b, r.book, orders=True)
+        P.same_history(h[:, b], r.history(), f"L2 history of book {b}")
+        P.same_book(env, b, r.book, orders=True)
         if start is not None:
             assert env.time(b) == start + T * step, b
         if rule is not None:
@@ -674,12 +623,12 @@ def test_market_with_a_huge_tick_asset_beside_a_tick_1_asset(bk, oracle, huge):
     env.run(T)
     ref = oracle.ManyMarkets(NM, SEED, 0, [huge, 1], 1000, True, L, groups)
     ref.run(T, n_threads=4)
-    assert not env.flags().any()
+    P.no_flags(env)
     h = env.history()
-    _hist_equal(h, ref.history())
+    P.same_history(h, ref.history())
     for m in range(NM):
         for a, tick in enumerate((huge, 1)):
-            _same_book(env, env.book(m, a), ref.book(m, a), tag=(m, a))
+            P.same_book(env, env.book(m, a), ref.book(m, a), tag=(m, a))
             assert np.array_equal(h[-1, env.book(m, a), 1:], _l2_rule(ref.book(m, a).orders_array(), L, tick)), (m, a)
     env.close()
 
@@ -762,7 +711,7 @@ def test_stats_grid_stride_over_300_000_books(bk):
     env = bk.ManyBookEnv(B, 7, 0, 2, 1000, levels=1, max_live_orders=64, trade_capacity=16, history_capacity=0)
     env.set_random_agents([(1, (40, 60), (U32 - 9, MAXP), 2, 0.9)])
     env.run(T)
-    assert not env.flags().any()
+    P.no_flags(env)
     st = env.stats()
     l2 = env.level2().astype(np.uint64)
     assert st["n_books"] == B
