@@ -19,7 +19,9 @@ import numpy as np
 import pytest
 
 from members_ingress_cases import CASES, MOM, NOISE, member_set
-from ingress_support import MOD, SEED, STEP, apply_oracle, check, ingress_env, submit
+from ingress_support import (MOD, SEED, STEP, WIDE_STEPS, BusyCounts, apply_oracle, check, ingress_env, submit, thin_flow,
+                             wide_flow, wide_set, wide_trading)
+from ingress_support import members_env as _make_env
 
 pytestmark = pytest.mark.gpu
 U64_MAX = 0xFFFFFFFFFFFFFFFF
@@ -55,42 +57,18 @@ class Run:
     def new_sets(self, members_of):
         """fresh agents (NoiseAgent::new ...) on the running envs"""
         self.sets = [self.oracle.AgentSet(members_of(b)) for b in range(self.B)]
-        nm = len(self.sets[0].members)
-        self.traded = [j for j in range(nm) if self.sets[0].members[j][0] != "random"]
-        self.count = {j: dict(cancel=0, limit=0, market=0, dropped=0, m_pos=0, m_neg=0) for j in self.traded}
-        self.mom = {}  # (book, member) -> (momentum, last mid)
+        self.traded = [j for j, m in enumerate(self.sets[0].members) if m[0] != "random"]
+        self.busy = BusyCounts(self.sets[0].members)
 
     def _update_oracle(self, b):
         ref, aset = self.refs[b], self.sets[b]
         before = ref.book.orders_array()
-        status = before["status"]
         n0 = len(before)
         lists0 = {j: aset.order_list(j) for j in self.traded}
         mid = ref.book.mid_price()
         aset.update(ref)
-        created = ref.book.orders_array()[n0:]
-        for j in self.traded:
-            kind, start, n, p = aset.members[j]
-            c = self.count[j]
-            kept = set(int(i) for i in aset.order_list(j))
-            for i in lists0[j]:
-                if status[int(i)] != 1:
-                    c["dropped"] += 1  # not Status::Active: no draw, gone from the list
-                elif int(i) not in kept:
-                    c["cancel"] += 1   # Active and not kept: its cancellation was queued
-            mine = created[(created["trader_id"] >= start) & (created["trader_id"] < start + n)]
-            market = ((mine["side"] == 1) & (mine["price"] == 0xFFFFFFFF)) | ((mine["side"] == 0) & (mine["price"] == 0))
-            # (the sets of one run use disjoint trader id ranges above the RandomAgents members' indices)
-            c["market"] += int(market.sum())
-            c["limit"] += int(sum(1 for i in kept if i >= n0))
-            if kind == "momentum":
-                m = 0.0
-                if (b, j) in self.mom:
-                    m0, last = self.mom[(b, j)]
-                    m = m0 * (1.0 - p["decay"]) + p["decay"] * (mid - last)
-                c["m_pos"] += m > 0.0
-                c["m_neg"] += m < 0.0
-                self.mom[(b, j)] = (m, mid)
+        self.busy.note(b, aset.members, before["status"], n0, lists0, {j: aset.order_list(j) for j in self.traded},
+                       ref.book.orders_array()[n0:], mid)
 
     def update(self):
         if self.env is not None:
@@ -120,12 +98,7 @@ class Run:
 
     def assert_busy(self, momentum_signs=True):
         """the condition on the oracle side, before any comparison"""
-        for j in self.traded:
-            c = self.count[j]
-            for k in ("cancel", "limit", "market", "dropped"):
-                assert c[k] > 0, (j, k, c)
-            if self.sets[0].members[j][0] == "momentum" and momentum_signs:
-                assert c["m_pos"] > 0 and c["m_neg"] > 0, (j, c)
+        self.busy.assert_busy(momentum_signs)
         trades = sum(r.book.n_trades() for r in self.refs)
         assert trades > self.B * self.steps, (trades, self.B * self.steps)
 
@@ -135,21 +108,6 @@ class Run:
             for j in range(len(self.sets[b].members)):
                 got, want = self.env.member_orders(b, j), _member_ids(self.oracle, self.sets[b], j)
                 assert np.array_equal(got, want), (b, j, got, want)
-
-
-def _thin_flow(rng, B, n_max, tick):
-    """new orders only: a few limit orders in a band of prices and now and then a market order, for every book"""
-    n_b = rng.integers(0, n_max + 1, size=B)
-    off = np.zeros(B + 1, dtype=np.int64)
-    off[1:] = np.cumsum(n_b)
-    n = int(off[-1])
-    bid = rng.integers(0, 2, size=n).astype(np.uint8)
-    price = (rng.integers(40, 60, size=n) * tick).astype(np.uint32)
-    if tick == 1:
-        market = rng.random(n) < 0.1
-        price[market] = np.where(bid[market] == 1, 0xFFFFFFFF, 0)
-    return off, (np.ones(n, np.uint32), bid, rng.integers(20, 200, size=n).astype(np.uint32),
-                 rng.integers(5000, 6000, size=n).astype(np.uint32), price, np.zeros(n, np.uint64))
 
 
 def _external(rng, run, n0, n_max, tick):
@@ -191,14 +149,6 @@ def _external(rng, run, n0, n_max, tick):
     return off, (action, side, vol, trader, price, order_id), targets, listed
 
 
-def _make_env(bk, torch, B, T, pool, members, tick, n_ext=0, updates=1, strict=True):
-    """an env whose queue takes `updates` updates of the set (every agent's orders, and a cancellation for every order
-    that can rest) and n_ext instructions per step, and whose order log takes the run's orders"""
-    per_update = sum(m[1] if m[0] == "random" else 2 * m[2] for m in members)
-    return ingress_env(bk, torch, B, T, pool, 0, (per_update + pool) * updates + n_ext, tick=tick, strict=strict,
-                       n_orders=(per_update * updates + n_ext) * T + 16)
-
-
 # ------------------------------------------------------------------------------------------------ 1. the sets, every pool
 def run_alone(oracle, case, which, env=None, torch=None):
     """case 1 on the oracle (and on `env`): T x { update; step }; the Momentum member alone beside a thin flow of orders"""
@@ -211,7 +161,7 @@ def run_alone(oracle, case, which, env=None, torch=None):
             run.trading(s == 1)
         run.update()
         if which == "momentum":
-            run.submit(*_thin_flow(rng, B, 4, 1))
+            run.submit(*thin_flow(rng, B, 4, 1))
         run.step()
     return run
 
@@ -269,6 +219,34 @@ def test_members_with_external_instructions_equal_the_oracle(bk, oracle, name, w
     run, targets, listed = run_with_external(oracle, case, which, members_first, env, torch, NX)
     run.assert_busy()
     assert targets > case["books"] * case["steps"] // 2 and 3 * listed >= targets, (targets, listed)
+    assert not env.flags().any()
+    run.check()
+    env.close()
+
+
+# ------------------------------------------------------------------------------------- 2b. members wider than a wave
+@pytest.mark.parametrize("pool", [256, 512])
+@pytest.mark.parametrize("which", ["noise", "momentum"])
+def test_members_wider_than_a_wave_equal_the_oracle(bk, oracle, which, pool):
+    """70 Noise traders who all place both orders (140 New events: place_new's flush inside the loop, twice) and 130
+    Momentum traders at p_limit, p_market >= 1 (260), with lists of more than 128 Active ids (cancel_live_orders' second
+    and third 64-entry pass, compacting in place): tests/ingress_support.py::wide_set.  The same runs are held to the
+    model in tests/test_gpu_agents_model.py."""
+    import torch
+
+    B, T = 64, WIDE_STEPS
+    members = wide_set(which)
+    env = _make_env(bk, torch, B, T, pool, members, 1, n_ext=4)
+    env.set_agents(members)
+    run = Run(oracle, lambda b: members, B, 1, env, torch)
+    for s in range(T):
+        run.trading(wide_trading(which, s))
+        run.update()
+        run.submit(*wide_flow(which, pool, s, B, lambda b: run.sets[b].order_list(0)))
+        run.step()
+    run.assert_busy()
+    assert run.busy.longest_list > 128 and run.busy.largest_batch == 2 * members[0][2], (run.busy.longest_list, run.busy.largest_batch)
+    assert run.max_live < pool, run.max_live
     assert not env.flags().any()
     run.check()
     env.close()

@@ -10,6 +10,14 @@ and rounding order, not the DISTRIBUTIONS.  These tests check the distributions 
   Smirnov distance, first four moments, the ziggurat's tail region, the gen_bool(0.5) side split, over 1.6 M orders;
 * pm_math.hpp's exp / log / tanh as compiled for gfx950: equal to the HOST build of the same header bit for bit (the
   oracle's), and within 2 ulp (log: 3, tanh: 5 measured, 6 allowed) of libm over dense sweeps.
+
+WHAT IS PINNED EXACTLY ELSEWHERE, AND WHAT STAYS STATISTICAL.  tests/agents_model.py restates the generator, the ziggurat with
+its tail, Open01, the log-normal offset, the price rounding with its clamps and the two agents' updates in plain Python over
+libm, from the reference's Rust and the published crates, sharing no code with pm_math.hpp, the oracle or the kernels.  The
+oracle (tests/test_agents_model.py) and the device (tests/test_gpu_agents_model.py: Momentum members, p_limit / p_market /
+p_cancel rates, ticks 1, 2 and 5, the clamps at 0 and 2^32 - 1) are held to it with exact equality of every generator state,
+order and member list.  That pins the algorithm as this project reads it; agreement with a real Rust BUILD - its rand_distr
+tables and its platform's libm - stays what the tests below can say: statistical.
 """
 import ctypes as C
 import math

@@ -5,6 +5,8 @@ here and none of its tests asserts an RNG-dependent value.
 """
 import numpy as np
 
+from agents_model import gen_range as _py_gen_range, shuffle as _py_shuffle
+
 
 def test_xoroshiro128starstar_known_answer(oracle):
     # Published known-answer vector of xoroshiro128** for state (1, 2)
@@ -51,19 +53,8 @@ def test_next_u32_is_low_half_and_f32_scaling(oracle):
         assert 0.0 <= f < 1.0
 
 
-def _py_gen_range(rng, lo, hi):
-    rng_ = hi - lo
-    lz = 32 - rng_.bit_length()
-    zone = ((rng_ << lz) & 0xFFFFFFFF) - 1
-    while True:
-        v = rng.next_u32()
-        m = v * rng_
-        if (m & 0xFFFFFFFF) <= zone:
-            return lo + (m >> 32)
-
-
 def test_gen_range_and_shuffle_match_python_restatement(oracle):
-    # UniformInt::sample_single + SliceRandom::shuffle restated independently in Python (App. B.3/B.4)
+    # UniformInt::sample_single + SliceRandom::shuffle restated independently in Python (App. B.3/B.4): tests/agents_model.py
     for lo, hi in ((0, 2), (10, 100), (32, 64), (10, 20), (50, 70), (0, 129), (5, 6)):
         a, b = oracle.Rng(seed=lo * 1000 + hi), oracle.Rng(seed=lo * 1000 + hi)
         for _ in range(200):
@@ -74,10 +65,7 @@ def test_gen_range_and_shuffle_match_python_restatement(oracle):
     for n in (0, 1, 2, 3, 17, 64, 128, 500):
         a, b = oracle.Rng(seed=n), oracle.Rng(seed=n)
         got = a.shuffle(np.arange(n, dtype=np.uint32))
-        ref = list(range(n))
-        for i in range(n - 1, 0, -1):
-            j = _py_gen_range(b, 0, i + 1)
-            ref[i], ref[j] = ref[j], ref[i]
+        ref = _py_shuffle(b, list(range(n)))
         assert got.tolist() == ref
         assert tuple(a.st) == tuple(b.st)
         assert sorted(got.tolist()) == list(range(n))
