@@ -185,6 +185,11 @@ SIGNATURES = {
     "bk_checkpoint_bytes": (_u64, [_vp]),
     "bk_checkpoint_save": (_i32, [_vp, _vp, _u64]),
     "bk_checkpoint_load": (_i32, [_vp, _vp, _u64]),
+    "bk_snapshot_bytes": (_u64, [_vp]),
+    "bk_snapshot_save": (_i32, [_vp, _u32]),
+    "bk_snapshot_drop": (_i32, [_vp, _u32]),
+    "bk_reset_books_device": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_reset_books": (_i32, [_vp, _u32, _vp, _vp]),
 }
 
 _lib = None

@@ -48,6 +48,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "step_events.hpp"
 #include "agents_ingress.hpp"
 #include "members_ingress.hpp"
+#include "book_reset.hpp"
 
 using namespace bkd;
 
@@ -127,6 +128,15 @@ struct bk_env {
   int pipeline = 0;  // the caller's request, 0 auto .. 5 (pipeline_plan.hpp PlanInput::request)
   DevBuf<uint32_t> warm_snap;         // bk_warm: state + L2 copy of the scratch steps
   bool warming = false;               // bk_warm's scratch steps: no history slots, no trade records
+  // bk_snapshot_save: device-resident copies of state + l2_last that bk_reset_books* put chosen books back to, each with
+  // the ckpt_header words (shape, agent set) of the env as it was saved
+  struct Snapshot {
+    DevBuf<uint32_t> buf;
+    bool used = false;
+    uint64_t shape[4] = {0, 0, 0, 0};  // ckpt_header h[2..5]
+  } snaps[BK_MAX_SNAPSHOTS];
+  DevBuf<uint8_t> reset_mask;    // bk_reset_books: device staging of the host mask / seeds [n_units]
+  DevBuf<uint64_t> reset_seeds;
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
   uint32_t wave_lookahead = 64;
@@ -2794,6 +2804,118 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
+}
+
+// ---------------------------------------------------------------- per-book reset to a device-resident snapshot
+// No counterpart in the reference (an Env is rebuilt, never rewound).  What is moved is what a checkpoint carries - the
+// books' state blocks and level-2 records - but device to device, and back only for the units a mask names
+// (book_reset.hpp).
+uint64_t bk_snapshot_bytes(const bk_env* env) {
+  return env ? static_cast<uint64_t>(env->cfg.n_books) * (env->stride + env->W) * 4 : 0;
+}
+
+// the env kinds bk_checkpoint_save refuses, refused here for the same reasons
+static int snapshot_env_ok(bk_env* env, uint32_t slot) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (slot >= BK_MAX_SNAPSHOTS) return fail(BK_INVALID_ARGUMENT, "snapshot slot out of range (BK_MAX_SNAPSHOTS = 4)");
+  if (env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "snapshots of a host-driven env (bk_device_ingress_enable) are not supported, as its "
+                                     "checkpoints are not: the queues, the order records and the agents' held ids would "
+                                     "have to be rewound as well");
+  if (env->agent_log)
+    return fail(BK_INVALID_ARGUMENT, "snapshots of an env with the agents' order log (bk_set_agent_order_log) are not "
+                                     "supported, as its checkpoints are not: the log would keep the abandoned run's orders");
+  if (!env->device_flow)  // (an env bk_run has stepped with agents holds no host-placed order: host_flow_ok)
+    for (const BookHost& bh : env->books)
+      if (!bh.orders.empty())
+        return fail(BK_INVALID_ARGUMENT, "snapshots of a host-driven env (host-placed orders) are not supported, as its "
+                                         "checkpoints are not: the host's order table is not part of the books' state");
+  return BK_OK;
+}
+
+int bk_snapshot_save(bk_env* env, uint32_t slot) {
+  if (int rc = snapshot_env_ok(env, slot)) return rc;
+  if (int rc = use_device(env)) return rc;
+  bk_env::Snapshot& s = env->snaps[slot];
+  const size_t sb = static_cast<size_t>(env->cfg.n_books) * env->stride, lb = static_cast<size_t>(env->cfg.n_books) * env->W;
+  if (!s.buf.p) HIPCHK(s.buf.alloc(sb + lb));
+  s.used = false;
+  HIPCHK(hipMemcpyAsync(s.buf.p, env->state.p, sb * 4, hipMemcpyDeviceToDevice, env->stream));
+  HIPCHK(hipMemcpyAsync(s.buf.p + sb, env->l2_last.p, lb * 4, hipMemcpyDeviceToDevice, env->stream));
+  uint64_t h[CKPT_HDR];
+  ckpt_header(env, h);
+  for (int i = 0; i < 4; ++i) s.shape[i] = h[2 + i];
+  s.used = true;
+  return BK_OK;
+}
+
+int bk_snapshot_drop(bk_env* env, uint32_t slot) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (slot >= BK_MAX_SNAPSHOTS) return fail(BK_INVALID_ARGUMENT, "snapshot slot out of range (BK_MAX_SNAPSHOTS = 4)");
+  if (int rc = use_device(env)) return rc;
+  bk_env::Snapshot& s = env->snaps[slot];
+  if (s.buf.p) HIPCHK(hipStreamSynchronize(env->stream));  // (a reset from the slot may still be queued)
+  s.used = false;
+  HIPCHK(s.buf.alloc(0));
+  return BK_OK;
+}
+
+// every refusal, before anything is enqueued
+static int reset_ok(bk_env* env, uint32_t slot, const void* mask) {
+  if (int rc = snapshot_env_ok(env, slot)) return rc;
+  if (!mask) return fail(BK_INVALID_ARGUMENT, "null mask");
+  const bk_env::Snapshot& s = env->snaps[slot];
+  if (!s.used) return fail(BK_INVALID_ARGUMENT, "snapshot slot is empty: call bk_snapshot_save first");
+  uint64_t h[CKPT_HDR];
+  ckpt_header(env, h);
+  if (s.shape[0] != h[2] || s.shape[1] != h[3])
+    return fail(BK_INVALID_ARGUMENT, "snapshot does not match this env (n_books / pool size / levels / assets)");
+  if (s.shape[2] != h[4] || s.shape[3] != h[5])
+    return fail(BK_INVALID_ARGUMENT, "snapshot was taken with a different agent set: install the same agents first");
+  return BK_OK;
+}
+
+// Holds NO host synchronisation: one launch on the env's stream - no stream wait, no host read of the mask, no allocation.
+int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
+  if (int rc = reset_ok(env, slot, mask_dev)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const size_t sb = static_cast<size_t>(env->cfg.n_books) * env->stride;
+  reset::ResetArgs g{};
+  g.state = env->state.p;
+  g.l2_last = env->l2_last.p;
+  g.snap_state = env->snaps[slot].buf.p;
+  g.snap_l2 = env->snaps[slot].buf.p + sb;
+  g.stride = env->stride;
+  g.W = env->W;
+  g.M = env->M;
+  g.n_units = env->cfg.n_books / env->M;
+  g.mask = mask_dev;
+  g.seeds = seeds_dev;
+  g.trading = env->trading;
+  const dim3 grid((g.n_units + reset::WAVES - 1) / reset::WAVES), block(64 * reset::WAVES);
+  switch (env->R) {
+    case 1: hipLaunchKernelGGL(reset::k_reset_books<1>, grid, block, 0, env->stream, g); break;
+    case 2: hipLaunchKernelGGL(reset::k_reset_books<2>, grid, block, 0, env->stream, g); break;
+    case 4: hipLaunchKernelGGL(reset::k_reset_books<4>, grid, block, 0, env->stream, g); break;
+    default: hipLaunchKernelGGL(reset::k_reset_books<8>, grid, block, 0, env->stream, g); break;
+  }
+  HIPCHK(hipGetLastError());
+  // which books changed is known on the device only: the members' lists of every book are rebuilt from the owner tags
+  env->ml_valid = false;
+  env->wl_valid = false;
+  return BK_OK;
+}
+
+int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host) {
+  if (int rc = reset_ok(env, slot, mask_host)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const size_t n_units = env->cfg.n_books / env->M;
+  if (!env->reset_mask.p) HIPCHK(env->reset_mask.alloc(n_units));
+  if (seeds_host && !env->reset_seeds.p) HIPCHK(env->reset_seeds.alloc(n_units));
+  HIPCHK(hipMemcpyAsync(env->reset_mask.p, mask_host, n_units, hipMemcpyHostToDevice, env->stream));
+  if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
+  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
+  return bk_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

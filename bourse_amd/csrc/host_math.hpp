@@ -6,20 +6,27 @@
 #include <cstdint>
 #include <vector>
 
+// the seeding is ONE text for the host (bk_env_create) and the device (book_reset.hpp): under hipcc it compiles for both
+#if defined(__HIPCC__)
+#define BKD_HOST_DEVICE __host__ __device__
+#else
+#define BKD_HOST_DEVICE
+#endif
+
 namespace bkd {
 
 // rand_xoshiro 0.6.0 `seed_from_u64` for Xoroshiro128StarStar: two SplitMix64 outputs
-inline void seed_from_u64(uint64_t seed, uint64_t& s0, uint64_t& s1) {
+BKD_HOST_DEVICE inline uint64_t splitmix64_next(uint64_t& x) {
+  x += 0x9e3779b97f4a7c15ull;
+  uint64_t z = x;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+BKD_HOST_DEVICE inline void seed_from_u64(uint64_t seed, uint64_t& s0, uint64_t& s1) {
   uint64_t x = seed;
-  auto next = [&x]() {
-    x += 0x9e3779b97f4a7c15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-  };
-  s0 = next();
-  s1 = next();
+  s0 = splitmix64_next(x);
+  s1 = splitmix64_next(x);
 }
 
 // `gen::<f32>() < rate` with gen = (u32 >> 8) * 2^-24 (App. B.5) as an integer threshold on k = (u32 >> 8):

@@ -941,6 +941,61 @@ class ManyBookEnv:
     def state_bytes_per_book(self) -> int:
         return int(self._L.bk_state_bytes_per_book(self._h))
 
+    # ------------------------------------------------------------ per-book reset to a device-resident snapshot
+    def snapshot_bytes(self) -> int:
+        """Device bytes one snapshot slot costs."""
+        return int(self._L.bk_snapshot_bytes(self._h))
+
+    def save_snapshot(self, slot: int = 0):
+        """``bk_snapshot_save``: a device-resident copy of every book's state (pool, clock, counters, RNG, level-2 record)
+        in ``slot`` (0 .. 3), queued on the env's stream; a later save of the slot overwrites it.  The reference has no
+        counterpart."""
+        check(self._L.bk_snapshot_save(self._h, int(slot)))
+
+    def drop_snapshot(self, slot: int = 0):
+        """Free the slot's device memory (``bk_snapshot_drop``)."""
+        check(self._L.bk_snapshot_drop(self._h, int(slot)))
+
+    def reset_books(self, mask, seeds=None, slot: int = 0, sync: bool = True):
+        """Books ``b`` with ``mask[b]`` set go back to their state in snapshot ``slot`` while the others carry on
+        (``bk_reset_books`` / ``bk_reset_books_device``); on a market env the mask is over markets and every book of a
+        masked market goes back.  ``mask``: bool / uint8, one per book (market) - a host array, or a torch CUDA tensor /
+        ``__cuda_array_interface__`` object written on the env's stream, which then never passes through the host.
+        ``seeds`` (uint64, same length, the same kind of object as the mask): the reset books start a new RNG stream,
+        seeded as a fresh env's book with that seed is.  A reset book keeps its sticky flags and takes the env's current
+        trading flag; no trade of the run it abandons stays retained; the env's step counter and history ring go on
+        (``history()`` rows of a reset book continue at the env's step index).  Queued on the env's stream; ``sync``
+        waits for it."""
+        n_units = self.n_books // self.assets
+
+        def is_dev(x):
+            return hasattr(x, "data_ptr") or hasattr(x, "__cuda_array_interface__")
+
+        def count(x):
+            return int(x.numel()) if hasattr(x, "numel") else int(np.prod(x.__cuda_array_interface__["shape"]))
+
+        if mask is None:
+            raise ValueError("mask: one bool / uint8 per book (market) is needed")
+        if seeds is not None and is_dev(mask) != is_dev(seeds):
+            raise ValueError("mask and seeds must both be host arrays or both be device arrays")
+        if is_dev(mask):
+            if count(mask) != n_units or (seeds is not None and count(seeds) != n_units):
+                raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
+            check(self._L.bk_reset_books_device(self._h, int(slot), self._dev_ptr(mask, 1, "mask"),
+                                                self._dev_ptr(seeds, 8, "seeds")))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError("mask: a bool or uint8 array is needed")
+            m = m.astype(np.uint8, copy=False)
+            s = None if seeds is None else np.ascontiguousarray(np.asarray(seeds), dtype=np.uint64)
+            if m.shape != (n_units,) or (s is not None and s.shape != (n_units,)):
+                raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
+            check(self._L.bk_reset_books(self._h, int(slot), m.ctypes.data_as(C.c_void_p),
+                                         None if s is None else s.ctypes.data_as(C.c_void_p)))
+        if sync:
+            self.sync()
+
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):
     """``sim_runner(env, agents, seed, n_steps, _)`` (ref runner.rs:46-69) for every book of ``env``.
@@ -968,6 +1023,11 @@ class ManyMarketEnv(ManyBookEnv):
         if not (0 <= market < self.n_markets and 0 <= asset < self.assets):
             raise IndexError("market / asset out of range")
         return market * self.assets + asset
+
+    def reset_markets(self, mask, seeds=None, slot: int = 0, sync: bool = True):
+        """``reset_books`` spelt by market: ``mask`` / ``seeds`` hold one element per market, and every book of a masked
+        market goes back to the snapshot (with ``seeds``, all of them on the market's new RNG stream)."""
+        self.reset_books(mask, seeds, slot, sync)
 
     def place_order(self, market: int, asset: int, bid: bool, vol: int, trader_id: int, price: Optional[int] = None):
         """``MarketEnv::place_order(asset, side, vol, trader_id, price)`` (market_env.rs:163-176) -> per-asset order id"""

@@ -468,6 +468,42 @@ uint64_t bk_checkpoint_bytes(const bk_env* env);
 int bk_checkpoint_save(bk_env* env, void* out, uint64_t nbytes);
 int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes);
 
+/* ------------------------------------------------------ per-book reset to a device-resident snapshot */
+/* Chosen books of an on-device-order-flow env go back to a snapshot that never leaves the device, while the others carry
+ * on: episodes that end at different times per book, a finished parameter row of a sweep started again.  The reference
+ * has no counterpart for any of these entries: its Env is rebuilt, never rewound, and one Env is one book.
+ * The unit of a reset is a book, or with assets > 1 a market (its books share one RNG stream): n_units = n_books /
+ * assets.  Every refusal below is BK_INVALID_ARGUMENT, is checked before anything is enqueued and leaves the env unchanged:
+ * slot >= BK_MAX_SNAPSHOTS, and - the conditions bk_checkpoint_save refuses on, for the same reasons - an env with the
+ * device ingress (its queues, order records and held ids would have to be rewound as well), an env with the agents'
+ * order log (the log would keep the abandoned run's orders), an env that holds host-placed orders. */
+#define BK_MAX_SNAPSHOTS 4
+/* Device bytes one slot costs: n_books * (pool block + level-2 row) * 4.  (No counterpart in the reference.) */
+uint64_t bk_snapshot_bytes(const bk_env* env);
+/* Device-to-device copy of every book's state block and level-2 record into `slot` (allocated at its first save,
+ * overwritten by a later one), with the agent set's hash and the env's shape recorded beside it.  Asynchronous on the
+ * env's stream.  (No counterpart in the reference.) */
+int bk_snapshot_save(bk_env* env, uint32_t slot);
+/* Frees the slot's memory (waits for the env's stream first); dropping an empty slot is not an error; bk_env_destroy
+ * drops every slot.  (No counterpart in the reference.) */
+int bk_snapshot_drop(bk_env* env, uint32_t slot);
+/* Units u with mask_dev[u] != 0 return to their state in `slot`; the others are not touched.  mask_dev [n_units] bytes and
+ * seeds_dev [n_units] u64 (nullable) are DEVICE memory written on the env's stream - by the caller's own kernels, for
+ * instance.  A reset unit gets back everything its books held at the save (pool, clock, id / step / event counters, trade
+ * volume, RNG, the members' state in the block) except: no trade record of the abandoned run stays retained (bk_trade_count
+ * = {the snapshot's total, first_retained = the same}); sticky flags are kept (snapshot's | current; bk_clear_flags clears);
+ * the trading flag is the env's current one; with seeds_dev, the unit's RNG is seed_from_u64(seeds_dev[u]) as bk_env_create
+ * seeds it (in every book of a market).  Not rewound: bk_steps_done, the history ring (a reset book keeps writing its rows
+ * at the env's step index), the other books.  Noise / Momentum members' lists are rebuilt from the pools by the next bk_run.
+ * HOLDS NO HOST SYNCHRONISATION: one kernel launch on the env's stream - no stream wait, no host read of the mask, no
+ * allocation.  Further refusals: empty slot, null mask, a slot saved with another agent set or shape ("install the same
+ * agents first", as bk_checkpoint_load).  (No counterpart in the reference.) */
+int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev);
+/* The same from HOST arrays: mask and seeds are staged in two env-owned device buffers (allocated at the first call),
+ * copied on the env's stream, and the copy is waited for - the caller's arrays are free on return; the reset itself
+ * stays asynchronous.  (No counterpart in the reference.) */
+int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host);
+
 #ifdef __cplusplus
 }
 #endif

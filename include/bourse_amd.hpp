@@ -217,6 +217,13 @@ class ManyEnv {
     check(bk_run(h_, n_steps));
     check(bk_env_sync(h_));
   }
+  // device-resident snapshot of every book (bk_snapshot_save), and chosen books back to it between two runs
+  // (bk_reset_books: mask[b] != 0 resets book b; seeds, if any, re-seed the reset books); the reference has no counterpart
+  void save_snapshot(uint32_t slot = 0) { check(bk_snapshot_save(h_, slot)); }
+  void reset_books(const std::vector<uint8_t>& mask, const uint64_t* seeds = nullptr, uint32_t slot = 0) {
+    if (mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_reset_books(h_, slot, mask.data(), seeds));
+  }
   bk_env* handle() { return h_; }
 
  private:
