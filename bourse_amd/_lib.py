@@ -190,6 +190,11 @@ SIGNATURES = {
     "bk_snapshot_drop": (_i32, [_vp, _u32]),
     "bk_reset_books_device": (_i32, [_vp, _u32, _vp, _vp]),
     "bk_reset_books": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_ingress_snapshot_save": (_i32, [_vp, _u32]),
+    "bk_ingress_snapshot_drop": (_i32, [_vp, _u32]),
+    "bk_ingress_snapshot_bytes": (_u64, [_vp, _u32]),
+    "bk_ingress_reset_books_device": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_ingress_reset_books": (_i32, [_vp, _u32, _vp, _vp]),
 }
 
 _lib = None

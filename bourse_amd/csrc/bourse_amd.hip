@@ -49,6 +49,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "agents_ingress.hpp"
 #include "members_ingress.hpp"
 #include "book_reset.hpp"
+#include "ingress_reset.hpp"
 
 using namespace bkd;
 
@@ -137,6 +138,24 @@ struct bk_env {
   } snaps[BK_MAX_SNAPSHOTS];
   DevBuf<uint8_t> reset_mask;    // bk_reset_books: device staging of the host mask / seeds [n_units]
   DevBuf<uint64_t> reset_seeds;
+  // bk_ingress_snapshot_save: slots of their own for a device-ingress env - the two arrays above, the order records of the
+  // ids the books had handed out ([n_books][n_keep] of dorders and order_log) and the agents' / members' per-book rows
+  // (ingress_reset.hpp), with the env's shape, its agent set and the count of bk_set_*agents* calls as it was saved
+  struct IngressSnapshot {
+    DevBuf<uint32_t> buf;
+    DevBuf<uint4> orders, log;
+    uint32_t n_keep = 0, keep_cap = 0;  // ids per book held / allocated
+    DevBuf<uint32_t> held, lists, lens, mflags;
+    DevBuf<uint64_t> mstate;
+    bool held_saved = false, members_saved = false;  // false: the env had not made these buffers yet (every agent holds None)
+    bool used = false;
+    uint64_t shape[4] = {0, 0, 0, 0};  // ckpt_header h[2..5]
+    uint64_t installs = 0;
+    uint64_t bytes = 0;
+  } isnaps[BK_MAX_SNAPSHOTS];
+  DevBuf<uint32_t> reset_list;  // [n_units] the masked units of one ingress reset, then its counter (k_collect_units)
+  int reset_blocks = 0;         // k_reset_records' fixed grid: 4 blocks of 4 waves per CU
+  uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
   uint32_t wave_lookahead = 64;
@@ -1777,6 +1796,7 @@ int bk_set_random_market_agents(bk_env* env, uint32_t n_groups, const bk_random_
   (void)env->dmtable.alloc(0);
   env->agents_hash = gs.empty() ? 0 : groups_hash(gs.data(), gs.size());
   env->agent_held_stale = true;  // (a new RandomAgents::new: the agents hold nothing)
+  env->agent_installs += 1;
   return BK_OK;
 }
 
@@ -1807,6 +1827,7 @@ int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_rando
   (void)env->dmtable.alloc(0);
   env->agents_hash = groups_hash(env->table.data(), env->table.size());
   env->agent_held_stale = true;
+  env->agent_installs += 1;
   return BK_OK;
 }
 
@@ -1890,6 +1911,7 @@ static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32
   env->member_n.resize(n_members);
   for (uint32_t i = 0; i < n_members; ++i) env->member_type[i] = ds[i].type, env->member_n[i] = ds[i].n;
   env->member_lists_stale = true;  // (a new AgentSet: empty lists, no momentum state; bk_update_members)
+  env->agent_installs += 1;
   env->wl_valid = false;
   for (uint32_t i = 0; i < MAX_MEMBERS; ++i) env->member_asset[i] = (assets && i < n_members) ? assets[i] : 0u;
   for (uint32_t as = 0; as < MAX_ASSETS; ++as) env->n_fixed_a[as] = fixed_a[as];
@@ -2814,7 +2836,8 @@ uint64_t bk_snapshot_bytes(const bk_env* env) {
   return env ? static_cast<uint64_t>(env->cfg.n_books) * (env->stride + env->W) * 4 : 0;
 }
 
-// the env kinds bk_checkpoint_save refuses, refused here for the same reasons
+// the env kinds bk_checkpoint_save refuses, refused here for the same reasons (a device-ingress env has entries of its
+// own, bk_ingress_snapshot_save / bk_ingress_reset_books* below, which rewind what it keeps beside the state blocks)
 static int snapshot_env_ok(bk_env* env, uint32_t slot) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (slot >= BK_MAX_SNAPSHOTS) return fail(BK_INVALID_ARGUMENT, "snapshot slot out of range (BK_MAX_SNAPSHOTS = 4)");
@@ -2875,16 +2898,14 @@ static int reset_ok(bk_env* env, uint32_t slot, const void* mask) {
   return BK_OK;
 }
 
-// Holds NO host synchronisation: one launch on the env's stream - no stream wait, no host read of the mask, no allocation.
-int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
-  if (int rc = reset_ok(env, slot, mask_dev)) return rc;
-  if (int rc = use_device(env)) return rc;
+// reset::k_reset_books<R> for the units the mask names, from `snap` = [state | l2_last] of a slot, on the env's stream
+static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
   const size_t sb = static_cast<size_t>(env->cfg.n_books) * env->stride;
   reset::ResetArgs g{};
   g.state = env->state.p;
   g.l2_last = env->l2_last.p;
-  g.snap_state = env->snaps[slot].buf.p;
-  g.snap_l2 = env->snaps[slot].buf.p + sb;
+  g.snap_state = snap;
+  g.snap_l2 = snap + sb;
   g.stride = env->stride;
   g.W = env->W;
   g.M = env->M;
@@ -2899,6 +2920,13 @@ int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, c
     case 4: hipLaunchKernelGGL(reset::k_reset_books<4>, grid, block, 0, env->stream, g); break;
     default: hipLaunchKernelGGL(reset::k_reset_books<8>, grid, block, 0, env->stream, g); break;
   }
+}
+
+// Holds NO host synchronisation: one launch on the env's stream - no stream wait, no host read of the mask, no allocation.
+int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
+  if (int rc = reset_ok(env, slot, mask_dev)) return rc;
+  if (int rc = use_device(env)) return rc;
+  launch_reset_books(env, env->snaps[slot].buf.p, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
   // which books changed is known on the device only: the members' lists of every book are rebuilt from the owner tags
   env->ml_valid = false;
@@ -2916,6 +2944,232 @@ int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const u
   if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
   HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
   return bk_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
+}
+
+// ---------------------------------------------------------------- the same for a device-ingress env
+// No counterpart in the reference.  A device-ingress env keeps more per book than the two arrays above: its queue length,
+// the order records of the ids it has handed out, the held ids of bk_update_agents and the lists and momentum state of
+// bk_update_members - all rewound here, on the device (ingress_reset.hpp).  The slots are the env's
+// isnaps, apart from bk_snapshot_save's.
+static bool held_active(const bk_env* env) { return env->M == 1 && !env->n_mixed && !env->groups.empty(); }
+static bool members_active(const bk_env* env) { return env->M == 1 && env->n_mixed != 0; }
+
+static int ingress_slot_ok(bk_env* env, uint32_t slot) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (slot >= BK_MAX_SNAPSHOTS) return fail(BK_INVALID_ARGUMENT, "snapshot slot out of range (BK_MAX_SNAPSHOTS = 4)");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "bk_ingress_snapshot_* / bk_ingress_reset_books* serve an env with the device ingress "
+                                     "(bk_device_ingress_enable): this env's entries are bk_snapshot_save / bk_reset_books");
+  return BK_OK;
+}
+
+// k_reset_records' arguments for this env's agents and members (the rows a reset moves); false: its work items would
+// not fit the kernel's 32-bit index
+static bool ingress_record_args(const bk_env* env, uint32_t n_keep, reset::RecordArgs& g) {
+  g.n_units = env->cfg.n_books / env->M;
+  g.M = env->M;
+  g.stride = env->stride;
+  g.max_orders = env->cfg.max_orders;
+  g.n_keep = n_keep;
+  uint32_t max_n = 0;
+  if (held_active(env)) g.n_agents = env->n_agents_total;
+  if (members_active(env)) {
+    g.n_members = env->n_mixed;
+    for (uint32_t j = 0; j < env->n_mixed; ++j) {
+      g.member_n[j] = env->member_n[j];
+      max_n = std::max(max_n, env->member_n[j]);
+      if (env->member_type[j] == BK_AGENT_RANDOM) g.random_mask |= 1u << j;
+    }
+    g.list_cap = bkd::ingress::members_list_cap(static_cast<uint32_t>(env->R), max_n);  // (as bk_update_members sizes a row)
+  }
+  const uint64_t s_book = uint64_t(reset::segs(n_keep * reset::ORD_V, reset::SEG_V)) + reset::segs(n_keep * reset::LOG_V, reset::SEG_V) +
+                          reset::segs(g.n_agents, reset::SEG_DW) + uint64_t(g.n_members) * reset::segs(g.list_cap, reset::SEG_DW);
+  return s_book * env->cfg.n_books < 0xFFFFFFFFull;
+}
+
+uint64_t bk_ingress_snapshot_bytes(const bk_env* env, uint32_t slot) {
+  return env && slot < BK_MAX_SNAPSHOTS && env->isnaps[slot].used ? env->isnaps[slot].bytes : 0;
+}
+
+// May synchronise (a reset may not): the number of ids to keep per book is read back from a small device reduction, and
+// the slot's record arrays are sized by it.
+int bk_ingress_snapshot_save(bk_env* env, uint32_t slot) {
+  if (int rc = ingress_slot_ok(env, slot)) return rc;
+  if (int rc = use_device(env)) return rc;
+  bk_env::IngressSnapshot& s = env->isnaps[slot];
+  const size_t B = env->cfg.n_books, n_units = B / env->M;
+  const size_t sb = B * env->stride, lb = B * env->W;
+  HIPCHK(hipStreamSynchronize(env->stream));  // (a reset from the slot may still be queued: its arrays may be replaced)
+  if (!env->reset_list.p) {
+    HIPCHK(env->reset_list.alloc(n_units + 1));
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->cfg.device));
+    env->reset_blocks = std::max(cus, 1) * 4;
+  }
+  uint32_t* counter = env->reset_list.p + n_units;
+  uint32_t n_keep = 0;
+  HIPCHK(hipMemsetAsync(counter, 0, 4, env->stream));
+  hipLaunchKernelGGL(reset::k_max_keep, dim3((B + 255) / 256), dim3(256), 0, env->stream, env->state.p, env->stride,
+                     static_cast<uint32_t>(B), env->cfg.max_orders, counter);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&n_keep, counter, 4, hipMemcpyDeviceToHost, env->stream));
+  HIPCHK(hipStreamSynchronize(env->stream));
+  reset::RecordArgs g{};
+  if (!ingress_record_args(env, n_keep, g))
+    return fail(BK_CAPACITY, "bk_ingress_snapshot_save: books x order records exceed what one reset launch indexes");
+  s.used = false;
+  if (!s.buf.p) HIPCHK(s.buf.alloc(sb + lb));
+  if (n_keep > s.keep_cap) {
+    HIPCHK(s.orders.alloc(B * n_keep * reset::ORD_V));
+    HIPCHK(s.log.alloc(B * n_keep * reset::LOG_V));
+    s.keep_cap = n_keep;
+  }
+  s.n_keep = n_keep;
+  HIPCHK(hipMemcpyAsync(s.buf.p, env->state.p, sb * 4, hipMemcpyDeviceToDevice, env->stream));
+  HIPCHK(hipMemcpyAsync(s.buf.p + sb, env->l2_last.p, lb * 4, hipMemcpyDeviceToDevice, env->stream));
+  if (n_keep) {  // the records of ids < keep_b, packed to rows of n_keep ids: k_reset_records over every unit
+    g.n_agents = g.n_members = 0;
+    g.keep_state = env->state.p;
+    g.dst_orders = reinterpret_cast<bk_u32x4*>(s.orders.p);
+    g.src_orders = reinterpret_cast<const bk_u32x4*>(env->dorders.p);
+    g.dst_log = reinterpret_cast<bk_u32x4*>(s.log.p);
+    g.src_log = reinterpret_cast<const bk_u32x4*>(env->order_log.p);
+    g.dst_ids = n_keep;
+    g.src_ids = env->cfg.max_orders;
+    hipLaunchKernelGGL(reset::k_reset_records, dim3(env->reset_blocks), dim3(64 * reset::RECORD_WAVES), 0, env->stream, g);
+    HIPCHK(hipGetLastError());
+  }
+  s.bytes = (sb + lb) * 4 + B * s.keep_cap * (reset::ORD_V + reset::LOG_V) * 16;
+  s.held_saved = held_active(env) && !env->agent_held_stale;
+  if (s.held_saved) {
+    const size_t n = B * env->n_agents_total;
+    if (s.held.n != n) HIPCHK(s.held.alloc(n));
+    if (n) HIPCHK(hipMemcpyAsync(s.held.p, env->agent_held.p, n * 4, hipMemcpyDeviceToDevice, env->stream));
+    s.bytes += n * 4;
+  }
+  s.members_saved = members_active(env) && !env->member_lists_stale;
+  if (s.members_saved) {
+    const size_t rows = B * env->n_mixed, nl = rows * env->member_list_cap;
+    if (s.lists.n != nl) HIPCHK(s.lists.alloc(nl));
+    if (s.lens.n != rows) HIPCHK(s.lens.alloc(rows));
+    if (s.mstate.n != rows * 2) HIPCHK(s.mstate.alloc(rows * 2));
+    if (s.mflags.n != B) HIPCHK(s.mflags.alloc(B));
+    HIPCHK(hipMemcpyAsync(s.lists.p, env->member_lists.p, nl * 4, hipMemcpyDeviceToDevice, env->stream));
+    HIPCHK(hipMemcpyAsync(s.lens.p, env->member_lens.p, rows * 4, hipMemcpyDeviceToDevice, env->stream));
+    HIPCHK(hipMemcpyAsync(s.mstate.p, env->member_state.p, rows * 16, hipMemcpyDeviceToDevice, env->stream));
+    HIPCHK(hipMemcpyAsync(s.mflags.p, env->member_flags.p, B * 4, hipMemcpyDeviceToDevice, env->stream));
+    s.bytes += nl * 4 + rows * 20 + B * 4;
+  }
+  uint64_t h[CKPT_HDR];
+  ckpt_header(env, h);
+  for (int i = 0; i < 4; ++i) s.shape[i] = h[2 + i];
+  s.installs = env->agent_installs;
+  s.used = true;
+  return BK_OK;
+}
+
+int bk_ingress_snapshot_drop(bk_env* env, uint32_t slot) {
+  if (int rc = ingress_slot_ok(env, slot)) return rc;
+  if (int rc = use_device(env)) return rc;
+  bk_env::IngressSnapshot& s = env->isnaps[slot];
+  if (s.buf.p) HIPCHK(hipStreamSynchronize(env->stream));  // (a reset from the slot may still be queued)
+  s.used = false;
+  s.n_keep = s.keep_cap = 0;
+  s.bytes = 0;
+  HIPCHK(s.buf.alloc(0));
+  HIPCHK(s.orders.alloc(0));
+  HIPCHK(s.log.alloc(0));
+  HIPCHK(s.held.alloc(0));
+  HIPCHK(s.lists.alloc(0));
+  HIPCHK(s.lens.alloc(0));
+  HIPCHK(s.mstate.alloc(0));
+  HIPCHK(s.mflags.alloc(0));
+  return BK_OK;
+}
+
+// every refusal, before anything is enqueued
+static int ingress_reset_ok(bk_env* env, uint32_t slot, const void* mask) {
+  if (int rc = ingress_slot_ok(env, slot)) return rc;
+  const bk_env::IngressSnapshot& s = env->isnaps[slot];
+  if (!s.used) return fail(BK_INVALID_ARGUMENT, "snapshot slot is empty: call bk_ingress_snapshot_save first");
+  if (!mask) return fail(BK_INVALID_ARGUMENT, "null mask");
+  uint64_t h[CKPT_HDR];
+  ckpt_header(env, h);
+  if (s.shape[0] != h[2] || s.shape[1] != h[3])
+    return fail(BK_INVALID_ARGUMENT, "snapshot does not match this env (n_books / pool size / levels / assets)");
+  if (s.shape[2] != h[4] || s.shape[3] != h[5])
+    return fail(BK_INVALID_ARGUMENT, "snapshot was taken with a different agent set: install the same agents first");
+  if (s.installs != env->agent_installs)
+    return fail(BK_INVALID_ARGUMENT, "agents were installed again (bk_set_*agents*) since the snapshot was taken: their held "
+                                     "ids and lists start empty at the next update, which a reset cannot restore - call "
+                                     "bk_ingress_snapshot_save again");
+  return BK_OK;
+}
+
+// Holds NO host synchronisation: a memset and three launches on the env's stream - no stream wait, no host read, no
+// allocation (the list of masked units was allocated by the first save).
+int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
+  if (int rc = ingress_reset_ok(env, slot, mask_dev)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const bk_env::IngressSnapshot& s = env->isnaps[slot];
+  const uint32_t n_units = env->cfg.n_books / env->M;
+  launch_reset_books(env, s.buf.p, mask_dev, seeds_dev);
+  HIPCHK(hipGetLastError());
+  uint32_t* counter = env->reset_list.p + n_units;
+  HIPCHK(hipMemsetAsync(counter, 0, 4, env->stream));
+  // (after a bk_set_*agents* call and before the next update the env's own rows are stale and are re-made by that update;
+  // the install count has refused every slot that holds rows by then)
+  const bool held = held_active(env) && !env->agent_held_stale, members = members_active(env) && !env->member_lists_stale;
+  reset::CollectArgs c{};
+  c.mask = mask_dev;
+  c.n_units = n_units;
+  c.M = env->M;
+  c.list = env->reset_list.p;
+  c.count = counter;
+  c.dqlen = env->dqlen.p;
+  if (members) {
+    c.n_members = env->n_mixed;
+    c.lens = env->member_lens.p;
+    c.mstate = env->member_state.p;
+    c.mflags = env->member_flags.p;
+    if (s.members_saved) c.snap_lens = s.lens.p, c.snap_mstate = s.mstate.p, c.snap_mflags = s.mflags.p;
+  }
+  hipLaunchKernelGGL(reset::k_collect_units, dim3((n_units + 255) / 256), dim3(256), 0, env->stream, c);
+  HIPCHK(hipGetLastError());
+  reset::RecordArgs g{};
+  ingress_record_args(env, s.n_keep, g);  // (checked at the save)
+  if (!held) g.n_agents = 0;
+  if (!members) g.n_members = g.list_cap = 0;
+  g.list = env->reset_list.p;
+  g.count = counter;
+  g.keep_state = s.buf.p;
+  g.dst_orders = reinterpret_cast<bk_u32x4*>(env->dorders.p);
+  g.src_orders = reinterpret_cast<const bk_u32x4*>(s.orders.p);
+  g.dst_log = reinterpret_cast<bk_u32x4*>(env->order_log.p);
+  g.src_log = reinterpret_cast<const bk_u32x4*>(s.log.p);
+  g.dst_ids = env->cfg.max_orders;
+  g.src_ids = s.n_keep;
+  g.held = env->agent_held.p;
+  g.snap_held = s.held_saved ? s.held.p : nullptr;
+  g.lists = env->member_lists.p;
+  g.snap_lists = s.members_saved ? s.lists.p : nullptr;
+  g.snap_lens = s.members_saved ? s.lens.p : nullptr;
+  hipLaunchKernelGGL(reset::k_reset_records, dim3(env->reset_blocks), dim3(64 * reset::RECORD_WAVES), 0, env->stream, g);
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;  // the readers' mirrors of the orders and the log fetch from the device again
+  return BK_OK;
+}
+
+int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host) {
+  if (int rc = ingress_reset_ok(env, slot, mask_host)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const size_t n_units = env->cfg.n_books / env->M;
+  if (!env->reset_mask.p) HIPCHK(env->reset_mask.alloc(n_units));
+  if (seeds_host && !env->reset_seeds.p) HIPCHK(env->reset_seeds.alloc(n_units));
+  HIPCHK(hipMemcpyAsync(env->reset_mask.p, mask_host, n_units, hipMemcpyHostToDevice, env->stream));
+  if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
+  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
+  return bk_ingress_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

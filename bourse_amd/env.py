@@ -966,6 +966,9 @@ class ManyBookEnv:
         trading flag; no trade of the run it abandons stays retained; the env's step counter and history ring go on
         (``history()`` rows of a reset book continue at the env's step index).  Queued on the env's stream; ``sync``
         waits for it."""
+        self._masked_reset(self._L.bk_reset_books_device, self._L.bk_reset_books, mask, seeds, slot, sync)
+
+    def _masked_reset(self, device_entry, host_entry, mask, seeds, slot, sync):
         n_units = self.n_books // self.assets
 
         def is_dev(x):
@@ -981,8 +984,7 @@ class ManyBookEnv:
         if is_dev(mask):
             if count(mask) != n_units or (seeds is not None and count(seeds) != n_units):
                 raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
-            check(self._L.bk_reset_books_device(self._h, int(slot), self._dev_ptr(mask, 1, "mask"),
-                                                self._dev_ptr(seeds, 8, "seeds")))
+            check(device_entry(self._h, int(slot), self._dev_ptr(mask, 1, "mask"), self._dev_ptr(seeds, 8, "seeds")))
         else:
             m = np.ascontiguousarray(np.asarray(mask))
             if m.dtype != np.bool_ and m.dtype != np.uint8:
@@ -991,10 +993,34 @@ class ManyBookEnv:
             s = None if seeds is None else np.ascontiguousarray(np.asarray(seeds), dtype=np.uint64)
             if m.shape != (n_units,) or (s is not None and s.shape != (n_units,)):
                 raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
-            check(self._L.bk_reset_books(self._h, int(slot), m.ctypes.data_as(C.c_void_p),
-                                         None if s is None else s.ctypes.data_as(C.c_void_p)))
+            check(host_entry(self._h, int(slot), m.ctypes.data_as(C.c_void_p),
+                             None if s is None else s.ctypes.data_as(C.c_void_p)))
         if sync:
             self.sync()
+
+    # ------------------------------------------------------------ the same for an env with the device ingress
+    def ingress_snapshot_bytes(self, slot: int = 0) -> int:
+        """Device bytes ingress-snapshot ``slot`` holds (0: empty)."""
+        return int(self._L.bk_ingress_snapshot_bytes(self._h, int(slot)))
+
+    def save_ingress_snapshot(self, slot: int = 0):
+        """``bk_ingress_snapshot_save``: ``save_snapshot`` for an env with the device ingress, in slots (0 .. 3) of their
+        own - besides every book's state, the order records of the ids handed out so far, the held ids of
+        ``update_agents`` and the lists and momentum state of ``update_members``.  Waits for the env's stream.  The
+        reference has no counterpart."""
+        check(self._L.bk_ingress_snapshot_save(self._h, int(slot)))
+
+    def drop_ingress_snapshot(self, slot: int = 0):
+        """Free the slot's device memory (``bk_ingress_snapshot_drop``)."""
+        check(self._L.bk_ingress_snapshot_drop(self._h, int(slot)))
+
+    def reset_ingress_books(self, mask, seeds=None, slot: int = 0, sync: bool = True):
+        """``reset_books`` for an env with the device ingress (``bk_ingress_reset_books`` /
+        ``bk_ingress_reset_books_device``), with the same ``mask`` / ``seeds`` / ``sync``: a masked book (market) also gets
+        back its order records, its agents' held ids and its members' lists and state, and its queue is emptied - what
+        was submitted or queued by an update since the last ``step`` is dropped, so reset right after ``step``.  Refused
+        after any ``set_*agents*`` call since the save: ``save_ingress_snapshot`` again."""
+        self._masked_reset(self._L.bk_ingress_reset_books_device, self._L.bk_ingress_reset_books, mask, seeds, slot, sync)
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):
@@ -1028,6 +1054,11 @@ class ManyMarketEnv(ManyBookEnv):
         """``reset_books`` spelt by market: ``mask`` / ``seeds`` hold one element per market, and every book of a masked
         market goes back to the snapshot (with ``seeds``, all of them on the market's new RNG stream)."""
         self.reset_books(mask, seeds, slot, sync)
+
+    def reset_ingress_markets(self, mask, seeds=None, slot: int = 0, sync: bool = True):
+        """``reset_ingress_books`` spelt by market (an env with the device ingress): a masked market's books, and its
+        queue, go back."""
+        self.reset_ingress_books(mask, seeds, slot, sync)
 
     def place_order(self, market: int, asset: int, bid: bool, vol: int, trader_id: int, price: Optional[int] = None):
         """``MarketEnv::place_order(asset, side, vol, trader_id, price)`` (market_env.rs:163-176) -> per-asset order id"""

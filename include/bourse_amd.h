@@ -475,8 +475,9 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes);
  * The unit of a reset is a book, or with assets > 1 a market (its books share one RNG stream): n_units = n_books /
  * assets.  Every refusal below is BK_INVALID_ARGUMENT, is checked before anything is enqueued and leaves the env unchanged:
  * slot >= BK_MAX_SNAPSHOTS, and - the conditions bk_checkpoint_save refuses on, for the same reasons - an env with the
- * device ingress (its queues, order records and held ids would have to be rewound as well), an env with the agents'
- * order log (the log would keep the abandoned run's orders), an env that holds host-placed orders. */
+ * device ingress (its queues, order records and held ids have to be rewound as well: it has entries of its own,
+ * bk_ingress_snapshot_save / bk_ingress_reset_books* below), an env with the agents' order log (the log would keep the
+ * abandoned run's orders), an env that holds host-placed orders. */
 #define BK_MAX_SNAPSHOTS 4
 /* Device bytes one slot costs: n_books * (pool block + level-2 row) * 4.  (No counterpart in the reference.) */
 uint64_t bk_snapshot_bytes(const bk_env* env);
@@ -503,6 +504,39 @@ int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, c
  * copied on the env's stream, and the copy is waited for - the caller's arrays are free on return; the reset itself
  * stays asynchronous.  (No counterpart in the reference.) */
 int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host);
+
+/* ------------------------------------------------------ per-book reset of a device-ingress env */
+/* The same for an env with the device ingress (bk_device_ingress_enable), which the entries above refuse: besides the state
+ * block and the level-2 record of its books, a reset unit (book, or market) gets back everything else such an env keeps for
+ * it - the order records (bk_get_orders / bk_order_status) of the ids it had handed out at the save, the held ids of
+ * bk_update_agents, the lists, lengths, momentum state and flags of bk_update_members - and its queue is EMPTIED: what was
+ * submitted or queued by an update for the unit since the last step is dropped, and the ids and statuses already written
+ * to the caller's out_ids / status arrays for those instructions are void.  The natural place for a reset is right after
+ * a step.  The slots are BK_MAX_SNAPSHOTS of their own, apart from bk_snapshot_save's.  Fix-ups and what is not rewound
+ * (bk_steps_done, the history ring, the other units) are bk_reset_books_device's.  Every refusal is BK_INVALID_ARGUMENT,
+ * checked before anything is enqueued, and leaves the env unchanged: null env, slot >= BK_MAX_SNAPSHOTS, an env without
+ * the device ingress (its entries are bk_snapshot_save / bk_reset_books).  Checkpoints and bk_run of a device-ingress env
+ * stay refused. */
+/* Device-to-device copy of the above into `slot` (overwritten by a later save; its record arrays grow if the books have
+ * handed out more ids since).  If no bk_update_agents / bk_update_members has run since the agents were installed, the
+ * slot records that they hold nothing yet, and a reset puts them back there.  MAY SYNCHRONISE: it waits for the env's
+ * stream and reads one word back to size the slot.  (No counterpart in the reference.) */
+int bk_ingress_snapshot_save(bk_env* env, uint32_t slot);
+/* Frees the slot's memory (waits for the env's stream first); dropping an empty slot is not an error.  (No counterpart
+ * in the reference.) */
+int bk_ingress_snapshot_drop(bk_env* env, uint32_t slot);
+/* Device bytes the slot holds; 0 for an empty slot.  (No counterpart in the reference.) */
+uint64_t bk_ingress_snapshot_bytes(const bk_env* env, uint32_t slot);
+/* Units u with mask_dev[u] != 0 return to their state in `slot`; mask_dev [n_units] bytes and seeds_dev [n_units] u64
+ * (nullable) are DEVICE memory written on the env's stream.  HOLDS NO HOST SYNCHRONISATION: launches on the env's stream
+ * only - no stream wait, no host read, no allocation - and an all-zero mask costs a time that does not depend on how many
+ * orders the slot holds.  Further refusals: empty slot, null mask, a slot saved with another agent set or shape ("install
+ * the same agents first"), and ANY bk_set_*agents* call since the save, the same agents included (it makes the next update
+ * start from empty hands, which would wipe what a reset restored: save again).  (No counterpart in the reference.) */
+int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev);
+/* The same from HOST arrays, staged and waited for as bk_reset_books stages them; the reset itself stays asynchronous.
+ * (No counterpart in the reference.) */
+int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host);
 
 #ifdef __cplusplus
 }

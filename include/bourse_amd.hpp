@@ -224,6 +224,14 @@ class ManyEnv {
     if (mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_reset_books(h_, slot, mask.data(), seeds));
   }
+  // the same for an env with the device ingress (bk_ingress_snapshot_save / bk_ingress_reset_books: order records,
+  // held ids and members' lists rewind too, the reset books' queues are emptied); the reference has no counterpart
+  void save_ingress_snapshot(uint32_t slot = 0) { check(bk_ingress_snapshot_save(h_, slot)); }
+  void drop_ingress_snapshot(uint32_t slot = 0) { check(bk_ingress_snapshot_drop(h_, slot)); }
+  void reset_ingress_books(const std::vector<uint8_t>& mask, const uint64_t* seeds = nullptr, uint32_t slot = 0) {
+    if (mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_ingress_reset_books(h_, slot, mask.data(), seeds));
+  }
   bk_env* handle() { return h_; }
 
  private:
