@@ -16,6 +16,7 @@ BK_OK, BK_PRICE, BK_UNKNOWN_ORDER, BK_CAPACITY, BK_STEP_SIZE, BK_INVALID, BK_HIP
 FLAG_POOL_OVERFLOW, FLAG_TRADE_OVERFLOW, FLAG_STEP_SIZE, FLAG_ORDER_LOG_FULL = 1, 2, 4, 8
 FLAG_UNKNOWN_ORDER, FLAG_HIST_OVERFLOW, FLAG_PRICE_TICK, FLAG_EVENT_OVERFLOW = 16, 32, 64, 128
 FLAG_DECODE_LOOKAHEAD = 256
+FLAG_ACCOUNTS_INEXACT = 512
 ACTION_MODIFY = 0x80000003  # BK_ACTION_MODIFY: the one extension of submit_instructions' action codes (0 / 1 / 2)
 FLAG_NAMES = {1: "POOL_OVERFLOW (live-order pool full: a resting order was dropped)",
               2: "TRADE_OVERFLOW (trade_capacity exceeded: records dropped, counts exact)",
@@ -24,8 +25,12 @@ FLAG_NAMES = {1: "POOL_OVERFLOW (live-order pool full: a resting order was dropp
               16: "UNKNOWN_ORDER", 32: "HIST_OVERFLOW",
               64: "PRICE_TICK (a Noise/Momentum limit price clamped to u32::MAX was not a tick multiple)",
               128: "EVENT_OVERFLOW (a market queued more events in one step than its shared list holds)",
-              256: "DECODE_LOOKAHEAD (a ziggurat rejection loop outran the members' decode's 128-draw look-ahead)"}
-CAPACITY_FLAGS = FLAG_POOL_OVERFLOW | FLAG_TRADE_OVERFLOW | FLAG_ORDER_LOG_FULL | FLAG_EVENT_OVERFLOW
+              256: "DECODE_LOOKAHEAD (a ziggurat rejection loop outran the members' decode's 128-draw look-ahead)",
+              512: "ACCOUNTS_INEXACT (a trade record could not be folded into the trader accounts: dropped beyond "
+                   "trade_capacity, or an order id beyond max_orders)"}
+# (ACCOUNTS_INEXACT comes of the same two capacities as TRADE_OVERFLOW and ORDER_LOG_FULL)
+CAPACITY_FLAGS = (FLAG_POOL_OVERFLOW | FLAG_TRADE_OVERFLOW | FLAG_ORDER_LOG_FULL | FLAG_EVENT_OVERFLOW |
+                  FLAG_ACCOUNTS_INEXACT)
 
 
 class BourseError(RuntimeError):
@@ -86,6 +91,11 @@ ORDER_DTYPE = np.dtype(
     {"names": ["side", "status", "arr_time", "end_time", "vol", "start_vol", "price", "trader_id", "order_id"],
      "formats": ["u1", "u1", "<u8", "<u8", "<u4", "<u4", "<u4", "<u4", "<u8"],
      "offsets": [0, 1, 8, 16, 24, 28, 32, 36, 40], "itemsize": 48})
+
+# bk_account: one trader's row of the accounts table (ManyBookEnv.accounts)
+ACCOUNT_DTYPE = np.dtype(
+    {"names": ["position", "cash", "volume", "fills"], "formats": ["<i8", "<i8", "<u8", "<u8"],
+     "offsets": [0, 8, 16, 24], "itemsize": 32})
 
 # bk_random_agents (RandomAgentsCfg) as a numpy structured dtype: the rows of ManyBookEnv.set_random_agents_per_book's table
 RANDOM_AGENTS_DTYPE = np.dtype(
@@ -195,6 +205,11 @@ SIGNATURES = {
     "bk_ingress_snapshot_bytes": (_u64, [_vp, _u32]),
     "bk_ingress_reset_books_device": (_i32, [_vp, _u32, _vp, _vp]),
     "bk_ingress_reset_books": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_accounts_enable": (_i32, [_vp, _u32, _i32]),
+    "bk_accounts_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_accounts": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_accounts_clear": (_i32, [_vp, _vp]),
+    "bk_accounts_clear_device": (_i32, [_vp, _vp]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "members_ingress.hpp"
 #include "book_reset.hpp"
 #include "ingress_reset.hpp"
+#include "accounts.hpp"
 
 using namespace bkd;
 
@@ -59,6 +60,9 @@ static_assert(sizeof(bk_config) == 72 && sizeof(bk_random_agents) == 28 && sizeo
                   sizeof(bk_order) == 48,
               "C ABI struct layout (mirrored by bourse_amd/_lib.py)");
 static_assert(sizeof(bk_agent_desc) == 104, "bk_agent_desc layout (mirrored by bourse_amd/_lib.py)");
+static_assert(sizeof(bk_account) == 32 && sizeof(bk_account) == 2 * sizeof(bk_u32x4) &&
+                  accounts::FLAG_ACCOUNTS_INEXACT == BK_FLAG_ACCOUNTS_INEXACT,
+              "bk_account layout / flag (accounts.hpp)");
 static_assert(sizeof(DevTrade) == 32 && sizeof(DevOrderLog) == 48 && sizeof(uint4) == 16, "device record layout");
 
 namespace {
@@ -155,6 +159,12 @@ struct bk_env {
   } isnaps[BK_MAX_SNAPSHOTS];
   DevBuf<uint32_t> reset_list;  // [n_units] the masked units of one ingress reset, then its counter (k_collect_units)
   int reset_blocks = 0;         // k_reset_records' fixed grid: 4 blocks of 4 waves per CU
+  // bk_accounts_enable: per-trader rows [n_books][acct_traders] of 32 B and the per-book cursors (accounts.hpp)
+  DevBuf<bk_u32x4> acct;
+  DevBuf<unsigned long long> acct_seen;
+  DevBuf<uint8_t> acct_mask;  // bk_accounts_clear: device staging of the host mask [n_books]
+  uint32_t acct_traders = 0;  // 0: no accounts
+  bool acct_consume = false;
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -1585,6 +1595,38 @@ int bk_submit_result(bk_env* env, uint64_t ticket, uint64_t* out_ids, uint32_t* 
 }
 
 // Env::step over the device-resident queues, asynchronous on the env's stream (bk_step = this + a wait)
+static void launch_accounts_fold(bk_env* env) {
+  accounts::FoldArgs g{};
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.trades = reinterpret_cast<const bk_u32x4*>(env->trades.p);
+  g.trade_cap = env->cfg.trade_capacity;
+  g.dorders = env->dorders.p;
+  g.max_orders = env->cfg.max_orders;
+  g.acct = env->acct.p;
+  g.n_traders = env->acct_traders;
+  g.seen = env->acct_seen.p;
+  g.consume = env->acct_consume ? 1u : 0u;
+  const uint32_t blocks = (g.n_books + accounts::FOLD_WAVES - 1) / accounts::FOLD_WAVES;
+  hipLaunchKernelGGL(accounts::k_fold, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
+}
+
+// rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
+static void launch_accounts_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M) {
+  accounts::ClearArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.acct = env->acct.p;
+  g.n_traders = env->acct_traders;
+  g.seen = env->acct_seen.p;
+  const uint32_t blocks = (g.n_books + accounts::FOLD_WAVES - 1) / accounts::FOLD_WAVES;
+  hipLaunchKernelGGL(accounts::k_clear, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
+}
+
 int bk_step_async(bk_env* env) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_step_async steps the device-resident queues: call bk_device_ingress_enable first");
@@ -1594,6 +1636,10 @@ int bk_step_async(bk_env* env) {
   // step has been on the host)
   const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, env->qcap); });
   if (rc != BK_OK) return rc;
+  if (env->acct_traders) {  // trader accounts: this step's new trade records, right behind the event kernel
+    launch_accounts_fold(env);
+    HIPCHK(hipGetLastError());
+  }
   HIPCHK(hipMemsetAsync(env->dqlen.p, 0, static_cast<size_t>(env->cfg.n_books / env->M) * 4, env->stream));
   env->steps_done += 1;
   env->ingest_epoch += 1;
@@ -2352,6 +2398,9 @@ int bk_get_order_keys(bk_env* env, uint32_t book, uint64_t first, uint64_t n, ui
 int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uint64_t n_orders, const bk_order* orders,
                  const uint32_t* key_price, const uint64_t* key_time, uint64_t n_trades, const bk_trade* trades) {
   if (int rc = check_book(env, book)) return rc;
+  if (env->acct_traders)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trader accounts (bk_accounts_enable) is not supported: "
+                                     "its trade records would have no order records to look the traders up in");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
   // (the agents' log holds what k_step_batch_log wrote for every id below the book's counter: a loaded book's orders
@@ -3156,6 +3205,10 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
   g.snap_lens = s.members_saved ? s.lens.p : nullptr;
   hipLaunchKernelGGL(reset::k_reset_records, dim3(env->reset_blocks), dim3(64 * reset::RECORD_WAVES), 0, env->stream, g);
   HIPCHK(hipGetLastError());
+  if (env->acct_traders) {  // trader accounts are not part of a snapshot: a reset book counts from its reset
+    launch_accounts_clear(env, mask_dev, env->M);
+    HIPCHK(hipGetLastError());
+  }
   env->ingest_epoch += 1;  // the readers' mirrors of the orders and the log fetch from the device again
   return BK_OK;
 }
@@ -3170,6 +3223,84 @@ int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host,
   if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
   HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
   return bk_ingress_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
+}
+
+// ------------------------------------------------------------------ trader accounts of a device-ingress env
+// No counterpart in the reference.  acct[n_books][n_traders] rows {position, cash, volume, fills} folded from each step's
+// new trade records by accounts::k_fold behind the step's event kernel (bk_step_async); accounts.hpp, DESIGN.md 2.16.
+int bk_accounts_enable(bk_env* env, uint32_t n_traders, int consume_trades) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "trader accounts serve an env with the device ingress (bk_device_ingress_enable): only "
+                                     "there are the orders' trader ids in device memory");
+  if (env->acct_traders) return fail(BK_INVALID_ARGUMENT, "trader accounts are already enabled on this env");
+  if (n_traders == 0 || n_traders > accounts::MAX_TRADERS)
+    return fail(BK_INVALID_ARGUMENT, "n_traders must be in 1..65536");
+  if (env->cfg.max_orders == 0)
+    return fail(BK_INVALID_ARGUMENT, "trader accounts need max_orders > 0: a trade record's traders are looked up in the "
+                                     "order records");
+  if (env->steps_done != 0 || env->ingest_epoch != 0)
+    return fail(BK_INVALID_ARGUMENT, "enable trader accounts before the first instruction, update or step");
+  for (const bk_env::IngressSnapshot& s : env->isnaps)
+    if (s.used) return fail(BK_INVALID_ARGUMENT, "enable trader accounts while no ingress snapshot slot is held");
+  if (int rc = use_device(env)) return rc;
+  const size_t B = env->cfg.n_books;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<unsigned long long> seen;
+  HIPCHK(rows.alloc(B * n_traders * 2));
+  HIPCHK(seen.alloc(B));
+  std::swap(env->acct.p, rows.p), std::swap(env->acct.n, rows.n);
+  std::swap(env->acct_seen.p, seen.p), std::swap(env->acct_seen.n, seen.n);
+  env->acct_traders = n_traders;
+  env->acct_consume = consume_trades != 0;
+  launch_accounts_clear(env, nullptr, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int accounts_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->acct_traders) return fail(BK_INVALID_ARGUMENT, "this env has no trader accounts: call bk_accounts_enable first");
+  return BK_OK;
+}
+
+int bk_accounts_device_ptr(bk_env* env, void** out) {
+  if (int rc = accounts_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->acct.p;
+  return BK_OK;
+}
+
+int bk_get_accounts(bk_env* env, uint32_t first_book, uint32_t n_books, bk_account* out) {
+  if (int rc = accounts_ok(env)) return rc;
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  if (n_books)
+    HIPCHK(hipMemcpy(out, env->acct.p + static_cast<size_t>(first_book) * env->acct_traders * 2,
+                     static_cast<size_t>(n_books) * env->acct_traders * sizeof(bk_account), hipMemcpyDeviceToHost));
+  return BK_OK;
+}
+
+int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = accounts_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  launch_accounts_clear(env, mask_dev, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_accounts_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = accounts_ok(env)) return rc;
+  if (!mask_host) return bk_accounts_clear_device(env, nullptr);
+  if (int rc = use_device(env)) return rc;
+  const size_t B = env->cfg.n_books;
+  if (!env->acct_mask.p) HIPCHK(env->acct_mask.alloc(B));
+  HIPCHK(hipMemcpyAsync(env->acct_mask.p, mask_host, B, hipMemcpyHostToDevice, env->stream));
+  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's array is free from here on
+  return bk_accounts_clear_device(env, env->acct_mask.p);
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

@@ -139,6 +139,7 @@ class ManyBookEnv:
         self.step_size, self.start_time = int(step_size), int(start_time)
         check(self._L.bk_env_create(C.byref(cfg), C.byref(self._h)))
         self.width = int(self._L.bk_l2_width(self._h))
+        self._stream = None if stream is None else int(stream)  # (None: the env's own stream, which Python never sees)
         if stream is not None:
             check(self._L.bk_env_set_stream(self._h, C.c_void_p(stream)))
         if tick_sizes is not None:
@@ -1021,6 +1022,88 @@ class ManyBookEnv:
         was submitted or queued by an update since the last ``step`` is dropped, so reset right after ``step``.  Refused
         after any ``set_*agents*`` call since the save: ``save_ingress_snapshot`` again."""
         self._masked_reset(self._L.bk_ingress_reset_books_device, self._L.bk_ingress_reset_books, mask, seeds, slot, sync)
+
+    # ------------------------------------------------------------ trader accounts of an env with the device ingress
+    ACCOUNT_DTYPE = _lib.ACCOUNT_DTYPE
+
+    def enable_accounts(self, n_traders: int, consume_trades: bool = False):
+        """``bk_accounts_enable``: keep ``position`` / ``cash`` / ``volume`` / ``fills`` of traders ``0 .. n_traders - 1``
+        per book in device memory, folded from every step's new trade records on the env's stream with no host in the
+        loop (trader ids >= ``n_traders`` - background members, say - are left out).  Call after
+        ``enable_device_ingress`` and before the first instruction, update or step.  ``consume_trades=True`` marks the
+        trade records consumed once folded (as ``clear_trades``), so ``trade_capacity`` only has to hold one step's trades.
+        A record that could not be folded sets ``FLAG_ACCOUNTS_INEXACT`` on its book.  The reference has no counterpart."""
+        if not 0 <= int(n_traders) <= 0xFFFFFFFF:
+            raise ValueError("n_traders out of range")
+        check(self._L.bk_accounts_enable(self._h, int(n_traders), int(bool(consume_trades))))
+        self._n_traders = int(n_traders)
+
+    def _accounts_traders(self) -> int:
+        n = getattr(self, "_n_traders", 0)
+        if not n:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no trader accounts: call enable_accounts first")
+        return n
+
+    def accounts(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
+        shape ``[n, n_traders]`` (``ACCOUNT_DTYPE``).  Waits for the env's stream."""
+        nt = self._accounts_traders()
+        n = self.n_books - int(first_book) if n_books is None else int(n_books)
+        if int(first_book) < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        out = np.zeros((n, nt), dtype=_lib.ACCOUNT_DTYPE)
+        check(self._L.bk_get_accounts(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def accounts_device_ptr(self) -> int:
+        """Device address of the table, ``bk_account[n_books][n_traders]`` (for on-device consumers)."""
+        out = C.c_void_p()
+        check(self._L.bk_accounts_device_ptr(self._h, C.byref(out)))
+        return int(out.value)
+
+    def accounts_view(self) -> "AccountsView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, n_traders, 4)``, the
+        last axis ``position, cash, volume, fills`` (the two unsigned words read as int64: the same bits).
+        ``torch.as_tensor(env.accounts_view(), device="cuda")`` is a zero-copy tensor that every later step updates; it is
+        written on the env's stream, so read it there (or after ``sync()``)."""
+        return AccountsView(self, self.accounts_device_ptr(), (self.n_books, self._accounts_traders(), 4), self._stream)
+
+    def clear_accounts(self, mask=None, sync: bool = True):
+        """Zero the rows of the books ``b`` with ``mask[b]`` set (``None``: every book); they count from the book's
+        current trade count on.  ``mask``: bool / uint8, one per BOOK - a host array (``bk_accounts_clear``), or a torch
+        CUDA tensor / ``__cuda_array_interface__`` object written on the env's stream (``bk_accounts_clear_device``: no
+        host synchronisation).  ``reset_ingress_books`` clears the books it resets by itself.  ``sync`` waits for it."""
+        self._accounts_traders()
+        if mask is None:
+            check(self._L.bk_accounts_clear_device(self._h, None))
+        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
+            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
+            if n != self.n_books:
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_accounts_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError("mask: a bool or uint8 array is needed")
+            m = m.astype(np.uint8, copy=False)
+            if m.shape != (self.n_books,):
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_accounts_clear(self._h, m.ctypes.data_as(C.c_void_p)))
+        if sync:
+            self.sync()
+
+
+class AccountsView:
+    """``ManyBookEnv.accounts_view()``: the accounts table where it lives, for ``torch.as_tensor(view, device="cuda")``,
+    cupy and anything else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
+
+    def __init__(self, env, ptr: int, shape, stream: Optional[int]):
+        self._env = env
+        # version 3 of the interface: `stream` is the stream the data is written on - None when unknown (an env on its own
+        # stream), 1 for the legacy default stream (whose handle 0 the interface disallows), else the handle
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": "<i8", "data": (int(ptr), False),
+                                         "version": 3, "strides": None,
+                                         "stream": None if stream is None else (stream if stream != 0 else 1)}
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):

@@ -49,6 +49,8 @@ enum bk_status {
                                      * longer than its 128-draw look-ahead (p < 2^-90): results of that book are suspect */
 #define BK_FLAG_EVENT_OVERFLOW 128u /* a MARKET with Noise/Momentum members queued more than max_live_orders events in one
                                      * step (its books share one queue of that size): the excess events were dropped */
+#define BK_FLAG_ACCOUNTS_INEXACT 512u /* trader accounts (bk_accounts_enable): a trade record of this book could not be folded
+                                     * into the rows - dropped beyond trade_capacity, or with an order id >= max_orders */
 
 typedef struct bk_env bk_env;
 
@@ -537,6 +539,61 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
 /* The same from HOST arrays, staged and waited for as bk_reset_books stages them; the reset itself stays asynchronous.
  * (No counterpart in the reference.) */
 int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host);
+
+/* ------------------------------------------------------ trader accounts of a device-ingress env */
+/* An opt-in table acct[n_books][n_traders] in DEVICE memory: what each trader bought and sold in each book, folded from
+ * the book's new trade records on the env's stream right behind every step's event kernel, with no host synchronisation
+ * anywhere on that path (bourse_amd/csrc/accounts.hpp).  A strategy that submits from device memory reads
+ * its own fills, inventory and cash there instead of joining bk_get_trades with bk_get_orders on the host.  The reference
+ * has no counterpart for any of these entries.
+ *
+ * Which fills a book's rows record.  The buyer of a trade record is the PASSIVE order's trader when side_is_bid == 1,
+ * otherwise the ACTIVE order's trader; the other trader is the seller.  A trader id >= n_traders is skipped without a flag:
+ * give background members (bk_set_agents*, bk_set_random_agents*) an agent_id_start above n_traders to keep them out.
+ * Markets need nothing special: a book of a market is a book, and the rows are per book (market * assets + asset).
+ *
+ * Arithmetic.  All of it is modulo 2^64, two's complement; vol * price is the full 32 x 32 -> 64-bit product. */
+typedef struct bk_account { /* 32 B, all little-endian 64-bit words */
+  int64_t position; /* + vol for every fill as buyer, - vol as seller */
+  int64_t cash;     /* - vol * price as buyer, + vol * price as seller (price = the trade record's: the passive order's) */
+  uint64_t volume;  /* sum of vol over the trader's fills, either side */
+  uint64_t fills;   /* trade records the trader took part in (a self-trade counts twice) */
+} bk_account;
+/* Enabling.  Accepted only on an env with the device ingress (bk_device_ingress_enable), with max_orders > 0 (the traders
+ * of a record's orders are looked up in the order records), before the first instruction, update or step, and while no
+ * ingress snapshot slot is held.  Refuses n_traders == 0, n_traders > 65536 and a second call.  A refusal returns
+ * BK_INVALID_ARGUMENT, leaves the env unchanged and puts the reason in bk_last_error().
+ *
+ * The fold and its cursor.  The fold runs after every bk_step_async / bk_step of such an env.  Each book has a cursor
+ * (a device array of its own, acct_seen[n_books]; the state block's layout is unchanged) counting the trades already
+ * folded.  A record that cannot be folded - it was dropped beyond trade_capacity, or one of its order ids is >= max_orders
+ * - sets the sticky flag BK_FLAG_ACCOUNTS_INEXACT on that book and the cursor moves past it: inexact rows are flagged,
+ * never silent.  Other books are unaffected.
+ *
+ * consume_trades.  With consume_trades = 1 the fold ends by setting the book's first retained trade to its trade count
+ * (bk_trade_count: first_retained == total), exactly as bk_clear_trades does: trade_capacity then only has to hold ONE
+ * step's trades.  With consume_trades = 0 the host's trade readers and bk_trades_compact see what they see today (the
+ * fold has run on the stream before any of them can mark a step's records consumed).
+ *
+ * bk_load_book is refused on an env with accounts.  Behaviour of an env without accounts does not change.
+ * (No counterpart in the reference.) */
+int bk_accounts_enable(bk_env* env, uint32_t n_traders, int consume_trades);
+/* Device pointer of the table, bk_account[n_books][n_traders], for on-device consumers; valid for the env's life, written
+ * on the env's stream.  BK_INVALID_ARGUMENT without accounts.  (No counterpart in the reference.) */
+int bk_accounts_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory, n_books * n_traders records.  Waits for the env's
+ * stream.  (No counterpart in the reference.) */
+int bk_get_accounts(bk_env* env, uint32_t first_book, uint32_t n_books, bk_account* out);
+/* Clearing.  Zeroes the rows of the books b with mask[b] != 0 (mask [n_books] bytes; NULL = every book) and sets their
+ * cursor to the book's current trade count: a cleared book counts from here.  bk_ingress_reset_books* does the same for
+ * the books it resets (every book of a reset market), after its own kernels, on the same stream, using the same device
+ * mask: accounts are not part of a snapshot, and a reset book counts from its reset, which is what an episode wants.
+ * From a HOST mask: staged on the env's stream and waited for, the clear itself stays asynchronous.  (No counterpart in
+ * the reference.) */
+int bk_accounts_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: one launch
+ * on the env's stream.  (No counterpart in the reference.) */
+int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev);
 
 #ifdef __cplusplus
 }

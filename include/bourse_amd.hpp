@@ -232,11 +232,35 @@ class ManyEnv {
     if (mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_ingress_reset_books(h_, slot, mask.data(), seeds));
   }
+  // trader accounts of an env with the device ingress (bk_accounts_enable): position / cash / volume / fills of traders
+  // 0 .. n_traders - 1 per book, folded on the device behind every step; the reference has no counterpart
+  void enable_accounts(uint32_t n_traders, bool consume_trades = false) {
+    check(bk_accounts_enable(h_, n_traders, consume_trades ? 1 : 0));
+    n_traders_ = n_traders;
+  }
+  // rows of books [first_book, first_book + n_books), n_traders each (waits for the env's stream)
+  std::vector<bk_account> accounts(uint32_t first_book, uint32_t n_books) {
+    std::vector<bk_account> rows(static_cast<size_t>(n_books) * n_traders_);
+    check(bk_get_accounts(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<bk_account> accounts() { return accounts(0, n_books_); }
+  // the table in device memory, bk_account[n_books][n_traders]
+  bk_account* accounts_device_ptr() {
+    void* p = nullptr;
+    check(bk_accounts_device_ptr(h_, &p));
+    return static_cast<bk_account*>(p);
+  }
+  // zero the rows of the books with mask[b] != 0 (an empty mask: every book); they count from here
+  void clear_accounts(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_accounts_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   bk_env* handle() { return h_; }
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
