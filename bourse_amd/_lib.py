@@ -97,6 +97,14 @@ ACCOUNT_DTYPE = np.dtype(
     {"names": ["position", "cash", "volume", "fills"], "formats": ["<i8", "<i8", "<u8", "<u8"],
      "offsets": [0, 8, 16, 24], "itemsize": 32})
 
+# bk_open_summary / bk_open_order: one trader's rows of the open-order tables (ManyBookEnv.open_orders)
+OPEN_SUMMARY_DTYPE = np.dtype(
+    {"names": ["bid_vol", "ask_vol", "n_bid", "n_ask", "best_bid", "best_ask"], "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
+     "offsets": [0, 8, 16, 20, 24, 28], "itemsize": 32})
+OPEN_ORDER_DTYPE = np.dtype(
+    {"names": ["order_id", "price", "vol", "side_is_bid"], "formats": ["<u4", "<u4", "<u4", "<u4"],
+     "offsets": [0, 4, 8, 12], "itemsize": 16})
+
 # bk_random_agents (RandomAgentsCfg) as a numpy structured dtype: the rows of ManyBookEnv.set_random_agents_per_book's table
 RANDOM_AGENTS_DTYPE = np.dtype(
     {"names": ["n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate"],
@@ -210,6 +218,10 @@ SIGNATURES = {
     "bk_get_accounts": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_accounts_clear": (_i32, [_vp, _vp]),
     "bk_accounts_clear_device": (_i32, [_vp, _vp]),
+    "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
+    "bk_open_orders_refresh": (_i32, [_vp]),
+    "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "bk_get_open_orders": (_i32, [_vp, _u32, _u32, _vp, _vp]),
 }
 
 _lib = None

@@ -51,6 +51,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "book_reset.hpp"
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
+#include "open_orders.hpp"
 
 using namespace bkd;
 
@@ -63,6 +64,10 @@ static_assert(sizeof(bk_agent_desc) == 104, "bk_agent_desc layout (mirrored by b
 static_assert(sizeof(bk_account) == 32 && sizeof(bk_account) == 2 * sizeof(bk_u32x4) &&
                   accounts::FLAG_ACCOUNTS_INEXACT == BK_FLAG_ACCOUNTS_INEXACT,
               "bk_account layout / flag (accounts.hpp)");
+static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
+                  sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
+                  sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
+              "bk_open_summary / bk_open_order layout (open_orders.hpp)");
 static_assert(sizeof(DevTrade) == 32 && sizeof(DevOrderLog) == 48 && sizeof(uint4) == 16, "device record layout");
 
 namespace {
@@ -165,6 +170,10 @@ struct bk_env {
   DevBuf<uint8_t> acct_mask;  // bk_accounts_clear: device staging of the host mask [n_books]
   uint32_t acct_traders = 0;  // 0: no accounts
   bool acct_consume = false;
+  // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
+  DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
+  DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
+  uint32_t open_traders = 0, open_depth = 0;  // open_traders == 0: no view
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -1627,6 +1636,29 @@ static void launch_accounts_clear(bk_env* env, const uint8_t* mask_dev, uint32_t
   hipLaunchKernelGGL(accounts::k_clear, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
 }
 
+// the open-order rows of the masked books (one mask byte per M books; nullptr: every book) from their pools as they are at
+// this point of the env's stream: one launch, no allocation, no stream wait, no host read
+static void launch_open_orders_refresh(bk_env* env, const uint8_t* mask_dev, uint32_t M) {
+  open_orders::RefreshArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.dorders = reinterpret_cast<const uint32_t*>(env->dorders.p);
+  g.max_orders = env->cfg.max_orders;
+  g.summary = env->open_summary.p;
+  g.entries = env->open_entries.p;
+  g.n_traders = env->open_traders;
+  g.depth = env->open_depth;
+  g.depth_inv = g.depth ? ((1u << 24) + g.depth - 1u) / g.depth : 0u;
+  const uint32_t blocks = (g.n_books + open_orders::REFRESH_WAVES - 1) / open_orders::REFRESH_WAVES;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(open_orders::k_refresh<decltype(r)::value>, dim3(blocks), dim3(64 * open_orders::REFRESH_WAVES), 0,
+                       env->stream, g);
+  });
+}
+
 int bk_step_async(bk_env* env) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_step_async steps the device-resident queues: call bk_device_ingress_enable first");
@@ -1638,6 +1670,10 @@ int bk_step_async(bk_env* env) {
   if (rc != BK_OK) return rc;
   if (env->acct_traders) {  // trader accounts: this step's new trade records, right behind the event kernel
     launch_accounts_fold(env);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->open_traders) {  // open orders: the pools as this step left them
+    launch_open_orders_refresh(env, nullptr, 1);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemsetAsync(env->dqlen.p, 0, static_cast<size_t>(env->cfg.n_books / env->M) * 4, env->stream));
@@ -3209,6 +3245,10 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
     launch_accounts_clear(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
   }
+  if (env->open_traders) {  // the reset books show the snapshot's resting orders before their next step
+    launch_open_orders_refresh(env, mask_dev, env->M);
+    HIPCHK(hipGetLastError());
+  }
   env->ingest_epoch += 1;  // the readers' mirrors of the orders and the log fetch from the device again
   return BK_OK;
 }
@@ -3301,6 +3341,75 @@ int bk_accounts_clear(bk_env* env, const uint8_t* mask_host) {
   HIPCHK(hipMemcpyAsync(env->acct_mask.p, mask_host, B, hipMemcpyHostToDevice, env->stream));
   HIPCHK(hipStreamSynchronize(env->stream));  // the caller's array is free from here on
   return bk_accounts_clear_device(env, env->acct_mask.p);
+}
+
+// ------------------------------------------------------------------ open orders of a device-ingress env
+// No counterpart in the reference.  summary[n_books][n_traders] and entries[n_books][n_traders][depth]: every trader's resting
+// orders per book, recomputed from the pool by open_orders::k_refresh behind every step's event kernel (bk_step_async) and
+// behind bk_ingress_reset_books*; open_orders.hpp, DESIGN.md 2.17.
+int bk_open_orders_enable(bk_env* env, uint32_t n_traders, uint32_t depth) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "the open-order view serves an env with the device ingress (bk_device_ingress_enable): "
+                                     "only there are the orders' trader ids in device memory");
+  if (env->open_traders) return fail(BK_INVALID_ARGUMENT, "the open-order view is already enabled on this env");
+  if (n_traders == 0 || n_traders > open_orders::MAX_TRADERS)
+    return fail(BK_INVALID_ARGUMENT, "n_traders must be in 1..65536");
+  if (depth > open_orders::MAX_DEPTH) return fail(BK_INVALID_ARGUMENT, "depth must be in 0..64 entries per trader and book");
+  if (env->cfg.max_orders == 0)
+    return fail(BK_INVALID_ARGUMENT, "the open-order view needs max_orders > 0: a resting order's trader is looked up in the "
+                                     "order records");
+  if (int rc = use_device(env)) return rc;
+  const size_t rows = static_cast<size_t>(env->cfg.n_books) * n_traders;
+  DevBuf<bk_u32x4> summary, entries;
+  HIPCHK(summary.alloc(rows * 2));
+  HIPCHK(entries.alloc(rows * depth));
+  std::swap(env->open_summary.p, summary.p), std::swap(env->open_summary.n, summary.n);
+  std::swap(env->open_entries.p, entries.p), std::swap(env->open_entries.n, entries.n);
+  env->open_traders = n_traders;
+  env->open_depth = depth;
+  launch_open_orders_refresh(env, nullptr, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int open_orders_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->open_traders)
+    return fail(BK_INVALID_ARGUMENT, "this env has no open-order view: call bk_open_orders_enable first");
+  return BK_OK;
+}
+
+int bk_open_orders_refresh(bk_env* env) {
+  if (int rc = open_orders_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  launch_open_orders_refresh(env, nullptr, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_open_orders_device_ptrs(bk_env* env, void** summary, void** entries) {
+  if (int rc = open_orders_ok(env)) return rc;
+  if (!summary || !entries) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *summary = env->open_summary.p;
+  *entries = env->open_entries.p;  // (nullptr with depth == 0)
+  return BK_OK;
+}
+
+int bk_get_open_orders(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_summary* summary_out,
+                       bk_open_order* entries_out) {
+  if (int rc = open_orders_ok(env)) return rc;
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (n_books && !summary_out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  const size_t first = static_cast<size_t>(first_book) * env->open_traders, rows = static_cast<size_t>(n_books) * env->open_traders;
+  if (rows) HIPCHK(hipMemcpy(summary_out, env->open_summary.p + first * 2, rows * sizeof(bk_open_summary), hipMemcpyDeviceToHost));
+  if (rows && entries_out && env->open_depth)
+    HIPCHK(hipMemcpy(entries_out, env->open_entries.p + first * env->open_depth, rows * env->open_depth * sizeof(bk_open_order),
+                     hipMemcpyDeviceToHost));
+  return BK_OK;
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

@@ -1092,6 +1092,85 @@ class ManyBookEnv:
         if sync:
             self.sync()
 
+    # ------------------------------------------------------------ open orders of an env with the device ingress
+    OPEN_SUMMARY_DTYPE = _lib.OPEN_SUMMARY_DTYPE
+    OPEN_ORDER_DTYPE = _lib.OPEN_ORDER_DTYPE
+
+    def enable_open_orders(self, n_traders: int, depth: int = 8):
+        """``bk_open_orders_enable``: keep, per book and for traders ``0 .. n_traders - 1``, a summary row (resting volume
+        and order count per side, own best bid and ask) and the ``depth`` oldest resting orders (id, price, remaining
+        volume, side) in device memory, recomputed from the pool on the env's stream behind every step and every
+        ``reset_ingress_books`` with no host in the loop (trader ids >= ``n_traders`` - background members, say - are left
+        out).  Call at any time after ``enable_device_ingress``; ``depth=0`` keeps the summary rows only.  The reference has
+        no counterpart."""
+        if not 0 <= int(n_traders) <= 0xFFFFFFFF or not 0 <= int(depth) <= 0xFFFFFFFF:
+            raise ValueError("n_traders / depth out of range")
+        check(self._L.bk_open_orders_enable(self._h, int(n_traders), int(depth)))
+        self._open_shape = (int(n_traders), int(depth))
+
+    def _open_orders_shape(self):
+        shape = getattr(self, "_open_shape", None)
+        if shape is None:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no open-order view: call enable_open_orders first")
+        return shape
+
+    def refresh_open_orders(self):
+        """``bk_open_orders_refresh``: recompute every book's rows now (asynchronous on the env's stream), for callers
+        that changed a pool outside a step."""
+        self._open_orders_shape()
+        check(self._L.bk_open_orders_refresh(self._h))
+
+    def open_orders(self, first_book: int = 0, n_books: Optional[int] = None):
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as of the last refresh:
+        ``(summary[n, n_traders]`` of ``OPEN_SUMMARY_DTYPE``, ``entries[n, n_traders, depth]`` of ``OPEN_ORDER_DTYPE``
+        or ``None`` with ``depth == 0)``.  A trader's entries are its resting orders in ascending order id; unused slots
+        hold ``order_id == 0xFFFFFFFF``.  Waits for the env's stream."""
+        nt, depth = self._open_orders_shape()
+        n = self.n_books - int(first_book) if n_books is None else int(n_books)
+        if int(first_book) < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        summary = np.zeros((n, nt), dtype=_lib.OPEN_SUMMARY_DTYPE)
+        entries = np.zeros((n, nt, depth), dtype=_lib.OPEN_ORDER_DTYPE) if depth else None
+        check(self._L.bk_get_open_orders(self._h, int(first_book), n, summary.ctypes.data_as(C.c_void_p),
+                                         entries.ctypes.data_as(C.c_void_p) if depth else None))
+        return summary, entries
+
+    def open_orders_device_ptrs(self):
+        """Device addresses ``(summary, entries)`` of ``bk_open_summary[n_books][n_traders]`` and
+        ``bk_open_order[n_books][n_traders][depth]`` (``entries`` is ``None`` with ``depth == 0``)."""
+        summary, entries = C.c_void_p(), C.c_void_p()
+        check(self._L.bk_open_orders_device_ptrs(self._h, C.byref(summary), C.byref(entries)))
+        return int(summary.value), (int(entries.value) if entries.value else None)
+
+    def open_orders_views(self):
+        """The two tables in place as objects with ``__cuda_array_interface__`` (``torch.as_tensor(view, device="cuda")``
+        is a zero-copy tensor that every later step updates; written on the env's stream, so read it there or after
+        ``sync()``): ``(summary_view, entries_view)``, the second ``None`` with ``depth == 0``.
+
+        ``summary_view``: int64, shape ``(n_books, n_traders, 4)``, the last axis ``bid_vol, ask_vol, counts, best`` (the
+        unsigned words read as int64: the same bits).  The last two words pack two ``u32`` each, the first in the low
+        half: ``n_bid = counts & 0xFFFFFFFF``, ``n_ask = counts >> 32``, ``best_bid = best & 0xFFFFFFFF``,
+        ``best_ask = (best >> 32) & 0xFFFFFFFF``.
+
+        ``entries_view``: int32, shape ``(n_books, n_traders, depth, 4)``, the last axis ``order_id, price, vol,
+        side_is_bid`` (the ``u32`` words read as int32: the same bits; an unused slot's ``order_id`` reads -1)."""
+        nt, depth = self._open_orders_shape()
+        summary, entries = self.open_orders_device_ptrs()
+        return (OpenOrdersView(self, summary, (self.n_books, nt, 4), "<i8", self._stream),
+                OpenOrdersView(self, entries, (self.n_books, nt, depth, 4), "<i4", self._stream) if depth else None)
+
+
+class OpenOrdersView:
+    """One table of ``ManyBookEnv.open_orders_views()`` where it lives, for ``torch.as_tensor(view, device="cuda")``, cupy
+    and anything else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
+
+    def __init__(self, env, ptr: int, shape, typestr: str, stream: Optional[int]):
+        self._env = env
+        # (`stream`: as AccountsView spells it - None when unknown, 1 for the legacy default stream, else the handle)
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 3, "strides": None,
+                                         "stream": None if stream is None else (stream if stream != 0 else 1)}
+
 
 class AccountsView:
     """``ManyBookEnv.accounts_view()``: the accounts table where it lives, for ``torch.as_tensor(view, device="cuda")``,

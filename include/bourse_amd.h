@@ -595,6 +595,57 @@ int bk_accounts_clear(bk_env* env, const uint8_t* mask_host);
  * on the env's stream.  (No counterpart in the reference.) */
 int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev);
 
+/* ------------------------------------------------------ open orders of a device-ingress env */
+/* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
+ * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or
+ * modify, the resting volume per side for an exposure limit, its own best bid and ask).  The tables are RECOMPUTED from
+ * each book's pool and the order records' trader ids on the env's stream (bourse_amd/csrc/open_orders.hpp):
+ * they hold no state of their own - no cursor, nothing in a snapshot - and cannot drift from the book.  The reference has
+ * no counterpart for any of these entries.
+ *
+ * summary[n_books][n_traders], and entries[n_books][n_traders][depth].  "Resting" means live in the pool as the last
+ * refresh found it: exactly the set bk_live_orders returns, with the remaining volume and the current price (partial fills
+ * and modifications show).  A trader's entries are its resting orders of either side in ascending order id (creation
+ * order; ids are u32 on the device); the first min(n_bid + n_ask, depth) are used and every slot behind them holds the
+ * empty entry {0xFFFFFFFF, 0, 0, 0}.  A trader that rests more than depth orders has its oldest depth listed and an exact
+ * summary: n_bid + n_ask > depth says so.  A trader id >= n_traders is skipped without a flag: give background members
+ * (bk_set_agents*, bk_set_random_agents*) an agent_id_start above n_traders to keep them out.  A resting order whose id is
+ * >= max_orders has no record to look its trader up in and is left out of the rows; BK_FLAG_ORDER_LOG_FULL is set on that
+ * book already.  Rows are per book, so markets need nothing special (market * assets + asset). */
+typedef struct bk_open_summary { /* 32 B */
+  uint64_t bid_vol, ask_vol;   /* sum of the remaining volume of the trader's resting bids / asks */
+  uint32_t n_bid, n_ask;       /* how many rest, ALL of them (not capped by depth) */
+  uint32_t best_bid, best_ask; /* highest own bid price (0 if none), lowest own ask price (0xFFFFFFFF if none) */
+} bk_open_summary;
+typedef struct bk_open_order { /* 16 B */
+  uint32_t order_id, price, vol, side_is_bid;
+} bk_open_order;
+/* Enabling.  Accepted on an env with the device ingress (bk_device_ingress_enable) and max_orders > 0, at any time - also
+ * mid-run and while an ingress snapshot slot is held: the tables are a function of the current pools.  depth == 0 keeps
+ * the summary rows only (no entry array, no ranking work).  Refuses n_traders == 0, n_traders > 65536, depth > 64 and a
+ * second call.  A refusal - here and in the three entries below - returns BK_INVALID_ARGUMENT, is made before anything is
+ * allocated or enqueued, leaves the env unchanged and puts the reason in bk_last_error().
+ *
+ * When the tables are refreshed: at this call (every book); behind every bk_step_async / bk_step, after the event kernel
+ * (and after the accounts' fold when both are on); behind bk_ingress_reset_books*, for the reset units only, after the
+ * reset's own kernels with the same device mask - a reset book shows the snapshot's resting orders before its next step;
+ * and at bk_open_orders_refresh.  Each is one launch on the env's stream: no allocation, no stream wait, no host read.
+ * The tables describe the books as of the last refresh: instructions submitted or queued since are not in them.
+ * Behaviour of an env without the view does not change.  (No counterpart in the reference.) */
+int bk_open_orders_enable(bk_env* env, uint32_t n_traders, uint32_t depth);
+/* Refresh the rows of every book now, for callers that changed a pool outside a step.
+ * (No counterpart in the reference.) */
+int bk_open_orders_refresh(bk_env* env);
+/* Device pointers of the two tables, bk_open_summary[n_books][n_traders] and bk_open_order[n_books][n_traders][depth]
+ * (*entries = NULL when depth == 0), for on-device consumers; valid for the env's life, written on the env's stream.
+ * (No counterpart in the reference.) */
+int bk_open_orders_device_ptrs(bk_env* env, void** summary, void** entries);
+/* Rows of books [first_book, first_book + n_books) to host memory: n_books * n_traders summary rows and, when entries_out
+ * (nullable) is not NULL and depth > 0, n_books * n_traders * depth entries.  Waits for the env's stream.
+ * (No counterpart in the reference.) */
+int bk_get_open_orders(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_summary* summary_out,
+                       bk_open_order* entries_out);
+
 #ifdef __cplusplus
 }
 #endif

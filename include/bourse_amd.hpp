@@ -256,11 +256,38 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_accounts_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
+  // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
+  void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
+    check(bk_open_orders_enable(h_, n_traders, depth));
+    open_traders_ = n_traders, open_depth_ = depth;
+  }
+  void refresh_open_orders() { check(bk_open_orders_refresh(h_)); }
+  // rows of books [first_book, first_book + n_books): n_traders summary rows per book and n_traders * depth entries
+  // (waits for the env's stream)
+  struct OpenOrders {
+    std::vector<bk_open_summary> summary;
+    std::vector<bk_open_order> entries;
+  };
+  OpenOrders open_orders(uint32_t first_book, uint32_t n_books) {
+    OpenOrders out;
+    out.summary.resize(static_cast<size_t>(n_books) * open_traders_);
+    out.entries.resize(out.summary.size() * open_depth_);
+    check(bk_get_open_orders(h_, first_book, n_books, out.summary.data(), open_depth_ ? out.entries.data() : nullptr));
+    return out;
+  }
+  OpenOrders open_orders() { return open_orders(0, n_books_); }
+  // the tables in device memory: bk_open_summary[n_books][n_traders], bk_open_order[n_books][n_traders][depth] (null: depth 0)
+  std::pair<bk_open_summary*, bk_open_order*> open_orders_device_ptrs() {
+    void *s = nullptr, *e = nullptr;
+    check(bk_open_orders_device_ptrs(h_, &s, &e));
+    return {static_cast<bk_open_summary*>(s), static_cast<bk_open_order*>(e)};
+  }
   bk_env* handle() { return h_; }
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
