@@ -527,7 +527,9 @@ int bk_ingress_snapshot_save(bk_env* env, uint32_t slot);
 /* Frees the slot's memory (waits for the env's stream first); dropping an empty slot is not an error.  (No counterpart
  * in the reference.) */
 int bk_ingress_snapshot_drop(bk_env* env, uint32_t slot);
-/* Device bytes the slot holds; 0 for an empty slot.  (No counterpart in the reference.) */
+/* Device bytes the slot holds; 0 for an empty slot.  This is what is ALLOCATED, not what the last save used: the record
+ * arrays grow with a save that finds more ids per book and never shrink, so a slot saved again with fewer ids reports the
+ * size of its largest save until it is dropped.  (No counterpart in the reference.) */
 uint64_t bk_ingress_snapshot_bytes(const bk_env* env, uint32_t slot);
 /* Units u with mask_dev[u] != 0 return to their state in `slot`; mask_dev [n_units] bytes and seeds_dev [n_units] u64
  * (nullable) are DEVICE memory written on the env's stream.  HOLDS NO HOST SYNCHRONISATION: launches on the env's stream
