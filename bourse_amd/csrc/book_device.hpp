@@ -170,6 +170,10 @@ __device__ __forceinline__ uint32_t sel(uint64_t mask, uint32_t if_set, uint32_t
   return __builtin_amdgcn_inverse_ballot_w64(mask) ? if_set : if_clear;  // v_cndmask_b32 with the SGPR mask
 }
 __device__ __forceinline__ bool lane_bit(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+// the number of set bits of a wave-uniform mask below this lane: the lane's place when the set lanes are compacted
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 // Full-wave (all 64 lanes active) reductions on the DPP network: butterfly inside each row
 // of 16, then row_bcast:15 / row_bcast:31 carry the row results into lane 63.
@@ -1685,7 +1689,7 @@ __device__ __forceinline__ void step_batch_raw(const DevArgs& a, uint32_t book, 
     B.price[r] = sel(pend, pv.x, B.price[r]);
     B.vol[r] = sel(pend, pv.y, B.vol[r]);
     // create_order ids: dense, in agent order (orderbook.rs:363): base + #placing agents below this slot
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
+    const uint32_t rank = lane_rank(pend);
     B.id[r] = sel(pend, base + rank, B.id[r]);
     if constexpr (LOG) {
       // create_order's record of each new order (orderbook.rs:356-396), lane-parallel: the trader id is the agent's index
@@ -1760,7 +1764,7 @@ __global__ void k_book_service(uint32_t* state, uint32_t stride, uint32_t n_book
 //   * create_order's tick check (orderbook.rs:367-382): the first new order whose price is not a multiple of the book's
 //     tick size stops THAT BOOK's batch - earlier elements stay created and queued, later ones are not looked at
 //     (`.collect::<Result<Vec<_>, _>>()` short-circuits, step_sim_numpy.rs:255-268); status = {code, elements applied};
-//   * ids: dense per book, in element order - base + exclusive prefix count of the new orders (a ballot + mbcnt);
+//   * ids: dense per book, in element order - base + exclusive prefix count of the new orders (a ballot + lane_rank);
 //   * the events are appended to the market's queue in element (then asset) order, the position = queue length +
 //     exclusive prefix count of the event-producing elements; action 0 / unknown actions produce nothing (:266);
 //   * the immutable half of every new order and its initial order-log entry (status New, arr_time = now) are written
@@ -1768,6 +1772,28 @@ __global__ void k_book_service(uint32_t* state, uint32_t stride, uint32_t n_book
 // BK_ACTION_MODIFY (0x80000003, outside the numpy API's 0 / 1 / 2; the host entry takes the same code) = Env::modify_order
 // (env.rs:208-219): side bit 1 = has price, bit 2 = has volume.  Every other action is a no-op (:266).
 // ==================================================================================
+// Where a book's new orders are recorded for the readers (bk_get_orders, bk_order_status, the ingress reset, the accounts,
+// the open orders), and when: the two arrays, the book's row of log_cap ids in them, the book's clock
+struct NewOrderRecords {
+  uint4* dorders;          // [n_books][log_cap][2]: {start_vol, trader, price, bid} {create_lo, create_hi, 0, 0}
+  DevOrderLog* order_log;  // [n_books][log_cap]
+  uint32_t book, log_cap, t_lo, t_hi;
+};
+// A new order's immutable half and its initial order-log entry - status New, nothing traded, provisional key (price, 0),
+// arrival = the book's clock (orderbook.rs:388-391) - by the lane that holds it; an id beyond the log's capacity is not
+// recorded (k_step_events flags it at its placement).  Every kernel that queues a New event writes them here.
+__device__ __forceinline__ void write_new_order(const NewOrderRecords& r, uint32_t id, uint32_t vol, uint32_t trader,
+                                                uint32_t price, uint32_t bid) {
+  if (id >= r.log_cap) return;
+  uint4* d = r.dorders + ((size_t)r.book * r.log_cap + id) * 2;
+  d[0] = make_uint4(vol, trader, price, bid);
+  d[1] = make_uint4(r.t_lo, r.t_hi, 0u, 0u);
+  uint4* l = reinterpret_cast<uint4*>(r.order_log + (size_t)r.book * r.log_cap + id);
+  l[0] = make_uint4(0u, vol, price, price);
+  l[1] = make_uint4(r.t_lo, r.t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
+  l[2] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 struct IngestArgs {
   const unsigned long long* off;  // [n_books + 1]
   const uint32_t* action;
@@ -1781,7 +1807,7 @@ struct IngestArgs {
   uint4* q;                       // [n_markets][qcap] event records (HostEvent layout)
   uint32_t* qlen;                 // [n_markets]
   uint32_t qcap;
-  uint4* dorders;                 // [n_books][log_cap][2]: {start_vol, trader, price, bid} {create_lo, create_hi, 0, 0}
+  uint4* dorders;                 // [n_books][log_cap][2] immutable halves (write_new_order)
   uint32_t* mods_flag;            // nullable: a word in mapped HOST memory, set to 1 when a BK_ACTION_MODIFY element is seen (a hint
                                   // for the host's choice of k_step_events instantiation: sticky, may lag by a step)
 };
@@ -1798,7 +1824,8 @@ __global__ __launch_bounds__(64) void k_ingest(DevArgs a, IngestArgs g) {
     uint32_t* hdr = a.state + (size_t)book * a.state_stride;
     const uint32_t tick = a.asset_tick[asset];
     uint32_t next_id = rfl(hdr[H_NEXT_ID]);
-    const uint32_t t_lo = rfl(hdr[H_T_LO]), t_hi = rfl(hdr[H_T_HI]);  // now: the book's clock (Env::place_order stamps it)
+    // now: the book's clock (Env::place_order stamps it)
+    const NewOrderRecords rec{g.dorders, a.order_log, book, a.log_cap, rfl(hdr[H_T_LO]), rfl(hdr[H_T_HI])};
     const unsigned long long lo = g.off[book], hi = g.off[book + 1];
     uint32_t code = ING_OK;
     unsigned long long applied = 0;
@@ -1831,8 +1858,8 @@ __global__ __launch_bounds__(64) void k_ingest(DevArgs a, IngestArgs g) {
       }
       const bool valid = in && (uint32_t)lane < cut;
       const uint64_t newm = __ballot(valid && is_new);
-      const uint32_t rank_ev = __builtin_amdgcn_mbcnt_hi((uint32_t)(evm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)evm, 0u));
-      const uint32_t rank_new = __builtin_amdgcn_mbcnt_hi((uint32_t)(newm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)newm, 0u));
+      const uint32_t rank_ev = lane_rank(evm);
+      const uint32_t rank_new = lane_rank(newm);
       const uint32_t id = next_id + rank_new;
       if (valid && is_ev) {
         uint4 e;
@@ -1846,16 +1873,7 @@ __global__ __launch_bounds__(64) void k_ingest(DevArgs a, IngestArgs g) {
         }
         q[qn + rank_ev] = e;
       }
-      if (valid && is_new && id < a.log_cap) {
-        uint4* d = g.dorders + ((size_t)book * a.log_cap + id) * 2;
-        d[0] = make_uint4(vol, trader, price, sd & 1u);
-        d[1] = make_uint4(t_lo, t_hi, 0u, 0u);
-        // initial order-log entry: status New, nothing traded, provisional key (price, 0) (orderbook.rs:388-391)
-        uint4* l = reinterpret_cast<uint4*>(a.order_log + (size_t)book * a.log_cap + id);
-        l[0] = make_uint4(0u, vol, price, price);
-        l[1] = make_uint4(t_lo, t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
-        l[2] = make_uint4(0u, 0u, 0u, 0u);
-      }
+      if (valid && is_new) write_new_order(rec, id, vol, trader, price, sd & 1u);
       if (valid && g.out_ids) g.out_ids[i] = is_new ? (unsigned long long)id : ~0ull;
       next_id += (uint32_t)__builtin_popcountll(newm);
       qn += (uint32_t)__builtin_popcountll(evm);

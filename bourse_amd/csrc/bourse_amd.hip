@@ -380,6 +380,10 @@ struct bk_env {
     for (size_t g = 0; g < groups.size(); ++g) a.groups[g] = groups[g];
     return a;
   }
+  // the queues and order records bk_update_agents' and bk_update_members' kernels write into
+  IngressArgs ingress_args() const {
+    return IngressArgs{state.p, stride, cfg.max_orders, qcap, dq.p, dqlen.p, dorders.p, order_log.p};
+  }
 };
 
 namespace {
@@ -1710,18 +1714,11 @@ int bk_update_agents(bk_env* env) {
     env->agent_held_stale = false;
   }
   AgentsIngressArgs g{};
-  g.state = env->state.p;
-  g.state_stride = env->stride;
+  g.io = env->ingress_args();
   g.n_agents = NA;
-  g.log_cap = env->cfg.max_orders;
-  g.qcap = env->qcap;
   g.groups = env->table.empty() ? env->agent_groups.p : env->dtable.p;
   g.g_stride = env->table.empty() ? 0u : static_cast<uint32_t>(env->groups.size());
   g.held = env->agent_held.p;
-  g.q = env->dq.p;
-  g.qlen = env->dqlen.p;
-  g.dorders = env->dorders.p;
-  g.order_log = env->order_log.p;
   by_R(env->R, [&](auto r) {
     hipLaunchKernelGGL(k_update_agents<decltype(r)::value>, dim3(B), dim3(64), 0, env->stream, g);
     return 0;
@@ -1768,11 +1765,8 @@ int bk_update_members(bk_env* env) {
     env->member_lists_stale = false;
   }
   bkd::ingress::MembersIngressArgs g{};
-  g.state = env->state.p;
-  g.state_stride = env->stride;
+  g.io = env->ingress_args();
   g.n_members = NM;
-  g.log_cap = env->cfg.max_orders;
-  g.qcap = env->qcap;
   g.tick = env->cfg.tick_size;
   g.descs = env->mtable.empty() ? env->mixed_descs.p : env->dmtable.p;
   g.id_start = env->member_id0_dev.p;
@@ -1782,10 +1776,6 @@ int bk_update_members(bk_env* env) {
   g.lens = env->member_lens.p;
   g.mstate = env->member_state.p;
   g.mflags = env->member_flags.p;
-  g.q = env->dq.p;
-  g.qlen = env->dqlen.p;
-  g.dorders = env->dorders.p;
-  g.order_log = env->order_log.p;
   by_R(env->R, [&](auto r) {
     hipLaunchKernelGGL(bkd::ingress::k_update_members<decltype(r)::value>, dim3(B), dim3(64), 0, env->stream, g);
     return 0;
@@ -2968,18 +2958,38 @@ int bk_snapshot_drop(bk_env* env, uint32_t slot) {
   return BK_OK;
 }
 
+// a slot's ckpt_header words (h[2..5], as its save kept them) against the env as it is now
+static int snapshot_shape_ok(bk_env* env, const uint64_t (&shape)[4]) {
+  uint64_t h[CKPT_HDR];
+  ckpt_header(env, h);
+  if (shape[0] != h[2] || shape[1] != h[3])
+    return fail(BK_INVALID_ARGUMENT, "snapshot does not match this env (n_books / pool size / levels / assets)");
+  if (shape[2] != h[4] || shape[3] != h[5])
+    return fail(BK_INVALID_ARGUMENT, "snapshot was taken with a different agent set: install the same agents first");
+  return BK_OK;
+}
+
 // every refusal, before anything is enqueued
 static int reset_ok(bk_env* env, uint32_t slot, const void* mask) {
   if (int rc = snapshot_env_ok(env, slot)) return rc;
   if (!mask) return fail(BK_INVALID_ARGUMENT, "null mask");
   const bk_env::Snapshot& s = env->snaps[slot];
   if (!s.used) return fail(BK_INVALID_ARGUMENT, "snapshot slot is empty: call bk_snapshot_save first");
-  uint64_t h[CKPT_HDR];
-  ckpt_header(env, h);
-  if (s.shape[0] != h[2] || s.shape[1] != h[3])
-    return fail(BK_INVALID_ARGUMENT, "snapshot does not match this env (n_books / pool size / levels / assets)");
-  if (s.shape[2] != h[4] || s.shape[3] != h[5])
-    return fail(BK_INVALID_ARGUMENT, "snapshot was taken with a different agent set: install the same agents first");
+  return snapshot_shape_ok(env, s.shape);
+}
+
+// A host mask of n entries (and seeds, when given) into lazily allocated device buffers, for the _device form of the
+// caller: waits for the env's stream, so the caller's arrays are free when it returns
+// (`seeds` is required when `seeds_host` is given; bk_accounts_clear has neither)
+static int stage_mask(bk_env* env, size_t n, const uint8_t* mask_host, DevBuf<uint8_t>& mask,
+                      const uint64_t* seeds_host = nullptr, DevBuf<uint64_t>* seeds = nullptr) {
+  if (!mask.p) HIPCHK(mask.alloc(n));
+  HIPCHK(hipMemcpyAsync(mask.p, mask_host, n, hipMemcpyHostToDevice, env->stream));
+  if (seeds_host) {
+    if (!seeds->p) HIPCHK(seeds->alloc(n));
+    HIPCHK(hipMemcpyAsync(seeds->p, seeds_host, n * 8, hipMemcpyHostToDevice, env->stream));
+  }
+  HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
 }
 
@@ -3023,11 +3033,7 @@ int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const u
   if (int rc = reset_ok(env, slot, mask_host)) return rc;
   if (int rc = use_device(env)) return rc;
   const size_t n_units = env->cfg.n_books / env->M;
-  if (!env->reset_mask.p) HIPCHK(env->reset_mask.alloc(n_units));
-  if (seeds_host && !env->reset_seeds.p) HIPCHK(env->reset_seeds.alloc(n_units));
-  HIPCHK(hipMemcpyAsync(env->reset_mask.p, mask_host, n_units, hipMemcpyHostToDevice, env->stream));
-  if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
-  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
+  if (int rc = stage_mask(env, n_units, mask_host, env->reset_mask, seeds_host, &env->reset_seeds)) return rc;
   return bk_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
 }
 
@@ -3178,12 +3184,7 @@ static int ingress_reset_ok(bk_env* env, uint32_t slot, const void* mask) {
   const bk_env::IngressSnapshot& s = env->isnaps[slot];
   if (!s.used) return fail(BK_INVALID_ARGUMENT, "snapshot slot is empty: call bk_ingress_snapshot_save first");
   if (!mask) return fail(BK_INVALID_ARGUMENT, "null mask");
-  uint64_t h[CKPT_HDR];
-  ckpt_header(env, h);
-  if (s.shape[0] != h[2] || s.shape[1] != h[3])
-    return fail(BK_INVALID_ARGUMENT, "snapshot does not match this env (n_books / pool size / levels / assets)");
-  if (s.shape[2] != h[4] || s.shape[3] != h[5])
-    return fail(BK_INVALID_ARGUMENT, "snapshot was taken with a different agent set: install the same agents first");
+  if (int rc = snapshot_shape_ok(env, s.shape)) return rc;
   if (s.installs != env->agent_installs)
     return fail(BK_INVALID_ARGUMENT, "agents were installed again (bk_set_*agents*) since the snapshot was taken: their held "
                                      "ids and lists start empty at the next update, which a reset cannot restore - call "
@@ -3257,11 +3258,7 @@ int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host,
   if (int rc = ingress_reset_ok(env, slot, mask_host)) return rc;
   if (int rc = use_device(env)) return rc;
   const size_t n_units = env->cfg.n_books / env->M;
-  if (!env->reset_mask.p) HIPCHK(env->reset_mask.alloc(n_units));
-  if (seeds_host && !env->reset_seeds.p) HIPCHK(env->reset_seeds.alloc(n_units));
-  HIPCHK(hipMemcpyAsync(env->reset_mask.p, mask_host, n_units, hipMemcpyHostToDevice, env->stream));
-  if (seeds_host) HIPCHK(hipMemcpyAsync(env->reset_seeds.p, seeds_host, n_units * 8, hipMemcpyHostToDevice, env->stream));
-  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's arrays are free from here on
+  if (int rc = stage_mask(env, n_units, mask_host, env->reset_mask, seeds_host, &env->reset_seeds)) return rc;
   return bk_ingress_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
 }
 
@@ -3336,10 +3333,7 @@ int bk_accounts_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = accounts_ok(env)) return rc;
   if (!mask_host) return bk_accounts_clear_device(env, nullptr);
   if (int rc = use_device(env)) return rc;
-  const size_t B = env->cfg.n_books;
-  if (!env->acct_mask.p) HIPCHK(env->acct_mask.alloc(B));
-  HIPCHK(hipMemcpyAsync(env->acct_mask.p, mask_host, B, hipMemcpyHostToDevice, env->stream));
-  HIPCHK(hipStreamSynchronize(env->stream));  // the caller's array is free from here on
+  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->acct_mask)) return rc;
   return bk_accounts_clear_device(env, env->acct_mask.p);
 }
 

@@ -9,7 +9,7 @@
 //   NoiseAgent::update                    crates/step_sim/src/agents/noise_agent.rs:127-176
 //   MomentumAgent::update                 crates/step_sim/src/agents/momentum_agent.rs:146-208
 //   RandomAgents::update                  crates/step_sim/src/agents/random_agent.rs:85-119
-// with the draws, thresholds and f64 routines of mixed_update_and_shuffle (mixed_agents.hpp:256-352) - the same MixedDesc
+// with the draws, thresholds and f64 routines of mixed_update_and_shuffle (mixed_agents.hpp) - the same MixedDesc
 // records, the same pm_math.hpp functions, no FMA contraction.
 //
 // One wave per book.  The walk over a member's list and its traders is the book's serial RNG stream - wave-uniform, the RNG
@@ -22,13 +22,13 @@
 //     needs the same 64 R compares per pass behind an LDS round trip.  Registers of the pool that hold nothing live are
 //     skipped.  An order queued earlier in the same step is New (not yet in the pool), a filled or cancelled one has left
 //     it: both are dropped without a draw - the order log is not read;
-//   * the draws that follow are one next_u32 per Active entry, in list order; the kept ids go back compacted (mbcnt), the
+//   * the draws that follow are one next_u32 per Active entry, in list order; the kept ids go back compacted (lane_rank), the
 //     cancellation records to the queue in list order;
 //   * the traders' loop collects its New orders in lanes (v_writelane), 64 at a time, and writes their records, their
-//     `dorders` halves, their first order-log entries (k_ingest's, book_device.hpp:1838-1858) and the list's new entries
+//     `dorders` halves, their first order-log entries (k_ingest's: write_new_order) and the list's new entries
 //     lane-parallel in event order;
-//   * a RandomAgents member keeps its agents' held ids (AGENT_HELD_NONE = None) in the same row and walks them exactly as
-//     k_update_agents does (agents_ingress.hpp:69-112);
+//   * a RandomAgents member keeps its agents' held ids (AGENT_HELD_NONE = None) in the same row and walks them with
+//     k_update_agents' pass (agents_ingress.hpp: random_agent, random_pass_end);
 //   * MomentumAgent's momentum / last_price / "has a last price" live in an array of their own (the header's H_GST words
 //     belong to bk_run's kernels); the RNG words, H_NEXT_ID, the flags and the queue length are written once per book.
 // Capacity: an event beyond the queue's room, or a New order once the u32 id space is exhausted, is dropped and the book
@@ -45,8 +45,8 @@ namespace bkd {
 namespace ingress {
 
 struct MembersIngressArgs {
-  uint32_t* state;
-  uint32_t state_stride, n_members, log_cap, qcap;
+  IngressArgs io;
+  uint32_t n_members;
   uint32_t tick;            // the book's tick size (create_order's check)
   const MixedDesc* descs;   // member j of book b: descs[b * d_stride + j] (the per-book table; d_stride 0 = one row for all)
   const uint32_t* id_start; // ... and its first trader id, id_start[b * d_stride + j]
@@ -56,10 +56,6 @@ struct MembersIngressArgs {
   uint32_t* lens;           // [n_books][n_members]
   uint64_t* mstate;         // [n_books][n_members][2] momentum, last_price (f64 bits)
   uint32_t* mflags;         // [n_books] bit j: member j has a last price
-  uint4* q;                 // [n_books][qcap] event records (k_ingest's layout)
-  uint32_t* qlen;           // [n_books]
-  uint4* dorders;           // [n_books][log_cap][2] immutable halves
-  DevOrderLog* order_log;
 };
 
 // rows this size never overflow (see above); the host sizes them with it
@@ -83,15 +79,6 @@ __device__ __forceinline__ MixedDesc sload_desc(const MixedDesc* p) {
   return D;
 }
 
-// what one book's update carries from member to member
-struct Walk {
-  uint32_t next_id, flags, n_ev, room, q0, t_lo, t_hi, log_cap;
-  uint32_t book;
-  uint4* q;
-  uint4* dorders;
-  DevOrderLog* order_log;
-};
-
 // New orders collected in lanes, in event order: lane k holds the k-th of the batch (ids id0 + k)
 struct NewBatch {
   uint32_t price, trader;  // per lane
@@ -99,7 +86,7 @@ struct NewBatch {
   uint32_t cnt, id0, ev0;
 };
 
-// the batch's records, dorders halves and first log entries (k_ingest's), and the limit orders' ids onto the list
+// the batch's records, dorders halves and first log entries (write_new_order), and the limit orders' ids onto the list
 __device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t vol, uint32_t* list, uint32_t& len,
                                           uint32_t list_cap, int lane) {
   if (N.cnt == 0) return;
@@ -108,18 +95,9 @@ __device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t v
   const uint32_t bid = lane_bit(N.bidm) ? 1u : 0u;
   if (mine) {
     W.q[W.q0 + N.ev0 + (uint32_t)lane] = make_uint4(bid << 8, id, N.price, vol);
-    if (id < W.log_cap) {
-      uint4* d = W.dorders + ((size_t)W.book * W.log_cap + id) * 2;
-      d[0] = make_uint4(vol, N.trader, N.price, bid);
-      d[1] = make_uint4(W.t_lo, W.t_hi, 0u, 0u);
-      // initial order-log entry: status New, nothing traded, provisional key (price, 0) (orderbook.rs:388-391)
-      uint4* lg = reinterpret_cast<uint4*>(W.order_log + (size_t)W.book * W.log_cap + id);
-      lg[0] = make_uint4(0u, vol, N.price, N.price);
-      lg[1] = make_uint4(W.t_lo, W.t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
-      lg[2] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    write_new_order(W.rec, id, vol, N.trader, N.price, bid);
   }
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(N.limm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)N.limm, 0u));
+  const uint32_t rank = lane_rank(N.limm);
   if (lane_bit(N.limm) && len + rank < list_cap) list[len + rank] = id;
   len += (uint32_t)__builtin_popcountll(N.limm);
   N.cnt = 0;
@@ -127,8 +105,8 @@ __device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t v
 }
 
 // Env::place_order from a Noise / Momentum trader: the id and the New event (dropped and flagged beyond the queue's room
-// or the id space); a limit price off the book's tick grid is flagged and creates nothing (mixed_create,
-// mixed_agents.hpp:134-140); a market order carries the extreme price of its side (orderbook.rs:595) and takes no check
+// or the id space); a limit price off the book's tick grid is flagged and creates nothing (mixed_create's rule,
+// mixed_agents.hpp); a market order carries the extreme price of its side (orderbook.rs:595) and takes no check
 __device__ __forceinline__ void place_new(Walk& W, NewBatch& N, bool limit, bool is_bid, uint32_t price, uint32_t trader,
                                           uint32_t tick, uint32_t vol, uint32_t* list, uint32_t& len, uint32_t list_cap,
                                           int lane) {
@@ -159,7 +137,7 @@ template <int R>
 __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
   const int lane = threadIdx.x;
   const uint32_t book = blockIdx.x;
-  uint32_t* st = g.state + (size_t)book * g.state_stride;
+  uint32_t* st = g.io.state + (size_t)book * g.io.state_stride;
   const uint32_t hdr = st[lane];
   uint64_t live[R];
 #pragma unroll
@@ -180,20 +158,8 @@ __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
     const uint32_t bid = wave_umax(mb), ask = wave_umin(mk);
     mid = static_cast<double>(bid) + 0.5 * static_cast<double>(ask - bid);
   }
-  Rng rng;
-  rng.s0 = mk64(rdl(hdr, H_S0_LO), rdl(hdr, H_S0_HI));
-  rng.s1 = mk64(rdl(hdr, H_S1_LO), rdl(hdr, H_S1_HI));
-  Walk W;
-  W.next_id = rdl(hdr, H_NEXT_ID), W.flags = rdl(hdr, H_FLAGS);
-  W.t_lo = rdl(hdr, H_T_LO), W.t_hi = rdl(hdr, H_T_HI);
-  W.q0 = rfl(g.qlen[book]);
-  W.room = g.qcap > W.q0 ? g.qcap - W.q0 : 0u;
-  W.n_ev = 0;
-  W.log_cap = g.log_cap;
-  W.book = book;
-  W.q = g.q + (size_t)book * g.qcap;
-  W.dorders = g.dorders;
-  W.order_log = g.order_log;
+  Walk W = walk_begin(g.io, book, hdr);
+  Rng& rng = W.rng;
   const MixedDesc* row = g.descs + (size_t)book * g.d_stride;
   const uint32_t* id_start = g.id_start + (size_t)book * g.d_stride;
   uint32_t mflags = rfl(g.mflags[book]);
@@ -202,73 +168,17 @@ __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
     const MixedDesc D = sload_desc(row + j);
     uint32_t* list = g.lists + ((size_t)book * g.n_members + j) * g.list_cap;
     if (D.type == 0) {
-      // ---- RandomAgents::update (random_agent.rs:85-119): k_update_agents' walk over the member's held ids
+      // ---- RandomAgents::update (random_agent.rs:85-119): k_update_agents' pass over the member's held ids
       const uint32_t n_agents = min(D.n, g.list_cap);
       for (uint32_t base = 0; base < n_agents; base += 64) {
         const uint32_t n_here = min(64u, n_agents - base);
         const bool in = (uint32_t)lane < n_here;
         const uint32_t h = in ? list[base + lane] : AGENT_HELD_NONE;
-        const uint32_t ev0 = W.n_ev, id0 = W.next_id;
-        uint64_t canm = 0, newm = 0, bidm = 0, dropm = 0;
-        uint32_t e_price = 0, e_vol = 0, e_trader = 0;
-        for (uint32_t l = 0; l < n_here; ++l) {
-          const uint32_t x = rng.next_u32();  // p = gen::<f32>()  (random_agent.rs:91)
-          if ((x >> 8) >= D.thr) continue;    // inactive: keeps what it holds
-          const uint64_t bit = 1ull << l;
-          const uint32_t hl = rdl(h, l);
-          uint64_t act = 0;
-          if (hl != AGENT_HELD_NONE) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) act |= __ballot(pid[r] == hl);
-          }
-          if (act) {  // holds an Active order: env.cancel_order (:95-97)
-            if (W.n_ev < W.room) {
-              canm |= bit;
-              W.n_ev += 1;
-            } else {
-              dropm |= bit;
-              W.flags |= FLAG_EVENT_OVERFLOW;
-            }
-            continue;
-          }
-          // env.place_order with side, tick, vol drawn in this order (:99-111)
-          const uint32_t side = rng.below(2u, 0x7FFFFFFFu);  // [Ask, Bid].choose: 0 = Ask, 1 = Bid
-          const uint32_t tick = D.tick_lo + rng.below(D.tick_rng, D.tick_zone);
-          const uint32_t vol = D.vol_lo + rng.below(D.vol_rng, D.vol_zone);
-          if (W.n_ev < W.room && W.next_id < AGENT_HELD_NONE - 1u) {
-            newm |= bit;
-            bidm |= side ? bit : 0ull;
-            e_price = wrl(tick * D.tick_size, l, e_price);
-            e_vol = wrl(vol, l, e_vol);
-            e_trader = wrl(base + l, l, e_trader);  // TraderId = the agent's index in its member
-            W.n_ev += 1;
-            W.next_id += 1;
-          } else {
-            dropm |= bit;
-            W.flags |= FLAG_EVENT_OVERFLOW;
-          }
-        }
-        // the pass's records, in agent order
-        const uint64_t evm = canm | newm;
-        const uint32_t rank_ev = __builtin_amdgcn_mbcnt_hi((uint32_t)(evm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)evm, 0u));
-        const uint32_t rank_new = __builtin_amdgcn_mbcnt_hi((uint32_t)(newm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)newm, 0u));
-        const bool is_new = lane_bit(newm), is_can = lane_bit(canm);
-        const uint32_t id = id0 + rank_new;
-        const uint32_t bid = lane_bit(bidm) ? 1u : 0u;
-        if (is_can) W.q[W.q0 + ev0 + rank_ev] = make_uint4(1u, h, 0u, 0u);
-        if (is_new) {
-          W.q[W.q0 + ev0 + rank_ev] = make_uint4(bid << 8, id, e_price, e_vol);
-          if (id < g.log_cap) {
-            uint4* d = g.dorders + ((size_t)book * g.log_cap + id) * 2;
-            d[0] = make_uint4(e_vol, e_trader, e_price, bid);
-            d[1] = make_uint4(W.t_lo, W.t_hi, 0u, 0u);
-            uint4* lg = reinterpret_cast<uint4*>(g.order_log + (size_t)book * g.log_cap + id);
-            lg[0] = make_uint4(0u, e_vol, e_price, e_price);
-            lg[1] = make_uint4(W.t_lo, W.t_hi, 0xFFFFFFFFu, 0xFFFFFFFFu);
-            lg[2] = make_uint4(0u, 0u, 0u, 0u);
-          }
-        }
-        if (in) list[base + lane] = is_new ? id : (is_can || lane_bit(dropm)) ? AGENT_HELD_NONE : h;
+        RandomPass S(W);
+        // TraderId = the agent's index in its member
+        for (uint32_t l = 0; l < n_here; ++l) random_agent<R>(W, S, D, pid, h, l, base + l);
+        const uint32_t now = random_pass_end(W, S, h);
+        if (in) list[base + lane] = now;
       }
       continue;
     }
@@ -301,13 +211,13 @@ __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
           W.flags |= FLAG_EVENT_OVERFLOW;
         }
       }
-      const uint32_t rank_can = __builtin_amdgcn_mbcnt_hi((uint32_t)(canm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)canm, 0u));
-      const uint32_t rank_keep = __builtin_amdgcn_mbcnt_hi((uint32_t)(keepm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keepm, 0u));
+      const uint32_t rank_can = lane_rank(canm);
+      const uint32_t rank_keep = lane_rank(keepm);
       if (lane_bit(canm)) W.q[W.q0 + ev0 + rank_can] = make_uint4(1u, e, 0u, 0u);
       if (lane_bit(keepm)) list[len + rank_keep] = e;  // (len + rank <= base + lane: behind every entry still to be read)
       len += (uint32_t)__builtin_popcountll(keepm);
     }
-    // ---- the traders' loops (mixed_agents.hpp:294-352)
+    // ---- the traders' loops (mixed_update_and_shuffle's, mixed_agents.hpp)
     const uint32_t trader0 = rfl(id_start[j]);
     NewBatch N;
     N.price = N.trader = 0;
@@ -369,19 +279,8 @@ __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
     flush_new(W, N, D.trade_vol, list, len, g.list_cap, lane);
     if (lane == 0) g.lens[(size_t)book * g.n_members + j] = min(len, g.list_cap);
   }
-  // the header words this call changed: the RNG, the id counter, the flags; then the members' flags and the queue's length
-  uint32_t w = hdr;
-  w = wrl((uint32_t)rng.s0, H_S0_LO, w);
-  w = wrl((uint32_t)(rng.s0 >> 32), H_S0_HI, w);
-  w = wrl((uint32_t)rng.s1, H_S1_LO, w);
-  w = wrl((uint32_t)(rng.s1 >> 32), H_S1_HI, w);
-  w = wrl(W.next_id, H_NEXT_ID, w);
-  w = wrl(W.flags, H_FLAGS, w);
-  if ((lane >= H_S0_LO && lane <= H_NEXT_ID) || lane == H_FLAGS) st[lane] = w;
-  if (lane == 0) {
-    g.mflags[book] = mflags;
-    g.qlen[book] = W.q0 + W.n_ev;
-  }
+  walk_end(W, g.io, st, hdr, lane);
+  if (lane == 0) g.mflags[book] = mflags;
 }
 
 }  // namespace ingress

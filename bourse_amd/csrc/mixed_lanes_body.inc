@@ -43,7 +43,7 @@
   const size_t NB = ml.n_books, NU = ml.n_units;
   const uint64_t act = __builtin_amdgcn_ballot_w64(true);  // the lanes with a book (all 64 but in the last workgroup)
   const uint32_t n_act = __builtin_popcountll(act);
-  const uint32_t my_rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+  const uint32_t my_rank = lane_rank(act);
 
   LaneRng rng;
   {
@@ -214,7 +214,7 @@
     const uint64_t w = __builtin_amdgcn_ballot_w64(pend_q);
     if (w == 0) return;
     if (pend_q) {
-      const uint32_t q = qc + __builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
+      const uint32_t q = qc + lane_rank(w);
       q_arg[q] = pend_arg;
       q_mid[q] = mid;
       q_info[q] = pend_info;

@@ -73,7 +73,7 @@
       const uint2 pvv = D.pv[r * 64 + lane];
       B.price[r] = sel(pend, pvv.x, B.price[r]);
       B.vol[r] = sel(pend, pvv.y, B.vol[r]);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
+      const uint32_t rank = lane_rank(pend);
       B.id[r] = sel(pend, base + rank, B.id[r]);
       base += __builtin_popcountll(pend);
       B.bid[r] = (B.bid[r] & ~pend) | (side & pend);

@@ -185,7 +185,7 @@ __device__ __forceinline__ bool step_events_keyed(Book<R>& B, const DevArgs& a, 
 #pragma unroll
   for (int re = 0; re < R; ++re) {
     if (R <= 4 && !is_new[re]) continue;
-    const uint32_t rank = n_new + __builtin_amdgcn_mbcnt_hi((uint32_t)(is_new[re] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)is_new[re], 0u));
+    const uint32_t rank = n_new + lane_rank(is_new[re]);
     if (lane_bit(is_new[re])) rank2ev[rank] = (uint16_t)(re * 64 + lane);
     n_new += __builtin_popcountll(is_new[re]);
   }
@@ -196,7 +196,7 @@ __device__ __forceinline__ bool step_events_keyed(Book<R>& B, const DevArgs& a, 
   for (int r = 0; r < R; ++r) {
     live0[r] = B.live[r];
     const uint64_t freem = ~(B.live[r] | B.pend[r]);
-    const uint32_t fr = nf + __builtin_amdgcn_mbcnt_hi((uint32_t)(freem >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)freem, 0u));
+    const uint32_t fr = nf + lane_rank(freem);
     const bool fre = lane_bit(freem), mine = fre && fr < n_new;
     const uint64_t nopm = __ballot(fre && fr == n_new);
     if (nopm) s_nop = (uint32_t)r * 64u + (uint32_t)__builtin_ctzll(nopm);

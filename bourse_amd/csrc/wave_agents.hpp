@@ -409,8 +409,7 @@ struct WaveDecoder {
         {
           const bool acted = (agw & WV_ACTED) != 0, placed = (agw & EV_NEW) != 0;
           const uint64_t am = __ballot(acted);
-          const uint32_t evi =
-              n_ev + __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+          const uint32_t evi = n_ev + lane_rank(am);
           if (acted) evl[evi] = (uint16_t)(agw | (placed ? (fside << 14) : 0u));
           if (placed) {
             const uint32_t slot = agw & EV_SLOT;
@@ -472,7 +471,7 @@ struct WaveDecoder {
       uint64_t acc = valid;
       uint32_t ii = 0, jj = 0;
       for (;;) {
-        const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(acc >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)acc, 0u));
+        const uint32_t k = lane_rank(acc);
         ii = i - k;                                  // <= 0 (wrapped): past the end of the shuffle
         const uint32_t r = ii + 1u;                  // range i + 1
         const bool in_range = is_valid && k < i;     // ii >= 1

@@ -127,7 +127,7 @@ __device__ __forceinline__ uint32_t rank_slots(const uint64_t (&mask)[R], uint16
   uint32_t acc = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const uint32_t lr = acc + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[r], 0u));
+    const uint32_t lr = acc + lane_rank(mask[r]);
     if (lane_bit(mask[r])) out[lr] = (uint16_t)(64u * r + (uint32_t)lane);
     acc += (uint32_t)__builtin_popcountll(mask[r]);
   }

@@ -136,14 +136,14 @@
       const bool alive = idx < len && ((lvw[(slot >> 5) & 15u] >> (slot & 31u)) & 1u) != 0u;  // else: filled / cancelled meanwhile
       const uint64_t am = __ballot(alive);
       S.ensure(S.pos + 64u);
-      const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+      const uint32_t rk = lane_rank(am);
       const uint32_t x = (uint32_t)S.at(S.pos + rk);
       const bool keep = alive && (int32_t)(x >> 8) > D.keep_thr;
       const bool cancel = alive && !keep;
       const uint64_t km = __ballot(keep), cm = __ballot(cancel);
-      if (cancel) evl[n_ev + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint16_t)slot;
+      if (cancel) evl[n_ev + lane_rank(cm)] = (uint16_t)slot;
       // in-place compaction: the write position never passes the read position, and this chunk's entries are in registers
-      if (keep) my[keep_pos + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = (uint16_t)slot;
+      if (keep) my[keep_pos + lane_rank(km)] = (uint16_t)slot;
       n_ev += (uint32_t)__builtin_popcountll(cm);
       keep_pos += (uint32_t)__builtin_popcountll(km);
       S.pos += (uint32_t)__builtin_popcountll(am);
@@ -243,7 +243,7 @@
         }
         V = __ballot(vis);
         if ((uint32_t)__builtin_popcountll(V) > rem) {  // the member's last trader sits inside this window
-          const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(V >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)V, 0u));
+          const uint32_t rk = lane_rank(V);
           V = __ballot(vis && rk < rem);
         }
         last = 63u - (uint32_t)__builtin_clzll(V);
@@ -273,8 +273,7 @@
       const bool do_b = vis && hit_b;
       const bool buy_b = noise ? (S.at(qb + 1u) >> 63) == 0ull : sgn > 0;
       const uint64_t CA = __ballot(do_a && ok_a), CB = __ballot(do_b);
-      const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(CA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)CA, 0u)) +
-                              __builtin_amdgcn_mbcnt_hi((uint32_t)(CB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)CB, 0u));
+      const uint32_t before = lane_rank(CA) + lane_rank(CB);
       // Env::place_order: dense ids in creation order (orderbook.rs:363), a trader's limit order before its market order
       auto emit = [&](uint32_t k, bool bid, uint32_t price, uint32_t tg) -> uint32_t {
         if (k >= n_free) return 0xFFFFu;  // pool full: the id is consumed, the order and its event are dropped (flagged below)
@@ -290,7 +289,7 @@
       if (do_a && ok_a) {
         const uint32_t slot = emit(n_created + before, buy_a, price_a, tag);
         // live_orders.push(order_id) (noise_agent.rs:158, momentum_agent.rs:188): behind the kept ones, in creation order
-        const uint32_t li = keep_pos + __builtin_amdgcn_mbcnt_hi((uint32_t)(CA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)CA, 0u));
+        const uint32_t li = keep_pos + lane_rank(CA);
         if (slot != 0xFFFFu) my[li] = (uint16_t)slot;
       }
       {  // the orders whose price is still to come
@@ -298,7 +297,7 @@
         const uint64_t qm = __ballot(qd);
         if (qc + (uint32_t)__builtin_popcountll(qm) > MW_QCAP) drain(1u);  // (no room for this window's: price what waits first)
         if (qd) {
-          const uint32_t qi = qc + __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
+          const uint32_t qi = qc + lane_rank(qm);
           q_arg[qi] = arg_a;
           q_info[qi] = (uint16_t)(freelist[n_created + before] | (buy_a ? 0x8000u : 0u));
         }

@@ -265,5 +265,17 @@ def test_refusals_and_capacity_flags(bk, oracle):
             env.update_agents()
             assert (env.flags() & bk._lib.FLAG_EVENT_OVERFLOW).all()
             assert all(env.order_count(b) <= 8 for b in range(B))
+            # the drop rule: a fresh env's first update (nobody holds an id) takes the oracle's draws whether an event fits
+            # or not, and queues exactly the first `room` placements, in agent order
+            for b in range(B):
+                ref = oracle.StepEnv(SEED + b, 0, 2, STEP)
+                oracle.RandomAgentSet(groups).update(ref)
+                want = ref.book.orders_array()
+                assert len(want) > 8, (b, len(want))  # the queue overflows in this book
+                assert env.rng_state(b) == tuple(int(x) for x in ref.rng_state()), b
+                assert env.order_count(b) == 8, b
+                got = env.orders(b)
+                for f in ("side", "price", "vol", "trader_id"):
+                    assert np.array_equal(got[f], want[f][:8]), (b, f, got[f], want[f][:8])
         env.step()
         env.close()

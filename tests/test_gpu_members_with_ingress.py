@@ -331,7 +331,9 @@ def test_a_short_queue_and_an_off_tick_price_are_flagged(bk, oracle):
     import torch
 
     B = 16
-    members = [("noise", 0, 32, dict(NOISE, p_limit=1.0, p_market=1.0))]  # 64 events per update
+    # 32 RandomAgents (about 29 place at their first update), then 64 events of a Noise member: the queue's 8 slots run out
+    # inside the RandomAgents member
+    members = [("random", 32, (32, 64), (10, 20), 2, 0.9), ("noise", 0, 32, dict(NOISE, p_limit=1.0, p_market=1.0))]
     for strict in (True, False):
         env = ingress_env(bk, torch, B, 2, 128, 0, 8, strict=strict, n_orders=256)
         env.set_agents(members)
@@ -343,9 +345,43 @@ def test_a_short_queue_and_an_off_tick_price_are_flagged(bk, oracle):
             assert (env.flags() & bk._lib.FLAG_EVENT_OVERFLOW).all()
             assert all(env.order_count(b) == 8 for b in range(B))  # a dropped New uses no id
             for b in range(B):
-                assert len(env.member_orders(b, 0)) <= 8  # ... and enters no list
+                assert len(env.member_orders(b, 1)) == 0  # ... and enters no list
+            # the drop rule: a fresh env's first update (nobody holds an id, the lists are empty) takes the oracle's draws
+            # whether an event fits or not, and queues exactly the first `room` placements, in agent order
+            for b in range(B):
+                ref, aset = oracle.StepEnv(SEED + b, 0, 2, STEP), oracle.AgentSet(members)
+                aset.update(ref)
+                held, want = _member_ids(oracle, aset, 0), ref.book.orders_array()
+                assert int((held != U64_MAX).sum()) > 8, (b, held)  # the queue overflows inside the RandomAgents member
+                assert env.rng_state(b) == tuple(int(x) for x in ref.rng_state()), b
+                got = env.orders(b)
+                for f in ("side", "price", "vol", "trader_id"):
+                    assert np.array_equal(got[f], want[f][:8]), (b, f, got[f], want[f][:8])
+                # ids 0 .. 7 with the oracle's first 8 placing agents, None with everybody else
+                assert np.array_equal(env.member_orders(b, 0), np.where(held < 8, held, U64_MAX)), (b, held)
         env.step()
         env.close()
+    # the same queue under a Noise member alone (64 events per update): it runs out inside the member's own loop, with a
+    # partly filled batch in place_new / flush_new
+    alone = [members[1]]
+    env = ingress_env(bk, torch, B, 2, 128, 0, 8, strict=False, n_orders=256)
+    env.set_agents(alone)
+    env.update_members()
+    assert (env.flags() & bk._lib.FLAG_EVENT_OVERFLOW).all()
+    for b in range(B):
+        ref, aset = oracle.StepEnv(SEED + b, 0, 2, STEP), oracle.AgentSet(alone)
+        aset.update(ref)
+        want, listed = ref.book.orders_array(), aset.order_list(0)
+        assert len(want) > 8, (b, len(want))
+        assert env.order_count(b) == 8, b  # a dropped New uses no id
+        assert env.rng_state(b) == tuple(int(x) for x in ref.rng_state()), b
+        got = env.orders(b)
+        for f in ("side", "price", "vol", "trader_id"):
+            assert np.array_equal(got[f], want[f][:8]), (b, f, got[f], want[f][:8])
+        ids = env.member_orders(b, 0)
+        assert 0 < len(ids) <= 8 and np.array_equal(ids, listed[listed < 8]), (b, ids, listed)  # ... and enters no list
+    env.step()
+    env.close()
     # every sell limit lands on the u32::MAX clamp, which the book's tick 2 does not divide (mixed_create's rule: flagged,
     # nothing created); the oracle creates nothing either, and everything else stays equal
     far = [("noise", 0, 16, dict(NOISE, p_limit=1.0, price_dist_mu=25.0, price_dist_sigma=0.0))]
