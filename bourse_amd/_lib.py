@@ -139,6 +139,8 @@ SIGNATURES = {
     "bk_step_async": (_i32, [_vp]),
     "bk_update_agents": (_i32, [_vp]),
     "bk_update_members": (_i32, [_vp]),
+    "bk_update_market_agents": (_i32, [_vp]),
+    "bk_update_market_members": (_i32, [_vp]),
     "bk_member_orders": (_i32, [_vp, _u32, _u32, _u32, _p64, _p32]),
     "bk_ingress_staging": (_i32, [_vp, _u64, C.POINTER(IngressArrays)]),
     "bk_submit_instructions_host": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _p64]),

@@ -110,6 +110,9 @@ inline int make_group_table(const bk_random_agents* rows, uint32_t n_units, uint
 // ---------------------------------------------------------------------------------------------------------------
 // AgentSets with Noise / Momentum members (mixed_agents.hpp, wave_mixed.hpp)
 constexpr int MAX_MEMBERS = 4;
+// ... and on an env with the device ingress, whose update kernels (members_ingress.hpp, market_ingress.hpp) walk the
+// members row by row and keep nothing per member in registers: bk_run's kernels, which hold MAX_MEMBERS, never run there
+constexpr int MAX_INGRESS_MEMBERS = 8;
 constexpr int MAX_ASSETS = 8;  // books per market (MarketEnv<ASSETS>)
 
 struct MixedDesc {
@@ -132,8 +135,12 @@ inline uint64_t fnv1a_bytes(const void* p, size_t n, uint64_t h = 14695981039346
   return h;
 }
 // the checkpoint header's agent-set hash of n MixedDesc records and the members' assets (member_asset[MAX_MEMBERS])
-inline uint64_t mixed_hash(const uint32_t* member_asset, const MixedDesc* d, size_t n) {
-  return fnv1a_bytes(member_asset, MAX_MEMBERS * sizeof(uint32_t), fnv1a_bytes(d, n * sizeof(MixedDesc)));
+// (member_asset[MAX_INGRESS_MEMBERS]; the assets of members beyond MAX_MEMBERS are hashed only where there are such members)
+inline uint64_t mixed_hash(const uint32_t* member_asset, const MixedDesc* d, size_t n, uint32_t n_members = 0) {
+  uint64_t h = fnv1a_bytes(member_asset, MAX_MEMBERS * sizeof(uint32_t), fnv1a_bytes(d, n * sizeof(MixedDesc)));
+  if (n_members > static_cast<uint32_t>(MAX_MEMBERS))
+    h = fnv1a_bytes(member_asset + MAX_MEMBERS, (MAX_INGRESS_MEMBERS - MAX_MEMBERS) * sizeof(uint32_t), h);
+  return h;
 }
 
 // One row of members: n_members records into out[0 .. n_members), the fixed RandomAgents slots of each asset's books into

@@ -127,15 +127,16 @@ __device__ __forceinline__ void random_agent(Walk& W, RandomPass& S, const Param
   }
 }
 
-// the pass's records, in agent order; returns what the lane's agent holds now (`h` for an inactive one)
-__device__ __forceinline__ uint32_t random_pass_end(const Walk& W, const RandomPass& S, uint32_t h) {
+// the pass's records, in agent order; returns what the lane's agent holds now (`h` for an inactive one).  `tag`: what a
+// market's queue carries in the event word beside the kind, asset << 16 (k_ingest's layout; 0 on independent books)
+__device__ __forceinline__ uint32_t random_pass_end(const Walk& W, const RandomPass& S, uint32_t h, uint32_t tag = 0u) {
   const uint32_t at = W.q0 + S.ev0 + lane_rank(S.canm | S.newm), id = S.id0 + lane_rank(S.newm);
   const bool is_new = lane_bit(S.newm), is_can = lane_bit(S.canm);
   const uint32_t bid = lane_bit(S.bidm) ? 1u : 0u;
   const uint32_t now = is_new ? id : (is_can || lane_bit(S.dropm)) ? AGENT_HELD_NONE : h;
-  if (is_can) W.q[at] = make_uint4(1u, h, 0u, 0u);
+  if (is_can) W.q[at] = make_uint4(1u | tag, h, 0u, 0u);
   if (is_new) {
-    W.q[at] = make_uint4(bid << 8, id, S.price, S.vol);
+    W.q[at] = make_uint4((bid << 8) | tag, id, S.price, S.vol);
     write_new_order(W.rec, id, S.vol, S.trader, S.price, bid);
   }
   return now;

@@ -48,6 +48,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "step_events.hpp"
 #include "agents_ingress.hpp"
 #include "members_ingress.hpp"
+#include "market_ingress.hpp"
 #include "book_reset.hpp"
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
@@ -213,7 +214,7 @@ struct bk_env {
   DevBuf<uint64_t> gather_buf;  // n_books u64: gather_header()
   bool fsm_attr_set = false;  // same for k_agents_fsm (its LDS is dynamic: book_device.hpp)
   bool ml_valid = false;  // the lists describe the pool as of steps_done (false after a wave-per-book launch / restore)
-  uint32_t member_asset[MAX_MEMBERS] = {0, 0, 0, 0};
+  uint32_t member_asset[MAX_INGRESS_MEMBERS] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t n_fixed_a[MAX_ASSETS] = {0, 0, 0, 0, 0, 0, 0, 0};
   MixedLists lists() const {
     return MixedLists{ml_list.p, ml_len.p, ml_inl.p, static_cast<uint32_t>(R) * 64u, cfg.n_books, cfg.n_books / M};
@@ -1686,6 +1687,48 @@ int bk_step_async(bk_env* env) {
   return BK_OK;
 }
 
+// The held ids of the installed RandomAgents, one row per unit (book, or market when assets > 1), made at the first update
+// after an install: every agent holds None; the old orders stay on the books, unowned.
+static int make_agent_held(bk_env* env) {
+  if (!env->agent_held_stale) return BK_OK;
+  const size_t n = static_cast<size_t>(env->cfg.n_books / env->M) * env->n_agents_total;
+  HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
+  HIPCHK(env->agent_held.alloc(n));
+  if (n) HIPCHK(hipMemset(env->agent_held.p, 0xFF, n * 4));
+  if (env->table.empty()) {
+    HIPCHK(env->agent_groups.alloc(env->groups.size()));
+    HIPCHK(hipMemcpy(env->agent_groups.p, env->groups.data(), env->groups.size() * sizeof(Group), hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(env->agent_groups.alloc(0));
+  }
+  env->agent_held_stale = false;
+  return BK_OK;
+}
+
+// The members' lists, lengths and momentum state, one row per unit and member, made at the first update after an install:
+// empty lists, no momentum state; the old orders stay, unowned.
+static int make_member_rows(bk_env* env) {
+  if (!env->member_lists_stale) return BK_OK;
+  const size_t units = env->cfg.n_books / env->M;
+  HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
+  uint32_t max_n = 0;
+  for (uint32_t n : env->member_n) max_n = std::max(max_n, n);
+  env->member_list_cap = bkd::ingress::members_list_cap(static_cast<uint32_t>(env->R), max_n);
+  const size_t rows = units * env->n_mixed;
+  HIPCHK(env->member_lists.alloc(rows * env->member_list_cap));
+  HIPCHK(env->member_lens.alloc(rows));
+  HIPCHK(env->member_state.alloc(rows * 2));
+  HIPCHK(env->member_flags.alloc(units));
+  HIPCHK(env->member_id0_dev.alloc(env->member_id0.size()));
+  HIPCHK(hipMemset(env->member_lists.p, 0xFF, rows * env->member_list_cap * 4));  // (a RandomAgents member's agents hold None)
+  HIPCHK(hipMemset(env->member_lens.p, 0, rows * 4));
+  HIPCHK(hipMemset(env->member_state.p, 0, rows * 16));
+  HIPCHK(hipMemset(env->member_flags.p, 0, units * 4));
+  HIPCHK(hipMemcpy(env->member_id0_dev.p, env->member_id0.data(), env->member_id0.size() * 4, hipMemcpyHostToDevice));
+  env->member_lists_stale = false;
+  return BK_OK;
+}
+
 // agents.update(env, rng) (random_agent.rs:85-119) of the installed RandomAgents for every book, into the device-resident
 // queues at this point of the book's stream (agents_ingress.hpp k_update_agents), asynchronous on the env's stream.  The
 // agents only place and cancel: they never queue a modification, so k_ingest's hint for k_step_events stays as it is.
@@ -1701,18 +1744,7 @@ int bk_update_agents(bk_env* env) {
   if (env->groups.empty()) return fail(BK_INVALID_ARGUMENT, "no RandomAgents groups installed (bk_set_random_agents)");
   if (int rc = use_device(env)) return rc;
   const uint32_t B = env->cfg.n_books, NA = env->n_agents_total;
-  if (env->agent_held_stale) {  // agents (re)installed: every agent holds None; the old orders stay on the books, unowned
-    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
-    HIPCHK(env->agent_held.alloc(static_cast<size_t>(B) * NA));
-    if (NA) HIPCHK(hipMemset(env->agent_held.p, 0xFF, static_cast<size_t>(B) * NA * 4));
-    if (env->table.empty()) {
-      HIPCHK(env->agent_groups.alloc(env->groups.size()));
-      HIPCHK(hipMemcpy(env->agent_groups.p, env->groups.data(), env->groups.size() * sizeof(Group), hipMemcpyHostToDevice));
-    } else {
-      HIPCHK(env->agent_groups.alloc(0));
-    }
-    env->agent_held_stale = false;
-  }
+  if (int rc = make_agent_held(env)) return rc;
   AgentsIngressArgs g{};
   g.io = env->ingress_args();
   g.n_agents = NA;
@@ -1746,24 +1778,7 @@ int bk_update_members(bk_env* env) {
   }
   if (int rc = use_device(env)) return rc;
   const uint32_t B = env->cfg.n_books, NM = env->n_mixed;
-  if (env->member_lists_stale) {  // members (re)installed: empty lists, no momentum state; the old orders stay, unowned
-    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier launch may still read the buffers replaced here)
-    uint32_t max_n = 0;
-    for (uint32_t n : env->member_n) max_n = std::max(max_n, n);
-    env->member_list_cap = bkd::ingress::members_list_cap(static_cast<uint32_t>(env->R), max_n);
-    const size_t rows = static_cast<size_t>(B) * NM;
-    HIPCHK(env->member_lists.alloc(rows * env->member_list_cap));
-    HIPCHK(env->member_lens.alloc(rows));
-    HIPCHK(env->member_state.alloc(rows * 2));
-    HIPCHK(env->member_flags.alloc(B));
-    HIPCHK(env->member_id0_dev.alloc(env->member_id0.size()));
-    HIPCHK(hipMemset(env->member_lists.p, 0xFF, rows * env->member_list_cap * 4));  // (a RandomAgents member's agents hold None)
-    HIPCHK(hipMemset(env->member_lens.p, 0, rows * 4));
-    HIPCHK(hipMemset(env->member_state.p, 0, rows * 16));
-    HIPCHK(hipMemset(env->member_flags.p, 0, static_cast<size_t>(B) * 4));
-    HIPCHK(hipMemcpy(env->member_id0_dev.p, env->member_id0.data(), env->member_id0.size() * 4, hipMemcpyHostToDevice));
-    env->member_lists_stale = false;
-  }
+  if (int rc = make_member_rows(env)) return rc;
   bkd::ingress::MembersIngressArgs g{};
   g.io = env->ingress_args();
   g.n_members = NM;
@@ -1785,6 +1800,82 @@ int bk_update_members(bk_env* env) {
   return BK_OK;
 }
 
+// RandomMarketAgents::update (random_agent.rs:204-245) of the groups installed by bk_set_random_market_agents or the
+// per-market table of bk_set_random_agents_per_book, for every market, into the market's device-resident queue at this
+// point of its stream (market_ingress.hpp k_update_market_agents), asynchronous on the env's stream.  An env of one asset
+// is a market of one book: there this entry and bk_update_agents share the held ids and are interchangeable step by step.
+int bk_update_market_agents(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_market_agents queues the agents' orders in the device-resident queues: call "
+                                     "bk_device_ingress_enable first");
+  if (env->n_mixed)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_market_agents runs RandomMarketAgents only: this env has a set with Noise / "
+                                     "Momentum members, which bk_update_market_members runs");
+  if (env->groups.empty())
+    return fail(BK_INVALID_ARGUMENT, "no RandomMarketAgents groups installed (bk_set_random_market_agents)");
+  if (int rc = use_device(env)) return rc;
+  if (int rc = make_agent_held(env)) return rc;
+  bkd::ingress::MarketAgentsArgs g{};
+  g.io = env->ingress_args();
+  g.assets = env->M;
+  g.n_agents = env->n_agents_total;
+  g.n_groups = static_cast<uint32_t>(env->groups.size());
+  g.groups = env->table.empty() ? env->agent_groups.p : env->dtable.p;
+  g.g_stride = env->table.empty() ? 0u : g.n_groups;
+  g.held = env->agent_held.p;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(bkd::ingress::k_update_market_agents<decltype(r)::value>, dim3(env->cfg.n_books / env->M), dim3(64), 0,
+                       env->stream, g);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;
+  return BK_OK;
+}
+
+// MarketAgent::update of the set installed by bk_set_market_agents or bk_set_agents_per_book - NoiseMarketAgent
+// (noise_agent.rs:226-340), MomentumMarketAgent (momentum_agent.rs:282-397) and RandomMarketAgents members, in declaration
+// order - for every market, into the market's device-resident queue at this point of its stream (market_ingress.hpp
+// k_update_market_members), asynchronous on the env's stream.  On an env of one asset it shares the lists and the
+// momentum state with bk_update_members.
+int bk_update_market_members(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "bk_update_market_members queues the members' orders in the device-resident queues: call "
+                                     "bk_device_ingress_enable first");
+  if (!env->n_mixed) {
+    if (!env->groups.empty())
+      return fail(BK_INVALID_ARGUMENT, "this env has RandomMarketAgents groups only (bk_set_random_market_agents*): they are "
+                                       "run by bk_update_market_agents");
+    return fail(BK_INVALID_ARGUMENT, "no MarketAgentSet installed (bk_set_market_agents / bk_set_agents_per_book)");
+  }
+  if (int rc = use_device(env)) return rc;
+  if (int rc = make_member_rows(env)) return rc;
+  bkd::ingress::MarketMembersArgs g{};
+  g.io = env->ingress_args();
+  g.assets = env->M;
+  for (int i = 0; i < MAX_ASSETS; ++i) g.asset_tick[i] = env->asset_tick[i];
+  for (uint32_t j = 0; j < env->n_mixed; ++j) g.member_assets |= static_cast<uint64_t>(env->member_asset[j]) << (8u * j);
+  g.n_members = env->n_mixed;
+  g.descs = env->mtable.empty() ? env->mixed_descs.p : env->dmtable.p;
+  g.id_start = env->member_id0_dev.p;
+  g.d_stride = env->mtable.empty() ? 0u : env->n_mixed;
+  g.list_cap = env->member_list_cap;
+  g.lists = env->member_lists.p;
+  g.lens = env->member_lens.p;
+  g.mstate = env->member_state.p;
+  g.mflags = env->member_flags.p;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(bkd::ingress::k_update_market_members<decltype(r)::value>, dim3(env->cfg.n_books / env->M), dim3(64), 0,
+                       env->stream, g);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;
+  return BK_OK;
+}
+
 // Member `member`'s `orders` vector of one book as the device holds it after the last bk_update_members (the ids a
 // RandomAgents member's agents hold, u64::MAX for None): *n_out = its length, the first min(cap, length) ids in out_ids.
 int bk_member_orders(bk_env* env, uint32_t book, uint32_t member, uint32_t cap, uint64_t* out_ids, uint32_t* n_out) {
@@ -1799,7 +1890,7 @@ int bk_member_orders(bk_env* env, uint32_t book, uint32_t member, uint32_t cap, 
   std::vector<uint32_t> ids(n, AGENT_HELD_NONE);
   if (!env->member_lists_stale) {  // (stale: installed and not yet updated - empty lists, every agent holds None)
     HIPCHK(hipStreamSynchronize(env->stream));
-    const size_t row = static_cast<size_t>(book) * env->n_mixed + member;
+    const size_t row = static_cast<size_t>(book / env->M) * env->n_mixed + member;  // (a market's rows: ids of the member's asset)
     if (!random) HIPCHK(hipMemcpy(&n, env->member_lens.p + row, 4, hipMemcpyDeviceToHost));
     n = std::min(n, env->member_list_cap);
     ids.resize(n);
@@ -1920,6 +2011,15 @@ int bk_set_tick_sizes(bk_env* env, uint32_t n, const uint32_t* tick_sizes) {
 }
 
 static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets);
+// bk_run's kernels hold MAX_MEMBERS members; on an env with the device ingress, where only bk_update_members /
+// bk_update_market_members run the set, MAX_INGRESS_MEMBERS
+static int member_count_ok(const bk_env* env, uint32_t n_members) {
+  if (n_members <= static_cast<uint32_t>(MAX_MEMBERS)) return BK_OK;
+  if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "at most 4 members in a set with Noise/Momentum agents");
+  if (n_members > static_cast<uint32_t>(MAX_INGRESS_MEMBERS))
+    return fail(BK_INVALID_ARGUMENT, "at most 8 members in a set with Noise/Momentum agents on a device-ingress env");
+  return BK_OK;
+}
 static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32_t n_members, const uint32_t* assets,
                            const uint32_t* fixed_a, std::vector<MixedDesc> table);
 
@@ -1948,7 +2048,7 @@ static int set_agents_impl(bk_env* env, uint32_t n_members, const bk_agent_desc*
                               members[i].vol_hi, members[i].tick_size, members[i].activity_rate};
     return bk_set_random_market_agents(env, n_members, g.data(), assets);
   }
-  if (n_members > MAX_MEMBERS) return fail(BK_INVALID_ARGUMENT, "at most 4 members in a set with Noise/Momentum agents");
+  if (int rc = member_count_ok(env, n_members)) return rc;
   if (env->agent_log)
     return fail(BK_INVALID_ARGUMENT, "the agents' order log (bk_set_agent_order_log) records RandomAgents only: "
                                      "a set with Noise / Momentum members cannot be installed on a logging env");
@@ -1985,7 +2085,7 @@ static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32
   env->member_lists_stale = true;  // (a new AgentSet: empty lists, no momentum state; bk_update_members)
   env->agent_installs += 1;
   env->wl_valid = false;
-  for (uint32_t i = 0; i < MAX_MEMBERS; ++i) env->member_asset[i] = (assets && i < n_members) ? assets[i] : 0u;
+  for (uint32_t i = 0; i < MAX_INGRESS_MEMBERS; ++i) env->member_asset[i] = (assets && i < n_members) ? assets[i] : 0u;
   for (uint32_t as = 0; as < MAX_ASSETS; ++as) env->n_fixed_a[as] = fixed_a[as];
   env->ml_valid = false;
   env->groups.clear();
@@ -1995,8 +2095,8 @@ static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32
   std::swap(env->dmtable.p, dt.p);  // (the previous table, if any, is freed with `dt`)
   std::swap(env->dmtable.n, dt.n);
   env->mtable.swap(table);
-  env->agents_hash = env->mtable.empty() ? mixed_hash(env->member_asset, ds.data(), ds.size())
-                                         : mixed_hash(env->member_asset, env->mtable.data(), env->mtable.size());
+  env->agents_hash = env->mtable.empty() ? mixed_hash(env->member_asset, ds.data(), ds.size(), n_members)
+                                         : mixed_hash(env->member_asset, env->mtable.data(), env->mtable.size(), n_members);
   return BK_OK;
 }
 
@@ -2022,7 +2122,7 @@ int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc*
                               members[k].vol_hi, members[k].tick_size, members[k].activity_rate};
     return bk_set_random_agents_per_book(env, n_members, g.data(), assets);
   }
-  if (n_members > MAX_MEMBERS) return fail(BK_INVALID_ARGUMENT, "at most 4 members in a set with Noise/Momentum agents");
+  if (int rc = member_count_ok(env, n_members)) return rc;
   if (env->agent_log)
     return fail(BK_INVALID_ARGUMENT, "the agents' order log (bk_set_agent_order_log) records RandomAgents only: "
                                      "a set with Noise / Momentum members cannot be installed on a logging env");
@@ -3042,8 +3142,8 @@ int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const u
 // the order records of the ids it has handed out, the held ids of bk_update_agents and the lists and momentum state of
 // bk_update_members - all rewound here, on the device (ingress_reset.hpp).  The slots are the env's
 // isnaps, apart from bk_snapshot_save's.
-static bool held_active(const bk_env* env) { return env->M == 1 && !env->n_mixed && !env->groups.empty(); }
-static bool members_active(const bk_env* env) { return env->M == 1 && env->n_mixed != 0; }
+static bool held_active(const bk_env* env) { return !env->n_mixed && !env->groups.empty(); }
+static bool members_active(const bk_env* env) { return env->n_mixed != 0; }
 
 static int ingress_slot_ok(bk_env* env, uint32_t slot) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
@@ -3073,9 +3173,10 @@ static bool ingress_record_args(const bk_env* env, uint32_t n_keep, reset::Recor
     }
     g.list_cap = bkd::ingress::members_list_cap(static_cast<uint32_t>(env->R), max_n);  // (as bk_update_members sizes a row)
   }
-  const uint64_t s_book = uint64_t(reset::segs(n_keep * reset::ORD_V, reset::SEG_V)) + reset::segs(n_keep * reset::LOG_V, reset::SEG_V) +
-                          reset::segs(g.n_agents, reset::SEG_DW) + uint64_t(g.n_members) * reset::segs(g.list_cap, reset::SEG_DW);
-  return s_book * env->cfg.n_books < 0xFFFFFFFFull;
+  // (the order records are rows per book, the agents' and members' rows per unit)
+  const uint64_t s_book = uint64_t(reset::segs(n_keep * reset::ORD_V, reset::SEG_V)) + reset::segs(n_keep * reset::LOG_V, reset::SEG_V);
+  const uint64_t s_rows = reset::segs(g.n_agents, reset::SEG_DW) + uint64_t(g.n_members) * reset::segs(g.list_cap, reset::SEG_DW);
+  return (s_book * env->M + s_rows) * g.n_units < 0xFFFFFFFFull;
 }
 
 uint64_t bk_ingress_snapshot_bytes(const bk_env* env, uint32_t slot) {
@@ -3133,23 +3234,23 @@ int bk_ingress_snapshot_save(bk_env* env, uint32_t slot) {
   s.bytes = (sb + lb) * 4 + B * s.keep_cap * (reset::ORD_V + reset::LOG_V) * 16;
   s.held_saved = held_active(env) && !env->agent_held_stale;
   if (s.held_saved) {
-    const size_t n = B * env->n_agents_total;
+    const size_t n = n_units * env->n_agents_total;
     if (s.held.n != n) HIPCHK(s.held.alloc(n));
     if (n) HIPCHK(hipMemcpyAsync(s.held.p, env->agent_held.p, n * 4, hipMemcpyDeviceToDevice, env->stream));
     s.bytes += n * 4;
   }
   s.members_saved = members_active(env) && !env->member_lists_stale;
   if (s.members_saved) {
-    const size_t rows = B * env->n_mixed, nl = rows * env->member_list_cap;
+    const size_t rows = n_units * env->n_mixed, nl = rows * env->member_list_cap;
     if (s.lists.n != nl) HIPCHK(s.lists.alloc(nl));
     if (s.lens.n != rows) HIPCHK(s.lens.alloc(rows));
     if (s.mstate.n != rows * 2) HIPCHK(s.mstate.alloc(rows * 2));
-    if (s.mflags.n != B) HIPCHK(s.mflags.alloc(B));
+    if (s.mflags.n != n_units) HIPCHK(s.mflags.alloc(n_units));
     HIPCHK(hipMemcpyAsync(s.lists.p, env->member_lists.p, nl * 4, hipMemcpyDeviceToDevice, env->stream));
     HIPCHK(hipMemcpyAsync(s.lens.p, env->member_lens.p, rows * 4, hipMemcpyDeviceToDevice, env->stream));
     HIPCHK(hipMemcpyAsync(s.mstate.p, env->member_state.p, rows * 16, hipMemcpyDeviceToDevice, env->stream));
-    HIPCHK(hipMemcpyAsync(s.mflags.p, env->member_flags.p, B * 4, hipMemcpyDeviceToDevice, env->stream));
-    s.bytes += nl * 4 + rows * 20 + B * 4;
+    HIPCHK(hipMemcpyAsync(s.mflags.p, env->member_flags.p, n_units * 4, hipMemcpyDeviceToDevice, env->stream));
+    s.bytes += nl * 4 + rows * 20 + n_units * 4;
   }
   uint64_t h[CKPT_HDR];
   ckpt_header(env, h);

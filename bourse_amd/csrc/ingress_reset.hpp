@@ -7,11 +7,11 @@
 //     H_NEXT_ID of b, max_orders)                                        -> the snapshot's (stored as [n_books][n_keep], n_keep =
 //     the largest keep_b); records at ids >= the snapshot's H_NEXT_ID need nothing: every reader stops at H_NEXT_ID, and
 //     they are overwritten as the ids are handed out again;
-//   * bk_update_agents' agent_held[b][n_agents]                          -> the snapshot's row, or None (0xFFFFFFFF) in every
-//     entry if the env had not made the buffer at the save;
-//   * bk_update_members' member_lists[b][n_members][list_cap], member_lens[b][n_members], member_state[b][n_members][2],
-//     member_flags[b]                                                    -> the snapshot's rows, or the state of a first update
-//     (lengths 0, state 0, flags 0, every list entry None);
+//   * bk_update_agents' / bk_update_market_agents' agent_held[u][n_agents] -> the snapshot's row, or None (0xFFFFFFFF) in every
+//     entry if the env had not made the buffer at the save (u: the unit - the book, or the market);
+//   * bk_update_members' / bk_update_market_members' member_lists[u][n_members][list_cap], member_lens[u][n_members],
+//     member_state[u][n_members][2], member_flags[u]                     -> the snapshot's rows, or the state of a first
+//     update (lengths 0, state 0, flags 0, every list entry None);
 //   * wcache: NOTHING.  WaveDecoder::load_cache validates the cached record against the book's RNG words, which rewind
 //     (or are re-seeded) with the state block, so a stale record is rejected and decoded again.
 //
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_collect_units(CollectArgs g) {
   if (!on) return;
   g.list[base + static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)))] = u;
   g.dqlen[u] = 0u;
-  if (g.n_members) {  // (members run on independent books: M == 1, the unit is the book)
+  if (g.n_members) {  // (the members' rows are per unit: a book, or a market)
     for (uint32_t j = 0; j < g.n_members; ++j) {
       const size_t row = static_cast<size_t>(u) * g.n_members + j;
       g.lens[row] = g.snap_lens ? g.snap_lens[row] : 0u;
@@ -120,7 +120,7 @@ struct RecordArgs {
   // member's row the snapshot's length moves (snap_lens), of a RandomAgents member's (bit j of random_mask) the whole
   // row of its agents' held ids (member_n[j])
   uint32_t n_members, list_cap, random_mask;
-  uint32_t member_n[MAX_MEMBERS];
+  uint32_t member_n[MAX_INGRESS_MEMBERS];
   uint32_t* lists;
   const uint32_t* snap_lists;
   const uint32_t* snap_lens;
@@ -161,21 +161,22 @@ __global__ __launch_bounds__(64 * RECORD_WAVES) void k_reset_records(RecordArgs 
   const uint32_t wave = rfl(blockIdx.x * RECORD_WAVES + (threadIdx.x >> 6));
   const uint32_t n_waves = gridDim.x * RECORD_WAVES;
   const uint32_t n_list = g.list ? rfl(*g.count) : g.n_units;
-  // the segments of one book, in this order: dorders, order_log, agent_held, the members' lists (the host checks that
-  // n_units * M * s_book fits 32 bits)
+  // the segments of one unit, in this order: dorders and order_log of each of its M books, then the unit's agent_held
+  // row and its members' lists (the host checks that n_units * s_unit fits 32 bits)
   const uint32_t s_ord = segs(g.n_keep * ORD_V, SEG_V), s_log = segs(g.n_keep * LOG_V, SEG_V);
   const uint32_t s_held = segs(g.n_agents, SEG_DW), s_row = segs(g.list_cap, SEG_DW);
-  const uint32_t s_book = s_ord + s_log + s_held + g.n_members * s_row;
-  const uint32_t s_unit = g.M * s_book;
+  const uint32_t s_book = s_ord + s_log;
+  const uint32_t s_unit = g.M * s_book + s_held + g.n_members * s_row;
   if (s_unit == 0) return;
   const uint32_t total = n_list * s_unit;
   for (uint32_t w = wave; w < total; w += n_waves) {
     const uint32_t e = w / s_unit, r = w - e * s_unit;
-    const uint32_t a = r / s_book;
-    uint32_t s = r - a * s_book;
     const uint32_t u = g.list ? rfl(g.list[e]) : e;
-    const size_t b = static_cast<size_t>(u) * g.M + a;
-    if (s < s_ord + s_log) {
+    uint32_t s = r;
+    if (r < g.M * s_book) {
+      const uint32_t a = r / s_book;
+      s = r - a * s_book;
+      const size_t b = static_cast<size_t>(u) * g.M + a;
       const uint32_t keep = min(rfl(g.keep_state[b * g.stride + H_NEXT_ID]), g.max_orders);
       if (s < s_ord) {
         move_vectors(g.dst_orders + b * g.dst_ids * ORD_V, g.src_orders + b * g.src_ids * ORD_V, s * SEG_V, keep * ORD_V, lane);
@@ -185,15 +186,16 @@ __global__ __launch_bounds__(64 * RECORD_WAVES) void k_reset_records(RecordArgs 
       }
       continue;
     }
-    s -= s_ord + s_log;
+    s -= g.M * s_book;
+    const size_t un = u;
     if (s < s_held) {
-      move_dwords(g.held + b * g.n_agents, g.snap_held ? g.snap_held + b * g.n_agents : nullptr, s * SEG_DW, g.n_agents, lane);
+      move_dwords(g.held + un * g.n_agents, g.snap_held ? g.snap_held + un * g.n_agents : nullptr, s * SEG_DW, g.n_agents, lane);
       continue;
     }
     s -= s_held;
     const uint32_t j = s / s_row;
     s -= j * s_row;
-    const size_t row = b * g.n_members + j;
+    const size_t row = un * g.n_members + j;
     uint32_t n = g.list_cap;  // (None in every entry)
     if (g.snap_lists) n = (g.random_mask >> j) & 1u ? g.member_n[j] : min(rfl(g.snap_lens[row]), g.list_cap);
     move_dwords(g.lists + row * g.list_cap, g.snap_lists ? g.snap_lists + row * g.list_cap : nullptr, s * SEG_DW, n, lane);

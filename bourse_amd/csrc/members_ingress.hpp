@@ -87,14 +87,15 @@ struct NewBatch {
 };
 
 // the batch's records, dorders halves and first log entries (write_new_order), and the limit orders' ids onto the list
+// (`tag`: random_pass_end's)
 __device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t vol, uint32_t* list, uint32_t& len,
-                                          uint32_t list_cap, int lane) {
+                                          uint32_t list_cap, int lane, uint32_t tag) {
   if (N.cnt == 0) return;
   const bool mine = (uint32_t)lane < N.cnt;
   const uint32_t id = N.id0 + (uint32_t)lane;
   const uint32_t bid = lane_bit(N.bidm) ? 1u : 0u;
   if (mine) {
-    W.q[W.q0 + N.ev0 + (uint32_t)lane] = make_uint4(bid << 8, id, N.price, vol);
+    W.q[W.q0 + N.ev0 + (uint32_t)lane] = make_uint4((bid << 8) | tag, id, N.price, vol);
     write_new_order(W.rec, id, vol, N.trader, N.price, bid);
   }
   const uint32_t rank = lane_rank(N.limm);
@@ -109,7 +110,7 @@ __device__ __forceinline__ void flush_new(const Walk& W, NewBatch& N, uint32_t v
 // mixed_agents.hpp); a market order carries the extreme price of its side (orderbook.rs:595) and takes no check
 __device__ __forceinline__ void place_new(Walk& W, NewBatch& N, bool limit, bool is_bid, uint32_t price, uint32_t trader,
                                           uint32_t tick, uint32_t vol, uint32_t* list, uint32_t& len, uint32_t list_cap,
-                                          int lane) {
+                                          int lane, uint32_t tag) {
   if (limit && price % tick != 0) {
     W.flags |= FLAG_PRICE_TICK;
     return;
@@ -118,7 +119,7 @@ __device__ __forceinline__ void place_new(Walk& W, NewBatch& N, bool limit, bool
     W.flags |= FLAG_EVENT_OVERFLOW;
     return;
   }
-  if (N.cnt == 64u) flush_new(W, N, vol, list, len, list_cap, lane);
+  if (N.cnt == 64u) flush_new(W, N, vol, list, len, list_cap, lane, tag);
   if (N.cnt == 0) {
     N.id0 = W.next_id;
     N.ev0 = W.n_ev;
@@ -165,119 +166,13 @@ __global__ __launch_bounds__(64) void k_update_members(MembersIngressArgs g) {
   uint32_t mflags = rfl(g.mflags[book]);
 
   for (uint32_t j = 0; j < g.n_members; ++j) {
-    const MixedDesc D = sload_desc(row + j);
-    uint32_t* list = g.lists + ((size_t)book * g.n_members + j) * g.list_cap;
-    if (D.type == 0) {
-      // ---- RandomAgents::update (random_agent.rs:85-119): k_update_agents' pass over the member's held ids
-      const uint32_t n_agents = min(D.n, g.list_cap);
-      for (uint32_t base = 0; base < n_agents; base += 64) {
-        const uint32_t n_here = min(64u, n_agents - base);
-        const bool in = (uint32_t)lane < n_here;
-        const uint32_t h = in ? list[base + lane] : AGENT_HELD_NONE;
-        RandomPass S(W);
-        // TraderId = the agent's index in its member
-        for (uint32_t l = 0; l < n_here; ++l) random_agent<R>(W, S, D, pid, h, l, base + l);
-        const uint32_t now = random_pass_end(W, S, h);
-        if (in) list[base + lane] = now;
-      }
-      continue;
-    }
-    // ---- common::cancel_live_orders (common.rs:56-75): the Active entries in list order, one f32 draw each;
-    // `draw > p_cancel` keeps the entry, otherwise its cancellation is queued and it leaves the list
-    const uint32_t len0 = min(rfl(g.lens[(size_t)book * g.n_members + j]), g.list_cap);
-    uint32_t len = 0;
-    for (uint32_t base = 0; base < len0; base += 64) {
-      const bool in = base + (uint32_t)lane < len0;
-      const uint32_t e = in ? list[base + lane] : AGENT_HELD_NONE;
-      uint64_t actm = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (live[r] == 0) continue;
-        for (uint32_t k = 0; k < 64; ++k) actm |= __ballot(e == rdl(pid[r], k));
-      }
-      // (an entry beyond the list, or a pool lane with nothing live, is AGENT_HELD_NONE on both sides)
-      actm &= __ballot(in);
-      const uint32_t ev0 = W.n_ev;
-      uint64_t keepm = 0, canm = 0;
-      for (uint64_t m = actm; m; m &= m - 1ull) {
-        const uint64_t bit = m & (~m + 1ull);
-        const uint32_t x = rng.next_u32();
-        if ((int32_t)(x >> 8) > D.keep_thr) {
-          keepm |= bit;
-        } else if (W.n_ev < W.room) {  // env.cancel_order(id)
-          canm |= bit;
-          W.n_ev += 1;
-        } else {
-          W.flags |= FLAG_EVENT_OVERFLOW;
-        }
-      }
-      const uint32_t rank_can = lane_rank(canm);
-      const uint32_t rank_keep = lane_rank(keepm);
-      if (lane_bit(canm)) W.q[W.q0 + ev0 + rank_can] = make_uint4(1u, e, 0u, 0u);
-      if (lane_bit(keepm)) list[len + rank_keep] = e;  // (len + rank <= base + lane: behind every entry still to be read)
-      len += (uint32_t)__builtin_popcountll(keepm);
-    }
-    // ---- the traders' loops (mixed_update_and_shuffle's, mixed_agents.hpp)
-    const uint32_t trader0 = rfl(id_start[j]);
-    NewBatch N;
-    N.price = N.trader = 0;
-    N.bidm = N.limm = 0;
-    N.cnt = N.id0 = N.ev0 = 0;
-    if (D.type == 1) {
-      // ---- NoiseAgent::update (noise_agent.rs:127-176)
-      for (uint32_t t = 0; t < D.n; ++t) {
-        if ((rng.next_u32() >> 8) < D.thr_limit) {                 // gen::<f32>() < p_limit
-          const bool buy = next_u64(rng) < 0x8000000000000000ull;  // gen_bool(0.5)
-          const double dist = pm::fabs_(uni(pm::exp(D.mu + D.sigma * sample_standard_normal(rng))));
-          const uint32_t price = rfl(buy ? round_price_down(mid - dist, D.tick_f) : round_price_up(mid + dist, D.tick_f));
-          place_new(W, N, true, buy, price, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
-        }
-        if ((rng.next_u32() >> 8) < D.thr_market) {                // gen::<f32>() < p_market
-          const bool buy = next_u64(rng) < 0x8000000000000000ull;
-          place_new(W, N, false, buy, buy ? 0xFFFFFFFFu : 0u, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
-        }
-      }
-    } else {
-      // ---- MomentumAgent::update (momentum_agent.rs:146-208)
-      uint64_t* ms = g.mstate + ((size_t)book * g.n_members + j) * 2;
-      double m = 0.0, p_market = 0.0;
-      if ((mflags >> j) & 1u) {
-        const double gm = uni(pm::from_bits(ms[0])), gl = uni(pm::from_bits(ms[1]));
-        m = uni(gm * (1.0 - D.decay) + D.decay * (mid - gl));
-        p_market = uni(D.demand * pm::tanh(D.scale * m) / D.n_f);
-      }
-      uint64_t thr_l, thr_m;
-      {
-        const double p_limit = D.order_ratio * p_market;
-        thr_l = thr53(p_limit);
-        thr_m = thr53(p_market);
-        thr_l = mk64(rfl((uint32_t)thr_l), rfl((uint32_t)(thr_l >> 32)));
-        thr_m = mk64(rfl((uint32_t)thr_m), rfl((uint32_t)(thr_m >> 32)));
-      }
-      const int sgn = (m > 0.0) ? 1 : ((m < 0.0) ? -1 : 0);
-      for (uint32_t t = 0; t < D.n; ++t) {
-        if ((next_u64(rng) >> 11) < thr_l) {  // gen::<f64>() < p_limit
-          if (sgn != 0) {
-            const double dist = pm::fabs_(uni(pm::exp(D.mu + D.sigma * sample_standard_normal(rng))));
-            const uint32_t price =
-                rfl(sgn > 0 ? round_price_down(mid - dist, D.tick_f) : round_price_up(mid + dist, D.tick_f));
-            place_new(W, N, true, sgn > 0, price, trader0 + t, g.tick, D.trade_vol, list, len, g.list_cap, lane);
-          }
-        }
-        if ((next_u64(rng) >> 11) < thr_m) {  // gen::<f64>() < p_market
-          if (sgn != 0)
-            place_new(W, N, false, sgn > 0, sgn > 0 ? 0xFFFFFFFFu : 0u, trader0 + t, g.tick, D.trade_vol, list, len,
-                      g.list_cap, lane);
-        }
-      }
-      if (lane == 0) {  // momentum, last_price, once per update
-        ms[0] = pm::to_bits(m);
-        ms[1] = pm::to_bits(mid);
-      }
-      mflags |= 1u << j;
-    }
-    flush_new(W, N, D.trade_vol, list, len, g.list_cap, lane);
-    if (lane == 0) g.lens[(size_t)book * g.n_members + j] = min(len, g.list_cap);
+#define BK_MU_UNIT book
+#define BK_MU_TICK g.tick
+#define BK_MU_TAG 0u
+#include "members_update_body.inc"
+#undef BK_MU_UNIT
+#undef BK_MU_TICK
+#undef BK_MU_TAG
   }
   walk_end(W, g.io, st, hdr, lane);
   if (lane == 0) g.mflags[book] = mflags;

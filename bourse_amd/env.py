@@ -340,9 +340,36 @@ class ManyBookEnv:
             if self.strict:
                 self.raise_on_flags()
 
+    def update_market_agents(self, sync: bool = True):
+        """``RandomMarketAgents::update`` (random_agent.rs:204-245) of the groups of ``set_random_market_agents`` /
+        ``set_random_market_agents_per_market`` for every market into the market's device-resident queue
+        (``bk_update_market_agents``): a group of asset ``a`` cancels and places on book ``market * assets + a``, with the
+        market's own RNG, and its events join the submitted instructions in call order; the next ``step()`` trades all of
+        it.  Needs ``enable_device_ingress()`` first, then the agents.  On an env of one asset it shares the held ids with
+        ``update_agents``.  ``sync=False``: queue it on the env's stream and return (no flag check)."""
+        check(self._L.bk_update_market_agents(self._h))
+        if sync:
+            self.sync()
+            if self.strict:
+                self.raise_on_flags()
+
+    def update_market_members(self, sync: bool = True):
+        """``MarketAgent::update`` of the set of ``set_market_agents`` / ``set_market_agents_per_market`` - NoiseMarketAgent
+        (noise_agent.rs:226-340), MomentumMarketAgent (momentum_agent.rs:282-397) and RandomMarketAgents members, in
+        declaration order - for every market into the market's device-resident queue (``bk_update_market_members``), each
+        member on the book of its asset.  Needs ``enable_device_ingress()`` first, then the set (an all-RandomAgents set is
+        ``update_market_agents``').  On an env of one asset it shares the lists and the momentum state with
+        ``update_members``.  ``sync=False``: queue it on the env's stream and return (no flag check)."""
+        check(self._L.bk_update_market_members(self._h))
+        if sync:
+            self.sync()
+            if self.strict:
+                self.raise_on_flags()
+
     def member_orders(self, book: int, member: int) -> np.ndarray:
         """Member ``member``'s ``orders`` vector of one book after the last ``update_members`` (``bk_member_orders``), u64
-        in list order; for a RandomAgents member the ids its agents hold, ``2**64 - 1`` for None."""
+        in list order; for a RandomAgents member the ids its agents hold, ``2**64 - 1`` for None.  On a market it is the
+        list of market ``book // assets``, whose ids are ids of the member's asset's book."""
         n = C.c_uint32(0)
         check(self._L.bk_member_orders(self._h, int(book), int(member), 0, None, C.byref(n)))
         out = np.zeros(max(int(n.value), 1), dtype=np.uint64)

@@ -242,10 +242,35 @@ int bk_update_agents(bk_env* env);
  * BK_INVALID_ARGUMENT (env unchanged): no device ingress, no AgentSet installed (an all-RandomAgents set is
  * bk_update_agents'), assets > 1. */
 int bk_update_members(bk_env* env);
+/* bk_update_market_agents: RandomMarketAgents::update (random_agent.rs:204-245) of the groups installed by
+ * bk_set_random_market_agents (or the per-market table of bk_set_random_agents_per_book) for every market of an env with
+ * the device ingress - background MarketAgents and a user's own agent sharing one MarketEnv and one rng
+ * (runner.rs:108-131).  bk_update_agents' semantics with these changes: a group of asset a tests Active against the pool
+ * of book market * assets + a, takes that book's next id and records its orders in that book's rows; its events go to the
+ * MARKET's queue, tagged with the asset, in call order behind whatever bk_submit_instructions_device or an earlier update
+ * queued; the draws come from the market's RNG, whose advanced state every book of the market receives.  A full queue or
+ * an exhausted id space drops the event and sets BK_FLAG_EVENT_OVERFLOW on the book of the event's asset.  An env of one
+ * asset is a market of one book: there this entry and bk_update_agents share the held ids and may alternate from step to
+ * step.  Asynchronous on the env's stream.
+ * BK_INVALID_ARGUMENT (env unchanged): no device ingress, no groups installed, Noise / Momentum members (they are
+ * bk_update_market_members'). */
+int bk_update_market_agents(bk_env* env);
+/* bk_update_market_members: MarketAgent::update of the set installed by bk_set_market_agents (or bk_set_agents_per_book) -
+ * NoiseMarketAgent (noise_agent.rs:226-340), MomentumMarketAgent (momentum_agent.rs:282-397) and RandomMarketAgents
+ * (random_agent.rs:204-245) members, in declaration order, with the market's own RNG - for every market of an env with the
+ * device ingress.  bk_update_members' semantics, each member on the book of its asset (that book's pool, mid price, tick
+ * size, next id and rows; BK_FLAG_PRICE_TICK and BK_FLAG_EVENT_OVERFLOW on that book), its events in the market's queue
+ * as bk_update_market_agents'.  The lists and the momentum state are kept per market; on an env of one asset they are
+ * bk_update_members' own.  Asynchronous on the env's stream.
+ * BK_INVALID_ARGUMENT (env unchanged): no device ingress, nothing installed, an all-RandomAgents set (it is
+ * bk_update_market_agents'). */
+int bk_update_market_members(bk_env* env);
 /* bk_member_orders: member `member`'s `orders` vector of one book as the device holds it after the last
  * bk_update_members (NoiseAgent.orders / MomentumAgent.orders, noise_agent.rs:104, momentum_agent.rs:114), in list order;
  * for a RandomAgents member the ids its agents hold (RandomAgents.orders, random_agent.rs:49), UINT64_MAX for None.
- * *n_out = the vector's length; the first min(cap, length) ids go to out_ids.  Waits for the env's stream. */
+ * *n_out = the vector's length; the first min(cap, length) ids go to out_ids.  Waits for the env's stream.  On a market
+ * (assets > 1, bk_update_market_members) the list is that of market book / assets, and its ids are ids of the member's
+ * asset's book. */
 int bk_member_orders(bk_env* env, uint32_t book, uint32_t member, uint32_t cap, uint64_t* out_ids, uint32_t* n_out);
 /* HOST arrays through the device ingress (a BaseNumpyAgent-style caller: src/bourse/step_sim/agents/base_agent.py:67-116
  * returns host numpy arrays, runner.py:103-112 passes them to submit_instructions, rust/src/step_sim_numpy.rs:233-275).

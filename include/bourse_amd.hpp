@@ -203,6 +203,10 @@ class ManyEnv {
   void update_agents() { check(bk_update_agents(h_)); }
   // agents.update(env, rng) of an AgentSet with Noise / Momentum members into the same queues (bk_update_members)
   void update_members() { check(bk_update_members(h_)); }
+  // RandomMarketAgents::update / MarketAgent::update of the installed set for every market into the market's queue
+  // (bk_update_market_agents, bk_update_market_members); an env of one asset is a market of one book
+  void update_market_agents() { check(bk_update_market_agents(h_)); }
+  void update_market_members() { check(bk_update_market_members(h_)); }
   // member j's `orders` vector of book b after the last update_members (bk_member_orders; UINT64_MAX = None)
   std::vector<uint64_t> member_orders(uint32_t book, uint32_t member) {
     uint32_t n = 0;
