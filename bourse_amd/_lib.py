@@ -105,6 +105,18 @@ OPEN_ORDER_DTYPE = np.dtype(
     {"names": ["order_id", "price", "vol", "side_is_bid"], "formats": ["<u4", "<u4", "<u4", "<u4"],
      "offsets": [0, 4, 8, 12], "itemsize": 16})
 
+# bk_open_queue: the queue position of one entry of the open-order tables (ManyBookEnv.open_queue)
+OPEN_QUEUE_DTYPE = np.dtype(
+    {"names": ["ahead_vol", "level_ahead_vol", "level_vol", "ahead_orders", "level_ahead_orders"],
+     "formats": ["<u8", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 8, 16, 24, 28], "itemsize": 32})
+
+
+class OpenQueue(C.Structure):
+    """bk_open_queue: one row of the queue table."""
+    _fields_ = [("ahead_vol", C.c_uint64), ("level_ahead_vol", C.c_uint64), ("level_vol", C.c_uint64),
+                ("ahead_orders", C.c_uint32), ("level_ahead_orders", C.c_uint32)]
+
+
 # bk_random_agents (RandomAgentsCfg) as a numpy structured dtype: the rows of ManyBookEnv.set_random_agents_per_book's table
 RANDOM_AGENTS_DTYPE = np.dtype(
     {"names": ["n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate"],
@@ -224,6 +236,9 @@ SIGNATURES = {
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "bk_get_open_orders": (_i32, [_vp, _u32, _u32, _vp, _vp]),
+    "bk_open_queue_enable": (_i32, [_vp]),
+    "bk_open_queue_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_open_queue": (_i32, [_vp, _u32, _u32, _vp]),
 }
 
 _lib = None

@@ -53,6 +53,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
 #include "open_orders.hpp"
+#include "open_queue.hpp"
 
 using namespace bkd;
 
@@ -69,6 +70,9 @@ static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * si
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
               "bk_open_summary / bk_open_order layout (open_orders.hpp)");
+static_assert(sizeof(bk_open_queue) == 32 && sizeof(bk_open_queue) == 2 * sizeof(bk_u32x4) &&
+                  sizeof(open_queue::Row) == sizeof(bk_open_queue) && open_queue::NO_ORDER == open_orders::NO_ORDER,
+              "bk_open_queue layout (open_queue.hpp)");
 static_assert(sizeof(DevTrade) == 32 && sizeof(DevOrderLog) == 48 && sizeof(uint4) == 16, "device record layout");
 
 namespace {
@@ -175,6 +179,8 @@ struct bk_env {
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
   uint32_t open_traders = 0, open_depth = 0;  // open_traders == 0: no view
+  // bk_open_queue_enable: the queue position of every entry above, recomputed right behind them (open_queue.hpp)
+  DevBuf<bk_u32x4> open_queue;  // [n_books][open_traders][open_depth][2]; empty: no queue view
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -1664,6 +1670,31 @@ static void launch_open_orders_refresh(bk_env* env, const uint8_t* mask_dev, uin
   });
 }
 
+// the queue rows of the masked books from their pools and the entries the open-order refresh in front of it wrote: one
+// launch, no allocation, no stream wait, no host read
+static void launch_open_queue_refresh(bk_env* env, const uint8_t* mask_dev, uint32_t M) {
+  open_queue::RefreshArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.entries = env->open_entries.p;
+  g.queue = env->open_queue.p;
+  g.n_entries = env->open_traders * env->open_depth;  // (<= 65536 * 64)
+  const uint32_t blocks = (g.n_books + open_queue::REFRESH_WAVES - 1) / open_queue::REFRESH_WAVES;
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(open_queue::k_refresh<decltype(r)::value>, dim3(blocks), dim3(64 * open_queue::REFRESH_WAVES), 0,
+                       env->stream, g);
+  });
+}
+
+// both tables of the open-order view: the rows, then - for an env with the queue view - their queue positions
+static void launch_open_refresh(bk_env* env, const uint8_t* mask_dev, uint32_t M) {
+  launch_open_orders_refresh(env, mask_dev, M);
+  if (env->open_queue.p) launch_open_queue_refresh(env, mask_dev, M);
+}
+
 int bk_step_async(bk_env* env) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_step_async steps the device-resident queues: call bk_device_ingress_enable first");
@@ -1678,7 +1709,7 @@ int bk_step_async(bk_env* env) {
     HIPCHK(hipGetLastError());
   }
   if (env->open_traders) {  // open orders: the pools as this step left them
-    launch_open_orders_refresh(env, nullptr, 1);
+    launch_open_refresh(env, nullptr, 1);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemsetAsync(env->dqlen.p, 0, static_cast<size_t>(env->cfg.n_books / env->M) * 4, env->stream));
@@ -3348,7 +3379,7 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
     HIPCHK(hipGetLastError());
   }
   if (env->open_traders) {  // the reset books show the snapshot's resting orders before their next step
-    launch_open_orders_refresh(env, mask_dev, env->M);
+    launch_open_refresh(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
   }
   env->ingest_epoch += 1;  // the readers' mirrors of the orders and the log fetch from the device again
@@ -3463,7 +3494,7 @@ int bk_open_orders_enable(bk_env* env, uint32_t n_traders, uint32_t depth) {
   std::swap(env->open_entries.p, entries.p), std::swap(env->open_entries.n, entries.n);
   env->open_traders = n_traders;
   env->open_depth = depth;
-  launch_open_orders_refresh(env, nullptr, 1);
+  launch_open_refresh(env, nullptr, 1);
   HIPCHK(hipGetLastError());
   return BK_OK;
 }
@@ -3478,7 +3509,7 @@ static int open_orders_ok(bk_env* env) {
 int bk_open_orders_refresh(bk_env* env) {
   if (int rc = open_orders_ok(env)) return rc;
   if (int rc = use_device(env)) return rc;
-  launch_open_orders_refresh(env, nullptr, 1);
+  launch_open_refresh(env, nullptr, 1);
   HIPCHK(hipGetLastError());
   return BK_OK;
 }
@@ -3503,6 +3534,53 @@ int bk_get_open_orders(bk_env* env, uint32_t first_book, uint32_t n_books, bk_op
   if (rows) HIPCHK(hipMemcpy(summary_out, env->open_summary.p + first * 2, rows * sizeof(bk_open_summary), hipMemcpyDeviceToHost));
   if (rows && entries_out && env->open_depth)
     HIPCHK(hipMemcpy(entries_out, env->open_entries.p + first * env->open_depth, rows * env->open_depth * sizeof(bk_open_order),
+                     hipMemcpyDeviceToHost));
+  return BK_OK;
+}
+
+// ------------------------------------------------------------------ queue positions of the open orders
+// No counterpart in the reference.  queue[n_books][n_traders][depth], one row per entry of the open-order view: the volume and
+// the orders with priority over it, recomputed from the pool by open_queue::k_refresh right behind open_orders::k_refresh
+// wherever that runs; open_queue.hpp, DESIGN.md 2.19.
+int bk_open_queue_enable(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->open_traders)
+    return fail(BK_INVALID_ARGUMENT, "the queue view has one row per entry of the open-order view: call bk_open_orders_enable first");
+  if (env->open_depth == 0)
+    return fail(BK_INVALID_ARGUMENT, "the queue view needs depth > 0: the open-order view of this env keeps no entries");
+  if (env->open_queue.p) return fail(BK_INVALID_ARGUMENT, "the queue view is already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  DevBuf<bk_u32x4> queue;
+  HIPCHK(queue.alloc(static_cast<size_t>(env->cfg.n_books) * env->open_traders * env->open_depth * 2));
+  std::swap(env->open_queue.p, queue.p), std::swap(env->open_queue.n, queue.n);
+  launch_open_refresh(env, nullptr, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int open_queue_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->open_queue.p) return fail(BK_INVALID_ARGUMENT, "this env has no queue view: call bk_open_queue_enable first");
+  return BK_OK;
+}
+
+int bk_open_queue_device_ptr(bk_env* env, void** out) {
+  if (int rc = open_queue_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->open_queue.p;
+  return BK_OK;
+}
+
+int bk_get_open_queue(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_queue* out) {
+  if (int rc = open_queue_ok(env)) return rc;
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  const size_t per_book = static_cast<size_t>(env->open_traders) * env->open_depth;
+  if (n_books)
+    HIPCHK(hipMemcpy(out, env->open_queue.p + first_book * per_book * 2, n_books * per_book * sizeof(bk_open_queue),
                      hipMemcpyDeviceToHost));
   return BK_OK;
 }

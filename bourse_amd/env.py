@@ -140,6 +140,7 @@ class ManyBookEnv:
         check(self._L.bk_env_create(C.byref(cfg), C.byref(self._h)))
         self.width = int(self._L.bk_l2_width(self._h))
         self._stream = None if stream is None else int(stream)  # (None: the env's own stream, which Python never sees)
+        self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
         if stream is not None:
             check(self._L.bk_env_set_stream(self._h, C.c_void_p(stream)))
         if tick_sizes is not None:
@@ -1185,6 +1186,51 @@ class ManyBookEnv:
         summary, entries = self.open_orders_device_ptrs()
         return (OpenOrdersView(self, summary, (self.n_books, nt, 4), "<i8", self._stream),
                 OpenOrdersView(self, entries, (self.n_books, nt, depth, 4), "<i4", self._stream) if depth else None)
+
+    # ------------------------------------------------------------ queue positions of the open orders
+    OPEN_QUEUE_DTYPE = _lib.OPEN_QUEUE_DTYPE
+
+    def enable_open_queue(self):
+        """``bk_open_queue_enable``: keep, beside every entry of the open-order view, where that resting order stands in
+        its book's queue - the volume and the number of orders with priority over it (better-priced, or earlier at its own
+        price), the part of both at its own price, and the whole volume of its level - in device memory, recomputed from
+        the pool right behind the open-order rows wherever those are refreshed.  Every live order counts, whoever owns
+        it.  Call at any time after ``enable_open_orders`` with ``depth > 0``.  The reference has no counterpart."""
+        check(self._L.bk_open_queue_enable(self._h))
+        self._open_queue = True
+
+    def _open_queue_shape(self):
+        if not self._open_queue:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no queue view: call enable_open_queue first")
+        return self._open_orders_shape()
+
+    def open_queue(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as of the last refresh, a
+        structured array of shape ``[n, n_traders, depth]`` (``OPEN_QUEUE_DTYPE``); row ``[b, t, k]`` belongs to entry
+        ``[b, t, k]`` of ``open_orders()``, and an unused entry's row is all zeros.  Waits for the env's stream."""
+        nt, depth = self._open_queue_shape()
+        n = self.n_books - int(first_book) if n_books is None else int(n_books)
+        if int(first_book) < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        out = np.zeros((n, nt, depth), dtype=_lib.OPEN_QUEUE_DTYPE)
+        check(self._L.bk_get_open_queue(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def open_queue_device_ptr(self) -> int:
+        """Device address of the table, ``bk_open_queue[n_books][n_traders][depth]`` (for on-device consumers)."""
+        self._open_queue_shape()
+        out = C.c_void_p()
+        check(self._L.bk_open_queue_device_ptr(self._h, C.byref(out)))
+        return int(out.value)
+
+    def open_queue_view(self) -> "OpenOrdersView":
+        """The table in place as an object with ``__cuda_array_interface__`` (``torch.as_tensor(view, device="cuda")`` is
+        a zero-copy tensor that every later step updates; written on the env's stream, so read it there or after
+        ``sync()``): int64, shape ``(n_books, n_traders, depth, 4)``, the last axis ``ahead_vol, level_ahead_vol,
+        level_vol, counts`` (the unsigned words read as int64: the same bits) with ``ahead_orders = counts & 0xFFFFFFFF``
+        and ``level_ahead_orders = counts >> 32``."""
+        nt, depth = self._open_queue_shape()
+        return OpenOrdersView(self, self.open_queue_device_ptr(), (self.n_books, nt, depth, 4), "<i8", self._stream)
 
 
 class OpenOrdersView:

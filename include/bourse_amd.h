@@ -673,6 +673,44 @@ int bk_open_orders_device_ptrs(bk_env* env, void** summary, void** entries);
 int bk_get_open_orders(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_summary* summary_out,
                        bk_open_order* entries_out);
 
+/* ------------------------------------------------------ queue positions of the open orders */
+/* An opt-in companion of the entries above, in DEVICE memory: queue[n_books][n_traders][depth], one row per entry, saying
+ * where that resting order stands in its book's queue - how much volume must trade before it is touched, and how much of
+ * that rests ahead of it at its own price.  Neither the level-2 ladder (volume per level, nothing inside a level) nor the
+ * order ids (a modification that replaces an order keeps its id and takes a fresh place) give it.  The rows are RECOMPUTED
+ * from each book's pool on the env's stream (bourse_amd/csrc/open_queue.hpp), right behind the open-order
+ * rows wherever those are refreshed; like them they hold no state of their own - no cursor, nothing in a snapshot.  The
+ * reference has no counterpart for any of these entries.
+ *
+ * For the listed order o of side S, price P and pool stamp q (the pool's `seq`, the time priority the matching engine
+ * trades by and bk_live_orders sorts by), r ranges over the OTHER live orders of the book on side S: r is better when its
+ * price is above P (bids) or below P (asks), level-earlier when its price is P and its stamp is below q.  Every live order
+ * counts, whoever owns it: background members and agents, traders >= n_traders, the trader's own other orders, and orders
+ * whose id is >= max_orders.  The row of an unused entry (order_id == 0xFFFFFFFF) is all zeros. */
+typedef struct bk_open_queue { /* 32 B */
+  uint64_t ahead_vol;          /* remaining volume that has priority over this order on its side */
+  uint64_t level_ahead_vol;    /* the part of it that rests at this order's own price */
+  uint64_t level_vol;          /* all remaining volume at this order's price and side, this order included */
+  uint32_t ahead_orders;       /* how many resting orders ahead_vol counts */
+  uint32_t level_ahead_orders; /* how many level_ahead_vol counts */
+} bk_open_queue;
+/* Enabling.  Accepted at any time after bk_open_orders_enable - also mid-run and while an ingress snapshot slot is held.
+ * Refuses an env without the open-order view (call bk_open_orders_enable first), one whose view has depth == 0 and a
+ * second call.  A refusal - here and in the two entries below - returns BK_INVALID_ARGUMENT, is made before anything is
+ * allocated or enqueued, leaves the env unchanged and puts the reason in bk_last_error().  Allocates the table and
+ * refreshes both tables for every book, the open-order rows first.
+ *
+ * When the rows are refreshed: wherever the open-order rows are (bk_open_orders_enable's list), by one more launch on the
+ * env's stream right behind that refresh and with the same mask: no allocation, no stream wait, no host read.  Behaviour
+ * of an env without the view does not change.  (No counterpart in the reference.) */
+int bk_open_queue_enable(bk_env* env);
+/* Device pointer of the table, bk_open_queue[n_books][n_traders][depth], for on-device consumers; valid for the env's
+ * life, written on the env's stream.  BK_INVALID_ARGUMENT without the queue view.  (No counterpart in the reference.) */
+int bk_open_queue_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory, n_books * n_traders * depth records.  Waits for the
+ * env's stream.  (No counterpart in the reference.) */
+int bk_get_open_queue(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_queue* out);
+
 #ifdef __cplusplus
 }
 #endif

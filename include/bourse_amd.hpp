@@ -287,6 +287,22 @@ class ManyEnv {
     check(bk_open_orders_device_ptrs(h_, &s, &e));
     return {static_cast<bk_open_summary*>(s), static_cast<bk_open_order*>(e)};
   }
+  // queue positions of the open orders (bk_open_queue_enable): one row per entry of the open-order view - the volume and
+  // the orders with priority over it - recomputed on the device right behind those rows; the reference has no counterpart
+  void enable_open_queue() { check(bk_open_queue_enable(h_)); }
+  // rows of books [first_book, first_book + n_books), n_traders * depth each (waits for the env's stream)
+  std::vector<bk_open_queue> open_queue(uint32_t first_book, uint32_t n_books) {
+    std::vector<bk_open_queue> rows(static_cast<size_t>(n_books) * open_traders_ * open_depth_);
+    check(bk_get_open_queue(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<bk_open_queue> open_queue() { return open_queue(0, n_books_); }
+  // the table in device memory, bk_open_queue[n_books][n_traders][depth]
+  bk_open_queue* open_queue_device_ptr() {
+    void* p = nullptr;
+    check(bk_open_queue_device_ptr(h_, &p));
+    return static_cast<bk_open_queue*>(p);
+  }
   bk_env* handle() { return h_; }
 
  private:
