@@ -117,6 +117,18 @@ class OpenQueue(C.Structure):
                 ("ahead_orders", C.c_uint32), ("level_ahead_orders", C.c_uint32)]
 
 
+# bk_quote: one trader's row of ManyBookEnv.submit_quotes' table; QUOTE_KEEP (BK_QUOTE_KEEP) as a side's vol leaves it alone
+QUOTE_DTYPE = np.dtype(
+    {"names": ["bid_price", "bid_vol", "ask_price", "ask_vol"], "formats": ["<u4", "<u4", "<u4", "<u4"],
+     "offsets": [0, 4, 8, 12], "itemsize": 16})
+QUOTE_KEEP = 0xFFFFFFFF
+
+
+class Quote(C.Structure):
+    """bk_quote: one row of the quote table."""
+    _fields_ = [("bid_price", C.c_uint32), ("bid_vol", C.c_uint32), ("ask_price", C.c_uint32), ("ask_vol", C.c_uint32)]
+
+
 # bk_random_agents (RandomAgentsCfg) as a numpy structured dtype: the rows of ManyBookEnv.set_random_agents_per_book's table
 RANDOM_AGENTS_DTYPE = np.dtype(
     {"names": ["n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate"],
@@ -239,6 +251,8 @@ SIGNATURES = {
     "bk_open_queue_enable": (_i32, [_vp]),
     "bk_open_queue_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_open_queue": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_submit_quotes_device": (_i32, [_vp, _vp, _vp, _vp]),
+    "bk_submit_quotes": (_i32, [_vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -54,6 +54,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "accounts.hpp"
 #include "open_orders.hpp"
 #include "open_queue.hpp"
+#include "quotes_ingress.hpp"
 
 using namespace bkd;
 
@@ -73,6 +74,10 @@ static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * si
 static_assert(sizeof(bk_open_queue) == 32 && sizeof(bk_open_queue) == 2 * sizeof(bk_u32x4) &&
                   sizeof(open_queue::Row) == sizeof(bk_open_queue) && open_queue::NO_ORDER == open_orders::NO_ORDER,
               "bk_open_queue layout (open_queue.hpp)");
+static_assert(sizeof(bk_quote) == 16 && sizeof(bk_quote) == sizeof(bk_u32x4) && sizeof(quotes::Quote) == sizeof(bk_quote) &&
+                  quotes::KEEP == BK_QUOTE_KEEP && quotes::ACT_MODIFY == BK_ACTION_MODIFY && quotes::ACT_MODIFY == ING_ACTION_MODIFY &&
+                  quotes::NO_ORDER == open_orders::NO_ORDER,
+              "bk_quote layout / constants (quote_rows.hpp)");
 static_assert(sizeof(DevTrade) == 32 && sizeof(DevOrderLog) == 48 && sizeof(uint4) == 16, "device record layout");
 
 namespace {
@@ -181,6 +186,11 @@ struct bk_env {
   uint32_t open_traders = 0, open_depth = 0;  // open_traders == 0: no view
   // bk_open_queue_enable: the queue position of every entry above, recomputed right behind them (open_queue.hpp)
   DevBuf<bk_u32x4> open_queue;  // [n_books][open_traders][open_depth][2]; empty: no queue view
+  // bk_submit_quotes: the host table goes caller -> pinned staging (before the call returns) -> device staging (on the
+  // env's stream); [n_books][open_traders] rows each, made at the first call; quote_copied: the last upload has left the pinned rows
+  DevBuf<bk_u32x4> quote_stage;
+  bk_quote* quote_pin = nullptr;
+  hipEvent_t quote_copied = nullptr;
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -1044,6 +1054,8 @@ void bk_env_destroy(bk_env* env) {
   if (env->hi.in) (void)hipStreamSynchronize(env->hi.in);
   if (env->hi.out) (void)hipStreamSynchronize(env->hi.out);
   if (env->mods_flag_host) (void)hipHostFree(env->mods_flag_host);
+  if (env->quote_pin) (void)hipHostFree(env->quote_pin);
+  if (env->quote_copied) (void)hipEventDestroy(env->quote_copied);
   for (auto& r : env->hi.retired) (void)hipHostFree(r.pin);
   env->hi.retired.clear();
   for (int i = 0; i < bk_env::HostIngress::SLOTS; ++i) {
@@ -3583,6 +3595,68 @@ int bk_get_open_queue(bk_env* env, uint32_t first_book, uint32_t n_books, bk_ope
     HIPCHK(hipMemcpy(out, env->open_queue.p + first_book * per_book * 2, n_books * per_book * sizeof(bk_open_queue),
                      hipMemcpyDeviceToHost));
   return BK_OK;
+}
+
+// ------------------------------------------------------------------ quotes through the device ingress
+// No counterpart in the reference.  quotes[n_books][n_traders], one target row per trader of the open-order view, joined with
+// the view's entries and queued as cancellations, volume-only modifications and new orders by quotes::k_submit - k_ingest's
+// passes over the dense grid n_traders x (depth + 2); quotes_ingress.hpp, DESIGN.md 2.20.
+static int submit_quotes_ok(bk_env* env, const void* quotes) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!quotes) return fail(BK_INVALID_ARGUMENT, "null quotes");
+  if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "call bk_device_ingress_enable first");
+  if (!env->open_traders)
+    return fail(BK_INVALID_ARGUMENT, "a quote row is joined with the trader's listed orders: call bk_open_orders_enable first");
+  if (env->open_depth == 0)
+    return fail(BK_INVALID_ARGUMENT, "quotes need depth > 0: the open-order view of this env keeps no entries");
+  return BK_OK;
+}
+
+int bk_submit_quotes_device(bk_env* env, const bk_quote* quotes_dev, uint64_t* out_ids_dev, uint32_t* status_dev) {
+  if (int rc = submit_quotes_ok(env, quotes_dev)) return rc;
+  if (reinterpret_cast<uintptr_t>(quotes_dev) & 15u) return fail(BK_INVALID_ARGUMENT, "quotes must be 16-byte aligned");
+  if (int rc = use_device(env)) return rc;
+  quotes::SubmitArgs g{};
+  g.quotes = reinterpret_cast<const bk_u32x4*>(quotes_dev);
+  g.entries = env->open_entries.p;
+  g.n_traders = env->open_traders;
+  g.depth = env->open_depth;
+  g.out_ids = reinterpret_cast<unsigned long long*>(out_ids_dev);
+  g.status = status_dev;
+  g.q = env->dq.p;
+  g.qlen = env->dqlen.p;
+  g.qcap = env->qcap;
+  g.dorders = env->dorders.p;
+  g.mods_flag = env->mods_flag_dev;
+  const DevArgs a = env->args();
+  hipLaunchKernelGGL(quotes::k_submit, dim3(env->cfg.n_books / env->M), dim3(64), 0, env->stream, a, g);
+  HIPCHK(hipGetLastError());
+  env->ingest_epoch += 1;
+  return BK_OK;
+}
+
+int bk_submit_quotes(bk_env* env, const bk_quote* quotes, uint64_t* out_ids_dev, uint32_t* status_dev) {
+  if (int rc = submit_quotes_ok(env, quotes)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const size_t rows = static_cast<size_t>(env->cfg.n_books) * env->open_traders;
+  if (!env->quote_pin) {  // (the view's shape is fixed once enabled: one size for the env's life)
+    DevBuf<bk_u32x4> stage;
+    HIPCHK(stage.alloc(rows));
+    void* pin = nullptr;
+    HIPCHK(hipHostMalloc(&pin, rows * sizeof(bk_quote), hipHostMallocDefault));
+    if (hipEventCreateWithFlags(&env->quote_copied, hipEventDisableTiming) != hipSuccess) {
+      (void)hipHostFree(pin);
+      return fail(BK_HIP_ERROR, "hipEventCreateWithFlags failed");
+    }
+    env->quote_pin = static_cast<bk_quote*>(pin);
+    std::swap(env->quote_stage.p, stage.p), std::swap(env->quote_stage.n, stage.n);
+  } else {
+    HIPCHK(hipEventSynchronize(env->quote_copied));  // the call before this one has been uploaded: the pinned rows are free
+  }
+  std::memcpy(env->quote_pin, quotes, rows * sizeof(bk_quote));  // the caller's table may be reused on return
+  HIPCHK(hipMemcpyAsync(env->quote_stage.p, env->quote_pin, rows * sizeof(bk_quote), hipMemcpyHostToDevice, env->stream));
+  HIPCHK(hipEventRecord(env->quote_copied, env->stream));
+  return bk_submit_quotes_device(env, reinterpret_cast<const bk_quote*>(env->quote_stage.p), out_ids_dev, status_dev);
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

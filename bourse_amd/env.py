@@ -1232,6 +1232,64 @@ class ManyBookEnv:
         nt, depth = self._open_queue_shape()
         return OpenOrdersView(self, self.open_queue_device_ptr(), (self.n_books, nt, depth, 4), "<i8", self._stream)
 
+    # ------------------------------------------------------------ quotes: requote every trader from one dense table
+    QUOTE_DTYPE = _lib.QUOTE_DTYPE
+    QUOTE_KEEP = _lib.QUOTE_KEEP
+
+    def submit_quotes(self, quotes, out_ids=None, status=None, check_status: bool = False):
+        """``bk_submit_quotes_device`` / ``bk_submit_quotes``: one row ``(bid_price, bid_vol, ask_price, ask_vol)`` per
+        book and trader of the open-order view, "this trader wants this bid and this ask".  Per side, against the trader's
+        listed entries as the last refresh left them: ``vol == QUOTE_KEEP`` leaves the side alone, ``vol == 0`` cancels
+        every listed order of it; otherwise the first listed order at the target price keeps (reduced in place when it
+        holds more, topped up by a new order behind it when it holds less), every other listed order of the side is
+        cancelled, and without a keeper a new limit order is placed.  The result is queued on the env's stream exactly
+        as ``submit_instructions_device`` queues the dense grid ``n_traders x (depth + 2)`` (include/bourse_amd.h).
+
+        ``quotes``: a torch CUDA tensor or ``__cuda_array_interface__`` object of 4-byte ints shaped ``(n_books,
+        n_traders, 4)``, written on the env's stream (the device entry), or a numpy array of that shape / of
+        ``QUOTE_DTYPE`` rows ``(n_books, n_traders)`` (the host entry).  ``out_ids`` (device, 8-byte, ``(n_books, n_traders,
+        2)``) receives the ids of the new bid and ask, 2**64 - 1 elsewhere; ``status`` (device, 4-byte, 2 per book)
+        ``{code, grid positions applied}``.  ``check_status`` behaves as on ``submit_instructions_device``."""
+        if check_status and status is None:
+            raise ValueError("check_status needs a status array")
+        shape = getattr(self, "_open_shape", None)
+        nt = shape[0] if shape else None  # (without the view the library refuses the call and says why)
+        P = self._dev_ptr
+        if hasattr(quotes, "data_ptr") or hasattr(quotes, "__cuda_array_interface__"):
+            ptr = P(quotes, 4, "quotes")
+            n = int(quotes.numel()) if hasattr(quotes, "numel") else int(np.prod(quotes.__cuda_array_interface__["shape"]))
+            if nt is not None and n != self.n_books * nt * 4:
+                raise ValueError(f"quotes: shape (n_books, n_traders, 4) = ({self.n_books}, {nt}, 4) is needed")
+            check(self._L.bk_submit_quotes_device(self._h, ptr, P(out_ids, 8, "out_ids"), P(status, 4, "status")))
+        else:
+            if quotes is None:
+                host = None
+            elif isinstance(quotes, np.ndarray) and quotes.dtype == _lib.QUOTE_DTYPE:
+                host = np.ascontiguousarray(quotes)
+            else:
+                q = np.asarray(quotes)
+                if q.dtype.kind not in "iu":
+                    raise ValueError("quotes: integers or QUOTE_DTYPE rows are needed")
+                if q.size and (q.min() < 0 or q.max() > 0xFFFFFFFF):
+                    raise ValueError("quotes: prices and volumes are 32-bit unsigned")
+                host = np.ascontiguousarray(q.astype(np.uint32))
+            if host is not None and nt is not None and host.nbytes != self.n_books * nt * 16:
+                raise ValueError(f"quotes: shape (n_books, n_traders, 4) = ({self.n_books}, {nt}, 4) is needed")
+            check(self._L.bk_submit_quotes(self._h, None if host is None else host.ctypes.data_as(C.c_void_p),
+                                           P(out_ids, 8, "out_ids"), P(status, 4, "status")))
+        if check_status:
+            self.sync()
+            st = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
+            st = st.reshape(-1, 2).view(np.uint32) if st.dtype.itemsize == 4 else st.reshape(-1, 2)
+            bad = np.nonzero(st[:, 0])[0]
+            if len(bad):
+                b, code = int(bad[0]), int(st[bad[0], 0])
+                if code == _lib.BK_PRICE:
+                    raise ValueError(f"book {b}: a quoted price was not a multiple of the tick size "
+                                     f"(grid position {int(st[b, 1])} of the book's batch; earlier positions are queued)")
+                raise _lib.CapacityError(code, f"book {b}: event queue / id space exhausted after {int(st[b, 1])} grid positions")
+        return out_ids, status
+
 
 class OpenOrdersView:
     """One table of ``ManyBookEnv.open_orders_views()`` where it lives, for ``torch.as_tensor(view, device="cuda")``, cupy

@@ -711,6 +711,56 @@ int bk_open_queue_device_ptr(bk_env* env, void** out);
  * env's stream.  (No counterpart in the reference.) */
 int bk_get_open_queue(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_queue* out);
 
+/* ------------------------------------------------------ quotes: requote every trader from one dense table */
+/* The action side of an on-device strategy loop: quotes[n_books][n_traders], one row per trader with a row in the
+ * open-order view (n_traders and depth are bk_open_orders_enable's; on a market the rows are per book, market * assets +
+ * asset), saying "this trader wants this bid and this ask".  The call joins the table with the view's entries on the
+ * device (bourse_amd/csrc/quotes_ingress.hpp) and queues the cancellations, in-place reductions and new
+ * orders that lead there.  The reference has no counterpart for any of these entries.
+ *
+ * Per side S of trader t in book b, against the trader's LISTED entries - entries[b][t][0 .. depth-1] in ascending order
+ * id, exactly as the last refresh left them:
+ *   vol == BK_QUOTE_KEEP   nothing for this side.
+ *   vol == 0               every listed order of side S is cancelled.
+ *   otherwise (P, V)       the KEEPER is the first listed order of side S whose price equals P; every other listed order of
+ *                          side S is cancelled.  With a keeper of remaining volume v: v == V nothing; v > V a volume-only
+ *                          modification to V (applied in place, priority kept); v < V a new limit order (P, V - v) - the
+ *                          keeper keeps its place and the top-up queues behind it.  Without a keeper: a new limit order
+ *                          (P, V).  New orders carry trader id t.
+ *
+ * The call is DEFINED as a dense instruction batch.  Book b's batch is the grid n_traders x G, G = depth + 2,
+ * trader-major: positions 0 .. depth-1 of a trader are its entry slots (action 2 with the entry's id, BK_ACTION_MODIFY with
+ * side bit 2, the new volume and the entry's id, or action 0), position depth is the new bid (action 1 or 0) and position
+ * depth + 1 the new ask.  For the queue, the ids, the order records, the flags and status_dev the call equals
+ * bk_submit_instructions_device given that grid with book_offsets[b] = b * n_traders * G: ids are dense in element order;
+ * the first new order whose price the book's tick does not divide stops that book's batch with
+ * BK_PRICE_NOT_TICK_MULTIPLE, earlier elements stay queued and other books are unaffected; a full queue or an exhausted
+ * id space gives BK_CAPACITY; status_dev (nullable, [2 * n_books]) = {code, grid positions applied}; the events are
+ * appended behind whatever was queued earlier in the step, in call order, beside bk_submit_instructions_device,
+ * bk_update_agents, bk_update_members and the market updates.  out_ids_dev (nullable, [n_books][n_traders][2] u64) holds
+ * the id of the new bid and the new ask the call created, UINT64_MAX otherwise; it is untouched from a book's failing
+ * element on.
+ *
+ * What is the caller's affair:
+ *   - The table describes the books as of the last refresh.  Orders submitted since, the trader's orders beyond `depth` and
+ *     a second call in one step are not seen: the entries are read as they lie.
+ *   - A volume-only modification whose order has meanwhile traded below V is the reference's replace_order.
+ *   - Prices are absolute.  Prices relative to the touch are out of scope: the level-2 data's device pointer and one
+ *     tensor operation give them.  Market orders are out of scope.
+ *   - Nothing is stateful: no snapshot content, nothing to clear. */
+typedef struct bk_quote { uint32_t bid_price, bid_vol, ask_price, ask_vol; } bk_quote; /* 16 B */
+#define BK_QUOTE_KEEP 0xFFFFFFFFu /* as a side's vol: leave that side's resting orders alone */
+/* quotes_dev: DEVICE memory, 16-byte aligned, written on the env's stream.  Asynchronous on the env's stream.  Refuses,
+ * with BK_INVALID_ARGUMENT, before anything is enqueued, the env unchanged and the reason in bk_last_error(): a null env
+ * or null quotes, an env without the device ingress, one without the open-order view (call bk_open_orders_enable first)
+ * and a view with depth == 0.  (No counterpart in the reference.) */
+int bk_submit_quotes_device(bk_env* env, const bk_quote* quotes_dev, uint64_t* out_ids_dev, uint32_t* status_dev);
+/* The same from a HOST table: copied into pinned staging before the call returns and from there, on the env's stream, into
+ * a device staging buffer - both owned by the env and made at the first call; out_ids_dev and status_dev stay device
+ * memory.  The host table may be reused on return; a call waits for the upload of the call before it, never for a kernel
+ * behind that.  Same refusals.  (No counterpart in the reference.) */
+int bk_submit_quotes(bk_env* env, const bk_quote* quotes, uint64_t* out_ids_dev, uint32_t* status_dev);
+
 #ifdef __cplusplus
 }
 #endif

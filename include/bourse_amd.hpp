@@ -303,6 +303,18 @@ class ManyEnv {
     check(bk_open_queue_device_ptr(h_, &p));
     return static_cast<bk_open_queue*>(p);
   }
+  // quotes (bk_submit_quotes_device): one bk_quote row per book and trader of the open-order view, joined with the view's
+  // entries on the device and queued as cancellations, in-place reductions and new orders - the dense grid n_traders x
+  // (depth + 2) through the device ingress; out_ids_dev ([n_books][n_traders][2]) and status_dev ([2 * n_books]) are
+  // device memory and may be null.  Asynchronous on the env's stream; the reference has no counterpart
+  void submit_quotes_device(const bk_quote* quotes_dev, uint64_t* out_ids_dev = nullptr, uint32_t* status_dev = nullptr) {
+    check(bk_submit_quotes_device(h_, quotes_dev, out_ids_dev, status_dev));
+  }
+  // the same from a host table of n_books * n_traders rows (copied through the env's device staging buffer)
+  void submit_quotes(const std::vector<bk_quote>& quotes, uint64_t* out_ids_dev = nullptr, uint32_t* status_dev = nullptr) {
+    if (quotes.size() != static_cast<size_t>(n_books_) * open_traders_) throw std::invalid_argument("quotes: n_books * n_traders rows");
+    check(bk_submit_quotes(h_, quotes.data(), out_ids_dev, status_dev));
+  }
   bk_env* handle() { return h_; }
 
  private:
