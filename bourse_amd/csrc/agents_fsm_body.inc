@@ -3,6 +3,7 @@
 // kernel compiles exactly as it did when this was its own source (see mixed_lanes_body.inc).
 // BK_PB = 1: a lane's groups are its unit's row of the table (u = b: table[u * n_groups + g]), as vector registers;
 // only the group sizes stay wave-uniform (DevArgs::groups).  The includer declares fsm_lds, the kernel's dynamic LDS.
+// BK_FSM_HAND = 1 (uniform kernel only): loop 1's draw loop is the hand-written statement of fsm_asm.hpp.
   uint16_t* list = reinterpret_cast<uint16_t*>(fsm_lds);  // event list of lane l: list[k * 64 + l], 64 * R * 64 entries
   // (which agents place, and on which side, is not tracked here: the event words say it - bit 15 New, bit 14 bid - and
   // k_step_batch rebuilds the masks from them with four LDS atomics per book instead of two per new order in this loop)
@@ -106,6 +107,13 @@
       uint64_t w = live[0];
 #pragma unroll
       for (int r = 1; r < R; ++r) w = ((sbeg >> 6) == (uint32_t)r) ? live[r] : w;
+#if BK_FSM_HAND
+      // the draw loop as ONE hand-written statement (fsm_asm.hpp); the C++ loop below is its specification, and the
+      // kernel's second copy of this body (BK_FSM_HAND = 0, DevArgs::fsm_loop = 1) still runs it
+      fsm_draw_asm(rng.a0, rng.a1, rng.b0, rng.b1, n, n_ev, v_trng, v_vrng, v_tzone, v_vzone,
+                   (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)(list + lane),
+                   __builtin_bitreverse64(w), pv, price0, thr8, g_tick_size, g_vol_lo, send);
+#else
       uint32_t cur_side = 0, cur_price = 0;
       // The phase of every lane lives in four WAVE MASKS carried across the iterations in scalar registers (one-hot per
       // lane) and is advanced by scalar mask algebra at the end of the iteration - round 3 kept it in a vector register:
@@ -152,6 +160,7 @@
         P_ACT = ADV;
         asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n) : "s"(ADV) : "vcc");  // n += lane_bit(ADV)
       }
+#endif
       sbeg = send;
     }
   }

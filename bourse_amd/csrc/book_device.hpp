@@ -24,6 +24,7 @@
 
 #include "event_asm.hpp"
 #include "event_asm_gen.hpp"
+#include "fsm_asm.hpp"
 #include "agent_table.hpp"  // struct Group
 
 // 1: the event loop of a 128-slot pool runs the hand-written gfx950 code of event_asm.hpp; 0: the compiled C++ below
@@ -100,6 +101,7 @@ struct DevArgs {
   // ev[m * ev_stride ..] and their number is ev_len[m] (null: the CSR form above, uploaded by the host)
   const uint32_t* ev_len;
   uint32_t ev_stride;
+  uint32_t fsm_loop;  // k_agents_fsm<R>'s draw loop: 0 = the hand-written statement (fsm_asm.hpp), 1 = the compiled C++ loop (BOURSE_AMD_FSM_LOOP)
   // split pipeline: per-book step batch written by k_agents_fsm, consumed by k_step_batch
   uint32_t* batch;
   uint32_t batch_stride;  // dwords per book: 64 + 160 * R
@@ -1510,6 +1512,14 @@ enum Phase : uint32_t { PH_ACT = 0, PH_SIDE = 1, PH_TICK = 2, PH_VOL = 3, PH_SHU
 #endif
 #define BK_STR2(x) #x
 #define BK_STR(x) BK_STR2(x)
+// 1 = k_agents_fsm<R>'s draw loop is the hand-written statement of fsm_asm.hpp; 0 = the C++ loop of agents_fsm_body.inc
+// (same semantics: with -DBOURSE_AMD_FSM_ASM=0 the kernel compiles exactly as it did before the statement existed)
+#ifndef BOURSE_AMD_FSM_ASM
+#define BOURSE_AMD_FSM_ASM 1
+#endif
+#if BOURSE_AMD_FSM_ASM && BOURSE_AMD_FSM_TOP_VGPR < 231
+#error "fsm_asm.hpp keeps its scratch in v196..v231: the kernel's claim (BOURSE_AMD_FSM_TOP_VGPR) must cover them"
+#endif
 
 constexpr uint32_t fsm_lds_bytes(int R) { return 64u * R * 32u * 4u; }
 
@@ -1531,7 +1541,21 @@ __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
   // up to that occupancy's budget (R = 2: 169 VGPRs + 102 SGPRs for a kernel using 34 + 46; 257 VGPRs for R = 4, 8).
   extern __shared__ uint32_t fsm_lds[];
 #define BK_PB 0
+#if BOURSE_AMD_FSM_ASM
+  // The body is compiled TWICE: with the hand-written draw loop (what runs), and as plain C++ - the statement's
+  // specification, kept runnable in the same library: DevArgs::fsm_loop = 1 (BOURSE_AMD_FSM_LOOP=compiled when the env is
+  // created) takes it, so either loop can be checked against the oracle and against the other without a second build.
+  // One wave-uniform branch at the kernel's entry; each copy keeps its own register allocation.
+  if (a.fsm_loop == 0u) {
+#define BK_FSM_HAND 1
 #include "agents_fsm_body.inc"
+#undef BK_FSM_HAND
+    return;
+  }
+#endif
+#define BK_FSM_HAND 0
+#include "agents_fsm_body.inc"
+#undef BK_FSM_HAND
 #undef BK_PB
 }
 
@@ -1540,7 +1564,9 @@ __global__ __launch_bounds__(64) void k_agents_fsm(DevArgs a) {
 template <int R>
 __device__ __forceinline__ void agents_fsm_pb(const DevArgs& a, const Group* table, uint32_t* fsm_lds) {
 #define BK_PB 1
+#define BK_FSM_HAND 0
 #include "agents_fsm_body.inc"
+#undef BK_FSM_HAND
 #undef BK_PB
 }
 template <int R, bool PB>

@@ -204,6 +204,7 @@ struct bk_env {
   bool mw_attr_set = false;
   uint32_t fused_resident = 0;   // books one residency round of k_run_wave<R> holds on this device (0 = not asked yet)
   bool step_decode = false;      // BOURSE_AMD_STEP_DECODE (pipeline_plan.hpp)
+  bool fsm_compiled_loop = false;  // BOURSE_AMD_FSM_LOOP=compiled: k_agents_fsm<R> runs its C++ draw loop, not fsm_asm.hpp's
   // split pipeline geometry (pipeline_plan.hpp lane_parts)
   int n_parts = 4;  // one per hardware queue (part_streams)
   uint32_t min_part = 4096;  // books (markets) per part below which the batch is cut in fewer parts
@@ -382,6 +383,7 @@ struct bk_env {
     a.ev = device_ingress ? dq.p : ev.p;
     a.ev_len = device_ingress ? dqlen.p : nullptr;
     a.ev_stride = qcap;
+    a.fsm_loop = fsm_compiled_loop ? 1u : 0u;
     a.batch = batch.p;
     a.batch_stride = batch_stride;
     a.book_begin = 0;
@@ -1009,6 +1011,7 @@ int bk_env_create(const bk_config* cfg, bk_env** out) {
   if (const char* sm = std::getenv("BOURSE_AMD_EV_WAVE_SHUFFLE_MIN")) env->ev_shuffle_min = std::atoi(sm);
   if (const char* su = std::getenv("BOURSE_AMD_STAGGER_US")) env->stagger_us = static_cast<uint32_t>(std::max(0, std::atoi(su)));
   if (const char* sd = std::getenv("BOURSE_AMD_STEP_DECODE")) env->step_decode = std::atoi(sd) != 0;
+  if (const char* fl = std::getenv("BOURSE_AMD_FSM_LOOP")) env->fsm_compiled_loop = std::strcmp(fl, "compiled") == 0;
   if (const char* mp = std::getenv("BOURSE_AMD_MIN_PART")) {
     const int v = std::atoi(mp);
     if (v >= 64) env->min_part = static_cast<uint32_t>(v);
