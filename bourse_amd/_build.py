@@ -29,6 +29,21 @@ def is_stale() -> bool:
 
 
 FSM_SCHED = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]  # fsm_unit.hip only (see its header)
+# The step kernels are dominated by wave-UNIFORM control flow (scalar branches).  By default LLVM's StructurizeCFG
+# pass also rewrites uniform regions, which costs ~9 % extra scalar instructions (flag registers + s_andn2/vccnz
+# branches) on the SALU-bound k_step_batch: skip it for uniform regions (+7 % book-steps/s, parity tests green).
+UNIFORM_CFG = ["-mllvm", "-structurizecfg-skip-uniform-regions=1"]
+
+
+def compile_flags(defines=()) -> list:
+    """hipcc's flags for either translation unit, -D defines included (BOURSE_AMD_HIPCC_FLAGS replaces UNIFORM_CFG)."""
+    extra = os.environ.get("BOURSE_AMD_HIPCC_FLAGS", " ".join(UNIFORM_CFG)).split()
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-D" + d for d in defines]
+
+
+def fsm_unit_flags(defines=()) -> list:
+    """... and fsm_unit.hip's: the same plus its scheduler strategy (BOURSE_AMD_FSM_HIPCC_FLAGS replaces FSM_SCHED)."""
+    return compile_flags(defines) + os.environ.get("BOURSE_AMD_FSM_HIPCC_FLAGS", " ".join(FSM_SCHED)).split()
 
 
 def build(force: bool = False, verbose: bool = False, out: str = None, defines=(), remarks: list = None) -> str:
@@ -37,13 +52,9 @@ def build(force: bool = False, verbose: bool = False, out: str = None, defines=(
     Two translation units: bourse_amd.hip (everything) and fsm_unit.hip (k_agents_fsm under the max-ilp scheduler)."""
     if out is None and not force and not is_stale():
         return LIB
-    # The step kernels are dominated by wave-UNIFORM control flow (scalar branches).  By default LLVM's StructurizeCFG
-    # pass also rewrites uniform regions, which costs ~9 % extra scalar instructions (flag registers + s_andn2/vccnz
-    # branches) on the SALU-bound k_step_batch: skip it for uniform regions (+7 % book-steps/s, parity tests green).
-    extra = os.environ.get("BOURSE_AMD_HIPCC_FLAGS", "-mllvm -structurizecfg-skip-uniform-regions=1").split()
-    fsm_extra = os.environ.get("BOURSE_AMD_FSM_HIPCC_FLAGS", " ".join(FSM_SCHED)).split()
     target = out or LIB
-    base = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-D" + d for d in defines]
+    base = [hipcc_path()] + compile_flags(defines)
+    fsm_extra = fsm_unit_flags(defines)[len(base) - 1:]
     if verbose or remarks is not None:  # (`remarks`: a list that receives the compiler's kernel-resource-usage report)
         base.insert(1, "-Rpass-analysis=kernel-resource-usage")
     objs = []

@@ -3,7 +3,8 @@
 // kernel compiles exactly as it did when this was its own source (see mixed_lanes_body.inc).
 // BK_PB = 1: a lane's groups are its unit's row of the table (u = b: table[u * n_groups + g]), as vector registers;
 // only the group sizes stay wave-uniform (DevArgs::groups).  The includer declares fsm_lds, the kernel's dynamic LDS.
-// BK_FSM_HAND = 1 (uniform kernel only): loop 1's draw loop is the hand-written statement of fsm_asm.hpp.
+// BK_FSM_HAND = 1 (uniform kernel only): loop 1's draw loop is the hand-written statement of fsm_asm.hpp, and with
+// BOURSE_AMD_FSM_TAIL so are the shuffle (bit 0) and the publish loop (bit 1).
   uint16_t* list = reinterpret_cast<uint16_t*>(fsm_lds);  // event list of lane l: list[k * 64 + l], 64 * R * 64 entries
   // (which agents place, and on which side, is not tracked here: the event words say it - bit 15 New, bit 14 bid - and
   // k_step_batch rebuilds the masks from them with four LDS atomics per book instead of two per new order in this loop)
@@ -167,6 +168,11 @@
 
   // ---- loop 2: transactions.shuffle(rng) (env.rs:121): for i in (1..n_ev).rev() { swap(i, gen_index(i + 1)) }
   // (rand SliceRandom::shuffle), again one draw per iteration per lane.
+#if BK_FSM_HAND && (BOURSE_AMD_FSM_TAIL & 1)
+  // ONE hand-written statement (fsm_asm.hpp); the C++ loop below is its specification
+  fsm_shuffle_asm(rng.a0, rng.a1, rng.b0, rng.b1, n_ev,
+                  (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)(list + lane));
+#else
   {
     uint32_t i = n_ev > 1 ? n_ev - 1 : 0;
     uint32_t rg = i + 1;
@@ -189,6 +195,7 @@
       }
     }
   }
+#endif
 
   // publish: RNG state back to the book header, the step batch for k_step_batch
   for (uint32_t as = 0; as < M; ++as) {  // every book of a market carries a copy of the market's RNG state
@@ -196,8 +203,15 @@
     *reinterpret_cast<uint2*>(st + (size_t)as * a.state_stride + H_S1_LO) = make_uint2(rng.b0, rng.b1);
   }
   bt[BT_NEV] = n_ev;
+#if BK_FSM_HAND && (BOURSE_AMD_FSM_TAIL & 2)
+  // eight events per 16-byte store, the entries of the last group at or beyond n_ev written as 0 (fsm_asm.hpp).
+  // NOTHING MAY FOLLOW THIS STATEMENT in the body: its global stores are neither waited for nor counted by the compiler,
+  // so a load (or anything else the compiler waits for with a counted vmcnt) behind it could be released too early
+  fsm_publish_asm(n_ev, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)(list + lane), bt + BT_EV);
+#else
   for (uint32_t k = 0; k < n_ev; k += 2) {
     const uint32_t lo = list[k * 64 + lane];
     const uint32_t hi = (k + 1 < n_ev) ? list[(k + 1) * 64 + lane] : 0u;
     bt[BT_EV + (k >> 1)] = lo | (hi << 16);
   }
+#endif

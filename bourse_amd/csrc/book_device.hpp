@@ -1517,6 +1517,14 @@ enum Phase : uint32_t { PH_ACT = 0, PH_SIDE = 1, PH_TICK = 2, PH_VOL = 3, PH_SHU
 #ifndef BOURSE_AMD_FSM_ASM
 #define BOURSE_AMD_FSM_ASM 1
 #endif
+// k_agents_fsm<R>'s loops BEHIND the draw loop by hand as well (fsm_asm.hpp): bit 0 = the shuffle, bit 1 = the publish
+// loop; with -DBOURSE_AMD_FSM_TAIL=0 the kernel compiles exactly as it did before those statements existed
+#ifndef BOURSE_AMD_FSM_TAIL
+#define BOURSE_AMD_FSM_TAIL (BOURSE_AMD_FSM_ASM ? 3 : 0)
+#endif
+#if BOURSE_AMD_FSM_TAIL && !BOURSE_AMD_FSM_ASM
+#error "BOURSE_AMD_FSM_TAIL needs the hand-written copy of the kernel's body (BOURSE_AMD_FSM_ASM)"
+#endif
 #if BOURSE_AMD_FSM_ASM && BOURSE_AMD_FSM_TOP_VGPR < 231
 #error "fsm_asm.hpp keeps its scratch in v196..v231: the kernel's claim (BOURSE_AMD_FSM_TOP_VGPR) must cover them"
 #endif
