@@ -97,6 +97,12 @@ ACCOUNT_DTYPE = np.dtype(
     {"names": ["position", "cash", "volume", "fills"], "formats": ["<i8", "<i8", "<u8", "<u8"],
      "offsets": [0, 8, 16, 24], "itemsize": 32})
 
+# bk_trade_bar: one book's bar of one step (ManyBookEnv.trade_bars)
+TRADE_BAR_DTYPE = np.dtype(
+    {"names": ["open", "high", "low", "close", "buy_vol", "sell_vol", "notional", "n_buy", "n_sell"],
+     "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", "<u4", "<u4"],
+     "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 44], "itemsize": 48})
+
 # bk_open_summary / bk_open_order: one trader's rows of the open-order tables (ManyBookEnv.open_orders)
 OPEN_SUMMARY_DTYPE = np.dtype(
     {"names": ["bid_vol", "ask_vol", "n_bid", "n_ask", "best_bid", "best_ask"], "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
@@ -244,6 +250,12 @@ SIGNATURES = {
     "bk_get_accounts": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_accounts_clear": (_i32, [_vp, _vp]),
     "bk_accounts_clear_device": (_i32, [_vp, _vp]),
+    "bk_trade_bars_enable": (_i32, [_vp, _u32, _i32]),
+    "bk_trade_bars_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_trade_bars_slot": (_i32, [_vp, C.POINTER(_u32)]),
+    "bk_get_trade_bars": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_trade_bars_clear": (_i32, [_vp, _vp]),
+    "bk_trade_bars_clear_device": (_i32, [_vp, _vp]),
     "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -52,6 +52,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "book_reset.hpp"
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
+#include "trade_bars.hpp"
 #include "open_orders.hpp"
 #include "open_queue.hpp"
 #include "quotes_ingress.hpp"
@@ -67,6 +68,8 @@ static_assert(sizeof(bk_agent_desc) == 104, "bk_agent_desc layout (mirrored by b
 static_assert(sizeof(bk_account) == 32 && sizeof(bk_account) == 2 * sizeof(bk_u32x4) &&
                   accounts::FLAG_ACCOUNTS_INEXACT == BK_FLAG_ACCOUNTS_INEXACT,
               "bk_account layout / flag (accounts.hpp)");
+static_assert(sizeof(bk_trade_bar) == 48 && sizeof(bk_trade_bar) == trade_bars::ROW_VECS * sizeof(bk_u32x4),
+              "bk_trade_bar layout (trade_bars.hpp)");
 static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
@@ -180,6 +183,12 @@ struct bk_env {
   DevBuf<uint8_t> acct_mask;  // bk_accounts_clear: device staging of the host mask [n_books]
   uint32_t acct_traders = 0;  // 0: no accounts
   bool acct_consume = false;
+  // bk_trade_bars_enable: per-step bars [n_books][bars_window] of 48 B and the per-book cursors (trade_bars.hpp)
+  DevBuf<bk_u32x4> bars;
+  DevBuf<unsigned long long> bars_seen;
+  DevBuf<uint8_t> bars_mask;  // bk_trade_bars_clear: device staging of the host mask [n_books]
+  uint32_t bars_window = 0;   // 0: no bars
+  bool bars_consume = false;
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -1642,9 +1651,43 @@ static void launch_accounts_fold(bk_env* env) {
   g.acct = env->acct.p;
   g.n_traders = env->acct_traders;
   g.seen = env->acct_seen.p;
-  g.consume = env->acct_consume ? 1u : 0u;
+  // (the last fold of a step consumes for both: the bars' fold runs in front of this one and leaves the records alone)
+  g.consume = env->acct_consume || env->bars_consume ? 1u : 0u;
   const uint32_t blocks = (g.n_books + accounts::FOLD_WAVES - 1) / accounts::FOLD_WAVES;
   hipLaunchKernelGGL(accounts::k_fold, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
+}
+
+// the step the env's counter reads k -> slot k % window of every book; in front of the accounts' fold, which then consumes
+static void launch_bars_fold(bk_env* env) {
+  trade_bars::FoldArgs g{};
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.trades = reinterpret_cast<const bk_u32x4*>(env->trades.p);
+  g.trade_cap = env->cfg.trade_capacity;
+  g.bars = env->bars.p;
+  g.window = env->bars_window;
+  g.slot = static_cast<uint32_t>(env->steps_done % env->bars_window);
+  g.prev_slot = (g.slot + env->bars_window - 1u) % env->bars_window;
+  g.seen = env->bars_seen.p;
+  g.consume = !env->acct_traders && env->bars_consume ? 1u : 0u;
+  const uint32_t blocks = (g.n_books + trade_bars::FOLD_WAVES - 1) / trade_bars::FOLD_WAVES;
+  hipLaunchKernelGGL(trade_bars::k_fold, dim3(blocks), dim3(64 * trade_bars::FOLD_WAVES), 0, env->stream, g);
+}
+
+// rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
+static void launch_bars_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M) {
+  trade_bars::ClearArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.bars = env->bars.p;
+  g.window = env->bars_window;
+  g.seen = env->bars_seen.p;
+  const uint32_t blocks = (g.n_books + trade_bars::FOLD_WAVES - 1) / trade_bars::FOLD_WAVES;
+  hipLaunchKernelGGL(trade_bars::k_clear, dim3(blocks), dim3(64 * trade_bars::FOLD_WAVES), 0, env->stream, g);
 }
 
 // rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
@@ -1719,7 +1762,11 @@ int bk_step_async(bk_env* env) {
   // step has been on the host)
   const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, env->qcap); });
   if (rc != BK_OK) return rc;
-  if (env->acct_traders) {  // trader accounts: this step's new trade records, right behind the event kernel
+  if (env->bars_window) {  // trade bars: this step's new trade records, right behind the event kernel
+    launch_bars_fold(env);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->acct_traders) {  // trader accounts: the same records
     launch_accounts_fold(env);
     HIPCHK(hipGetLastError());
   }
@@ -2573,6 +2620,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (env->acct_traders)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trader accounts (bk_accounts_enable) is not supported: "
                                      "its trade records would have no order records to look the traders up in");
+  if (env->bars_window)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trade bars (bk_trade_bars_enable) is not supported: "
+                                     "its trade records would pass as the next step's");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
   // (the agents' log holds what k_step_batch_log wrote for every id below the book's counter: a loaded book's orders
@@ -3393,6 +3443,10 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
     launch_accounts_clear(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
   }
+  if (env->bars_window) {  // trade bars are not part of a snapshot either: zero rows, the cursor at the restored count
+    launch_bars_clear(env, mask_dev, env->M);
+    HIPCHK(hipGetLastError());
+  }
   if (env->open_traders) {  // the reset books show the snapshot's resting orders before their next step
     launch_open_refresh(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
@@ -3482,6 +3536,81 @@ int bk_accounts_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = use_device(env)) return rc;
   if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->acct_mask)) return rc;
   return bk_accounts_clear_device(env, env->acct_mask.p);
+}
+
+// ------------------------------------------------------------------ trade bars of a device-ingress env
+// No counterpart in the reference.  bars[n_books][window] rows {open, high, low, close, buy_vol, sell_vol, notional, n_buy,
+// n_sell}: the bar of step k in slot k % window, folded from the step's new trade records by trade_bars::k_fold behind the
+// step's event kernel (bk_step_async); trade_bars.hpp, DESIGN.md 2.21.
+int bk_trade_bars_enable(bk_env* env, uint32_t window, int consume_trades) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->device_ingress)
+    return fail(BK_INVALID_ARGUMENT, "trade bars serve an env with the device ingress (bk_device_ingress_enable): they are "
+                                     "folded behind bk_step_async");
+  if (env->bars_window) return fail(BK_INVALID_ARGUMENT, "trade bars are already enabled on this env");
+  if (window == 0 || window > trade_bars::MAX_WINDOW) return fail(BK_INVALID_ARGUMENT, "window must be in 1..1024 steps");
+  if (int rc = use_device(env)) return rc;
+  const size_t B = env->cfg.n_books;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<unsigned long long> seen;
+  HIPCHK(rows.alloc(B * window * trade_bars::ROW_VECS));
+  HIPCHK(seen.alloc(B));
+  std::swap(env->bars.p, rows.p), std::swap(env->bars.n, rows.n);
+  std::swap(env->bars_seen.p, seen.p), std::swap(env->bars_seen.n, seen.n);
+  env->bars_window = window;
+  env->bars_consume = consume_trades != 0;
+  launch_bars_clear(env, nullptr, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int trade_bars_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->bars_window) return fail(BK_INVALID_ARGUMENT, "this env has no trade bars: call bk_trade_bars_enable first");
+  return BK_OK;
+}
+
+int bk_trade_bars_device_ptr(bk_env* env, void** out) {
+  if (int rc = trade_bars_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->bars.p;
+  return BK_OK;
+}
+
+int bk_trade_bars_slot(bk_env* env, uint32_t* out) {
+  if (int rc = trade_bars_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = static_cast<uint32_t>((env->steps_done % env->bars_window + env->bars_window - 1u) % env->bars_window);
+  return BK_OK;
+}
+
+int bk_get_trade_bars(bk_env* env, uint32_t first_book, uint32_t n_books, bk_trade_bar* out) {
+  if (int rc = trade_bars_ok(env)) return rc;
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  if (n_books)
+    HIPCHK(hipMemcpy(out, env->bars.p + static_cast<size_t>(first_book) * env->bars_window * trade_bars::ROW_VECS,
+                     static_cast<size_t>(n_books) * env->bars_window * sizeof(bk_trade_bar), hipMemcpyDeviceToHost));
+  return BK_OK;
+}
+
+int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = trade_bars_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  launch_bars_clear(env, mask_dev, 1);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = trade_bars_ok(env)) return rc;
+  if (!mask_host) return bk_trade_bars_clear_device(env, nullptr);
+  if (int rc = use_device(env)) return rc;
+  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->bars_mask)) return rc;
+  return bk_trade_bars_clear_device(env, env->bars_mask.p);
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env

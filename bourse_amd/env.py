@@ -1120,6 +1120,83 @@ class ManyBookEnv:
         if sync:
             self.sync()
 
+    # ------------------------------------------------------------ per-step trade bars of an env with the device ingress
+    TRADE_BAR_DTYPE = _lib.TRADE_BAR_DTYPE
+
+    def enable_trade_bars(self, window: int = 1, consume_trades: bool = False):
+        """``bk_trade_bars_enable``: keep, per book, a ring of the last ``window`` steps' bars in device memory - ``open`` /
+        ``high`` / ``low`` / ``close`` price, ``buy_vol`` / ``sell_vol`` by the aggressor's side, ``notional`` and the
+        record counts ``n_buy`` / ``n_sell`` - folded from every step's new trade records on the env's stream with no host
+        in the loop.  The step run while ``steps_done()`` reads ``k`` goes to slot ``k % window``; a book-step without a
+        trade carries the previous close and is zero otherwise.  Call after ``enable_device_ingress``, at any time.
+        ``consume_trades=True`` marks the trade records consumed once folded (as ``clear_trades``), so ``trade_capacity``
+        only has to hold one step's trades.  A record dropped beyond ``trade_capacity`` is left out of its bar; that book carries ``FLAG_TRADE_OVERFLOW``.  The
+        reference has no counterpart."""
+        if not 0 <= int(window) <= 0xFFFFFFFF:
+            raise ValueError("window out of range")
+        check(self._L.bk_trade_bars_enable(self._h, int(window), int(bool(consume_trades))))
+        self._bars_window = int(window)
+
+    def _trade_bars_window(self) -> int:
+        n = getattr(self, "_bars_window", 0)
+        if not n:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no trade bars: call enable_trade_bars first")
+        return n
+
+    def trade_bars(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rings of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
+        shape ``[n, window]`` (``TRADE_BAR_DTYPE``).  Waits for the env's stream."""
+        w = self._trade_bars_window()
+        n = self.n_books - int(first_book) if n_books is None else int(n_books)
+        if int(first_book) < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        out = np.zeros((n, w), dtype=_lib.TRADE_BAR_DTYPE)
+        check(self._L.bk_get_trade_bars(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def trade_bars_device_ptr(self) -> int:
+        """Device address of the ring, ``bk_trade_bar[n_books][window]`` (for on-device consumers)."""
+        out = C.c_void_p()
+        check(self._L.bk_trade_bars_device_ptr(self._h, C.byref(out)))
+        return int(out.value)
+
+    def trade_bars_slot(self) -> int:
+        """The slot the latest folded step went to, ``(steps_done() - 1) % window``: a host integer, no wait."""
+        out = C.c_uint32(0)
+        check(self._L.bk_trade_bars_slot(self._h, C.byref(out)))
+        return int(out.value)
+
+    def trade_bars_view(self) -> "TradeBarsView":
+        """The ring in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, window, 6)``.  Word 0
+        is ``open | high << 32``, word 1 ``low | close << 32``, words 2..4 ``buy_vol``, ``sell_vol``, ``notional`` (unsigned,
+        read as int64: the same bits) and word 5 ``n_buy | n_sell << 32``.  ``torch.as_tensor(env.trade_bars_view(),
+        device="cuda")`` is a zero-copy tensor that every later step updates; it is written on the env's stream, so read it
+        there (or after ``sync()``)."""
+        return TradeBarsView(self, self.trade_bars_device_ptr(), (self.n_books, self._trade_bars_window(), 6), self._stream)
+
+    def clear_trade_bars(self, mask=None, sync: bool = True):
+        """Zero all rows of the books ``b`` with ``mask[b]`` set (``None``: every book); their bars count from the book's
+        current trade count on and the carried price starts at 0.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
+        (``bk_trade_bars_clear`` / ``bk_trade_bars_clear_device``).  ``reset_ingress_books`` clears the books it resets."""
+        self._trade_bars_window()
+        if mask is None:
+            check(self._L.bk_trade_bars_clear_device(self._h, None))
+        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
+            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
+            if n != self.n_books:
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_trade_bars_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError("mask: a bool or uint8 array is needed")
+            m = m.astype(np.uint8, copy=False)
+            if m.shape != (self.n_books,):
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_trade_bars_clear(self._h, m.ctypes.data_as(C.c_void_p)))
+        if sync:
+            self.sync()
+
     # ------------------------------------------------------------ open orders of an env with the device ingress
     OPEN_SUMMARY_DTYPE = _lib.OPEN_SUMMARY_DTYPE
     OPEN_ORDER_DTYPE = _lib.OPEN_ORDER_DTYPE
@@ -1314,6 +1391,10 @@ class AccountsView:
         self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": "<i8", "data": (int(ptr), False),
                                          "version": 3, "strides": None,
                                          "stream": None if stream is None else (stream if stream != 0 else 1)}
+
+
+class TradeBarsView(AccountsView):
+    """``ManyBookEnv.trade_bars_view()``: the ring of trade bars where it lives, read the same way."""
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):

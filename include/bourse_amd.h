@@ -622,6 +622,68 @@ int bk_accounts_clear(bk_env* env, const uint8_t* mask_host);
  * on the env's stream.  (No counterpart in the reference.) */
 int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev);
 
+/* ------------------------------------------------------ per-step trade bars of a device-ingress env */
+/* An opt-in ring bars[n_books][window] in DEVICE memory: WHAT TRADED in each book in each of the last `window` steps - the
+ * first, highest, lowest and last trade price, the volume whose aggressor bought and sold, the notional behind a VWAP and
+ * the record counts - folded from the book's new trade records on the env's stream right behind every step's event kernel,
+ * with no host synchronisation anywhere on that path (bourse_amd/csrc/trade_bars.hpp).  It is the
+ * market-wide counterpart of the per-trader accounts above: a policy that observes and acts in device memory reads signed
+ * flow, last price and the step's range there instead of waiting for bk_get_trades.  The reference has no counterpart for
+ * any of these entries.
+ *
+ * Which step goes where.  The step that bk_step_async / bk_step runs while bk_steps_done reads k is folded into slot
+ * k % window of every book.  A trade record whose PASSIVE order was an ask (side_is_bid == 0) is a buy, one with
+ * side_is_bid == 1 a sell: the aggressor's side, the same reading of the field as the accounts'.  Every record counts,
+ * whoever owns its orders; no order record is looked up.  open / close are the prices of the first / last of the step's
+ * records in the book's record order, high / low the largest / smallest.  A book-step without a trade overwrites its slot
+ * all the same: open = high = low = close = the close of the previous step's slot ((k - 1) % window, read before the write),
+ * every other word 0; before a book's first trade since enable, clear or reset that carried price is 0.  Rows are per book,
+ * so markets need nothing special (market * assets + asset).
+ *
+ * Arithmetic.  The 64-bit words are sums modulo 2^64, vol * price the full 32 x 32 -> 64-bit product; the counts wrap
+ * modulo 2^32. */
+typedef struct bk_trade_bar { /* 48 B, three 16-byte vectors, little-endian */
+  uint32_t open, high, low, close; /* prices of the step's trade records, in record order */
+  uint64_t buy_vol, sell_vol;      /* volume whose aggressor bought / sold */
+  uint64_t notional;               /* sum of vol * price */
+  uint32_t n_buy, n_sell;          /* records whose aggressor bought / sold */
+} bk_trade_bar;
+/* Enabling.  Accepted on an env with the device ingress (bk_device_ingress_enable), at any time - also mid-run and while an
+ * ingress snapshot slot is held: the rows are not part of a snapshot.  Zeroes all rows and starts every book's cursor (a
+ * device array of its own, bars_seen[n_books]; the state block's layout is unchanged) at its current trade count: steps
+ * before the call leave zero rows.  Refuses window outside 1..1024 and a second call.  A refusal - here and in the entries
+ * below - returns BK_INVALID_ARGUMENT, leaves the env unchanged and puts the reason in bk_last_error().
+ *
+ * A record the fold cannot read - dropped beyond trade_capacity - is stepped over: the bar is that of the records that
+ * could be read.  Such a book carries BK_FLAG_TRADE_OVERFLOW already (the step's kernel set it when it dropped the record),
+ * so an inexact bar is never silent; no flag bit of its own is added.  The fold runs in the same call as the step's
+ * kernel, so nothing can consume a step's records before the fold has seen them.
+ *
+ * consume_trades.  With consume_trades = 1 the folded records are marked consumed as bk_clear_trades does:
+ * trade_capacity then only has to hold ONE step's trades.  On an env that also has accounts the bars' fold runs first and
+ * the accounts' fold consumes, once, if either feature asked for it: neither fold hides a record from the other.
+ *
+ * bk_ingress_reset_books* zeroes all `window` rows of the books it resets (every book of a reset market) and moves their
+ * cursors to the restored trade count, where it clears the accounts.  bk_load_book is refused on an env with bars.
+ * Behaviour of an env without bars does not change.  (No counterpart in the reference.) */
+int bk_trade_bars_enable(bk_env* env, uint32_t window, int consume_trades);
+/* Device pointer of the ring, bk_trade_bar[n_books][window], for on-device consumers; valid for the env's life, written
+ * on the env's stream.  BK_INVALID_ARGUMENT without bars.  (No counterpart in the reference.) */
+int bk_trade_bars_device_ptr(bk_env* env, void** out);
+/* The slot the latest folded step went to, (bk_steps_done - 1) % window (window - 1 before the first step): a host
+ * integer, no wait.  (No counterpart in the reference.) */
+int bk_trade_bars_slot(bk_env* env, uint32_t* out);
+/* Rows of books [first_book, first_book + n_books) to host memory, n_books * window records.  Waits for the env's
+ * stream.  (No counterpart in the reference.) */
+int bk_get_trade_bars(bk_env* env, uint32_t first_book, uint32_t n_books, bk_trade_bar* out);
+/* Clearing.  Zeroes all rows of the books b with mask[b] != 0 (mask [n_books] bytes; NULL = every book) and sets their
+ * cursor to the book's current trade count: the carried price starts at 0 again.  From a HOST mask: staged on the env's
+ * stream and waited for, the clear itself stays asynchronous.  (No counterpart in the reference.) */
+int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: one launch
+ * on the env's stream.  (No counterpart in the reference.) */
+int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev);
+
 /* ------------------------------------------------------ open orders of a device-ingress env */
 /* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
  * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or

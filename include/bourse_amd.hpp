@@ -260,6 +260,37 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_accounts_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-step trade bars of an env with the device ingress (bk_trade_bars_enable): a ring of the last `window` steps' open /
+  // high / low / close, buy / sell volume, notional and record counts per book, folded on the device behind every step; the
+  // reference has no counterpart
+  void enable_trade_bars(uint32_t window = 1, bool consume_trades = false) {
+    check(bk_trade_bars_enable(h_, window, consume_trades ? 1 : 0));
+    bars_window_ = window;
+  }
+  // rings of books [first_book, first_book + n_books), window rows each (waits for the env's stream)
+  std::vector<bk_trade_bar> trade_bars(uint32_t first_book, uint32_t n_books) {
+    std::vector<bk_trade_bar> rows(static_cast<size_t>(n_books) * bars_window_);
+    check(bk_get_trade_bars(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<bk_trade_bar> trade_bars() { return trade_bars(0, n_books_); }
+  // the ring in device memory, bk_trade_bar[n_books][window]
+  bk_trade_bar* trade_bars_device_ptr() {
+    void* p = nullptr;
+    check(bk_trade_bars_device_ptr(h_, &p));
+    return static_cast<bk_trade_bar*>(p);
+  }
+  // the slot the latest folded step went to, (steps_done - 1) % window: no wait
+  uint32_t trade_bars_slot() {
+    uint32_t slot = 0;
+    check(bk_trade_bars_slot(h_, &slot));
+    return slot;
+  }
+  // zero all rows of the books with mask[b] != 0 (an empty mask: every book); the carried price starts at 0 again
+  void clear_trade_bars(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_trade_bars_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
   // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
   void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
@@ -319,7 +350,7 @@ class ManyEnv {
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
