@@ -103,6 +103,67 @@ TRADE_BAR_DTYPE = np.dtype(
      "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", "<u4", "<u4"],
      "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 44], "itemsize": 48})
 
+# bk_series_row: one book's series moments of the level-2 history (ManyBookEnv.series), 24 words of 8 bytes
+SERIES_FIELDS = ("n_steps", "n_two_sided", "sum_m", "sum_spread", "sum_spread_sq", "sum_bid_vol", "sum_ask_vol", "sum_trade_vol",
+                 "sum_trade_vol_sq", "n_trade_steps", "n_ret", "sum_d", "sum_abs_d", "sum_d2", "sum_d4_lo", "sum_d4_hi", "max_abs_d",
+                 "n_pairs", "sum_dd", "sum_abs_dd", "min_m", "max_m", "carry_m", "carry_d")
+SERIES_SIGNED = ("sum_d", "sum_dd", "carry_d")
+SERIES_DTYPE = np.dtype(
+    {"names": list(SERIES_FIELDS), "formats": ["<i8" if n in SERIES_SIGNED else "<u8" for n in SERIES_FIELDS],
+     "offsets": [8 * i for i in range(24)], "itemsize": 192})
+
+SERIES_MOMENTS_DTYPE = np.dtype([(n, "<f8") for n in (
+    "mean_mid", "mean_spread", "var_spread", "mean_return", "var_return", "kurtosis_return", "acf1_return", "acf1_abs_return",
+    "mean_trade_vol", "mean_bid_vol", "mean_ask_vol")])
+
+
+def series_moments(rows) -> np.ndarray:
+    """``SERIES_DTYPE`` rows (``ManyBookEnv.series()``) -> float64 moments per book (``SERIES_MOMENTS_DTYPE``), computed
+    exactly in Python integers and rounded once.  With ``d`` the step-to-step change of TWICE the mid between consecutive
+    two-sided steps (a return of the mid is ``d / 2``):
+
+    ``mean_mid`` = sum_m / (2 n_two_sided); ``mean_spread``, ``var_spread`` (population variance) over two-sided steps;
+    ``mean_return`` = sum_d / (2 n_ret); ``var_return`` = (sum_d2 / n_ret - (sum_d / n_ret)^2) / 4;
+    ``kurtosis_return`` = n_ret sum_d4 / sum_d2^2 - 3, the excess kurtosis ABOUT ZERO (the row keeps no third power);
+    ``acf1_return`` = (sum_dd / n_pairs - mean_d^2) / var_d and ``acf1_abs_return`` the same of ``|d|`` - lag-1
+    autocorrelations with the moments of all returns for both factors; ``mean_trade_vol``, ``mean_bid_vol``,
+    ``mean_ask_vol`` (the touch volumes) per step.  A division by a zero count or a zero variance gives NaN.  The words
+    are read as they are: a sum that has wrapped modulo 2^64 is not detected (the counts and ``max_abs_d`` bound them)."""
+    from fractions import Fraction as F
+
+    rows = np.atleast_1d(np.asarray(rows))
+    if rows.dtype != SERIES_DTYPE:
+        raise ValueError("series_moments needs SERIES_DTYPE rows")
+    out = np.full(rows.shape, np.nan, dtype=SERIES_MOMENTS_DTYPE)
+
+    def div(a, b):
+        return F(a, b) if b else None
+
+    def put(o, name, x):
+        o[name] = np.nan if x is None else float(x)
+
+    for r, o in zip(rows.reshape(-1), out.reshape(-1)):
+        w = {n: int(r[n]) for n in SERIES_FIELDS}
+        n2, nr, npair, ns = w["n_two_sided"], w["n_ret"], w["n_pairs"], w["n_steps"]
+        d4 = w["sum_d4_lo"] | (w["sum_d4_hi"] << 64)
+        put(o, "mean_mid", div(w["sum_m"], 2 * n2))
+        ms = div(w["sum_spread"], n2)
+        put(o, "mean_spread", ms)
+        put(o, "var_spread", None if ms is None else F(w["sum_spread_sq"], n2) - ms * ms)
+        md, mabs = div(w["sum_d"], nr), div(w["sum_abs_d"], nr)
+        put(o, "mean_return", None if md is None else md / 2)
+        var_d = None if md is None else F(w["sum_d2"], nr) - md * md
+        var_abs = None if mabs is None else F(w["sum_d2"], nr) - mabs * mabs
+        put(o, "var_return", None if var_d is None else var_d / 4)
+        put(o, "kurtosis_return", None if not w["sum_d2"] else F(nr * d4, w["sum_d2"] ** 2) - 3)
+        put(o, "acf1_return", None if not npair or not var_d else (F(w["sum_dd"], npair) - md * md) / var_d)
+        put(o, "acf1_abs_return", None if not npair or not var_abs else (F(w["sum_abs_dd"], npair) - mabs * mabs) / var_abs)
+        put(o, "mean_trade_vol", div(w["sum_trade_vol"], ns))
+        put(o, "mean_bid_vol", div(w["sum_bid_vol"], ns))
+        put(o, "mean_ask_vol", div(w["sum_ask_vol"], ns))
+    return out
+
+
 # bk_open_summary / bk_open_order: one trader's rows of the open-order tables (ManyBookEnv.open_orders)
 OPEN_SUMMARY_DTYPE = np.dtype(
     {"names": ["bid_vol", "ask_vol", "n_bid", "n_ask", "best_bid", "best_ask"], "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
@@ -256,6 +317,12 @@ SIGNATURES = {
     "bk_get_trade_bars": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_trade_bars_clear": (_i32, [_vp, _vp]),
     "bk_trade_bars_clear_device": (_i32, [_vp, _vp]),
+    "bk_series_enable": (_i32, [_vp]),
+    "bk_series_fold": (_i32, [_vp]),
+    "bk_series_clear": (_i32, [_vp, _vp]),
+    "bk_series_clear_device": (_i32, [_vp, _vp]),
+    "bk_series_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_series": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -53,6 +53,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
 #include "trade_bars.hpp"
+#include "series.hpp"
 #include "open_orders.hpp"
 #include "open_queue.hpp"
 #include "quotes_ingress.hpp"
@@ -70,6 +71,10 @@ static_assert(sizeof(bk_account) == 32 && sizeof(bk_account) == 2 * sizeof(bk_u3
               "bk_account layout / flag (accounts.hpp)");
 static_assert(sizeof(bk_trade_bar) == 48 && sizeof(bk_trade_bar) == trade_bars::ROW_VECS * sizeof(bk_u32x4),
               "bk_trade_bar layout (trade_bars.hpp)");
+static_assert(sizeof(bk_series_row) == 192 && sizeof(bk_series_row) == series::ROW_VECS * sizeof(bk_u32x4) &&
+                  sizeof(bk_series_row) == series::ROW_WORDS * 8 && offsetof(bk_series_row, carry_m) == series::CARRY_M * 8 &&
+                  offsetof(bk_series_row, min_m) == series::MIN_M * 8 && offsetof(bk_series_row, sum_d4_lo) == series::SUM_D4_LO * 8,
+              "bk_series_row layout (series_fold.hpp)");
 static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
@@ -189,6 +194,11 @@ struct bk_env {
   DevBuf<uint8_t> bars_mask;  // bk_trade_bars_clear: device staging of the host mask [n_books]
   uint32_t bars_window = 0;   // 0: no bars
   bool bars_consume = false;
+  // bk_series_enable: one row of series moments per book [n_books] of 192 B, folded from the history ring (series.hpp)
+  DevBuf<bk_u32x4> series_rows;
+  DevBuf<uint8_t> series_mask;  // bk_series_clear: device staging of the host mask [n_books]
+  uint64_t series_seen = 0;     // steps below it are folded (a host integer, as steps_done)
+  bool series = false;
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -2474,6 +2484,56 @@ int bk_clear_history(bk_env* env) {
   return BK_OK;
 }
 
+// ------------------------------------------------------------------ per-book series moments of the level-2 history
+// No counterpart in the reference.  series_rows[n_books] rows of 24 u64 words, folded from the history ring by
+// series::k_fold on the env's stream when bk_series_fold, a masked clear or a reset asks; series.hpp, DESIGN.md 2.22.
+// steps [series_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
+static void launch_series_fold(bk_env* env, uint64_t n) {
+  series::FoldArgs g{};
+  g.hist = env->hist.p;
+  g.hist_cap = env->cfg.history_capacity;
+  g.n_books = env->cfg.n_books;
+  g.W = env->W;
+  g.slot0 = static_cast<uint32_t>(env->series_seen % env->cfg.history_capacity);
+  g.n = static_cast<uint32_t>(n);
+  g.rows = env->series_rows.p;
+  const uint32_t blocks = (g.n_books + series::FOLD_WAVES - 1) / series::FOLD_WAVES;
+  hipLaunchKernelGGL(series::k_fold, dim3(blocks), dim3(64 * series::FOLD_WAVES), 0, env->stream, g);
+}
+
+// rows of the masked books (one mask byte per M books; nullptr: every book) -> cleared, or only their carry words -> 0
+static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
+  series::ClearArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.n_books = env->cfg.n_books;
+  g.carry_only = carry_only ? 1u : 0u;
+  g.rows = env->series_rows.p;
+  const uint32_t blocks = (g.n_books + series::FOLD_WAVES - 1) / series::FOLD_WAVES;
+  hipLaunchKernelGGL(series::k_clear, dim3(blocks), dim3(64 * series::FOLD_WAVES), 0, env->stream, g);
+}
+
+// fold what is outstanding (nothing: no launch); a step the ring no longer retains refuses, rows and cursor unchanged
+static int series_fold_outstanding(bk_env* env) {
+  const uint64_t first = hist_first(env);
+  if (env->series_seen < first) {
+    char msg[224];
+    std::snprintf(msg, sizeof msg,
+                  "%llu step(s) of the series were lost: steps [%llu, %llu) are no longer retained by the history ring "
+                  "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
+                  "bk_series_clear(env, NULL) starts again",
+                  static_cast<unsigned long long>(first - env->series_seen), static_cast<unsigned long long>(env->series_seen),
+                  static_cast<unsigned long long>(first));
+    return fail(BK_INVALID_ARGUMENT, msg);
+  }
+  if (env->series_seen == env->steps_done) return BK_OK;
+  if (int rc = use_device(env)) return rc;
+  launch_series_fold(env, env->steps_done - env->series_seen);
+  HIPCHK(hipGetLastError());
+  env->series_seen = env->steps_done;
+  return BK_OK;
+}
+
 static int read_hdr(bk_env* env, uint32_t book, int first_dw, int n_dw, uint32_t* out) {
   if (int rc = use_device(env)) return rc;
   HIPCHK(hipStreamSynchronize(env->stream));
@@ -2623,6 +2683,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (env->bars_window)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trade bars (bk_trade_bars_enable) is not supported: "
                                      "its trade records would pass as the next step's");
+  if (env->series)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with series moments (bk_series_enable) is not supported: "
+                                     "the book's next record would pass as the successor of the replaced book's last");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
   // (the agents' log holds what k_step_batch_log wrote for every id below the book's counter: a loaded book's orders
@@ -3095,6 +3158,11 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
   hipLaunchKernelGGL(k_book_service, dim3((B + 255) / 256), dim3(256), 0, env->stream, env->state.p, env->stride, B, 0,
                      0u);
   HIPCHK(hipGetLastError());
+  if (env->series) {  // series moments are no part of a checkpoint: every row starts again at the restored step
+    launch_series_clear(env, nullptr, 1, false);
+    HIPCHK(hipGetLastError());
+    env->series_seen = env->steps_done;
+  }
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
 }
@@ -3217,6 +3285,11 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
 int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
   if (int rc = reset_ok(env, slot, mask_dev)) return rc;
   if (int rc = use_device(env)) return rc;
+  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
+    if (int rc = series_fold_outstanding(env)) return rc;
+    launch_series_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
   launch_reset_books(env, env->snaps[slot].buf.p, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
   // which books changed is known on the device only: the members' lists of every book are rebuilt from the owner tags
@@ -3396,6 +3469,11 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
   if (int rc = use_device(env)) return rc;
   const bk_env::IngressSnapshot& s = env->isnaps[slot];
   const uint32_t n_units = env->cfg.n_books / env->M;
+  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
+    if (int rc = series_fold_outstanding(env)) return rc;
+    launch_series_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
   launch_reset_books(env, s.buf.p, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
   uint32_t* counter = env->reset_list.p + n_units;
@@ -3611,6 +3689,77 @@ int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = use_device(env)) return rc;
   if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->bars_mask)) return rc;
   return bk_trade_bars_clear_device(env, env->bars_mask.p);
+}
+
+// ------------------------------------------------------------------ per-book series moments: the entries
+// (the launches and the fold of what is outstanding stand with the history ring above)
+int bk_series_enable(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->cfg.history_capacity)
+    return fail(BK_INVALID_ARGUMENT, "the series moments are folded from the level-2 history ring: history_capacity must be > 0");
+  if (env->series) return fail(BK_INVALID_ARGUMENT, "the series moments are already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  DevBuf<bk_u32x4> rows;
+  HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * series::ROW_VECS));
+  std::swap(env->series_rows.p, rows.p), std::swap(env->series_rows.n, rows.n);
+  env->series = true;
+  env->series_seen = env->steps_done;
+  launch_series_clear(env, nullptr, 1, false);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int series_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->series) return fail(BK_INVALID_ARGUMENT, "this env has no series moments: call bk_series_enable first");
+  return BK_OK;
+}
+
+int bk_series_fold(bk_env* env) {
+  if (int rc = series_ok(env)) return rc;
+  return series_fold_outstanding(env);
+}
+
+int bk_series_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = series_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  if (mask_dev) {
+    if (int rc = series_fold_outstanding(env)) return rc;
+  } else {
+    env->series_seen = env->steps_done;  // every row starts again here: nothing is folded, lost steps are forgotten
+  }
+  launch_series_clear(env, mask_dev, 1, false);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_series_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = series_ok(env)) return rc;
+  if (!mask_host) return bk_series_clear_device(env, nullptr);
+  if (env->series_seen < hist_first(env)) return series_fold_outstanding(env);  // (refused before the mask is staged)
+  if (int rc = use_device(env)) return rc;
+  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->series_mask)) return rc;
+  return bk_series_clear_device(env, env->series_mask.p);
+}
+
+int bk_series_device_ptr(bk_env* env, void** out) {
+  if (int rc = series_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->series_rows.p;
+  return BK_OK;
+}
+
+int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out) {
+  if (int rc = series_ok(env)) return rc;
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  if (n_books)
+    HIPCHK(hipMemcpy(out, env->series_rows.p + static_cast<size_t>(first_book) * series::ROW_VECS,
+                     static_cast<size_t>(n_books) * sizeof(bk_series_row), hipMemcpyDeviceToHost));
+  return BK_OK;
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env

@@ -1197,6 +1197,90 @@ class ManyBookEnv:
         if sync:
             self.sync()
 
+    # ------------------------------------------------------------ per-book series moments of the level-2 history
+    SERIES_DTYPE = _lib.SERIES_DTYPE
+
+    def enable_series(self):
+        """``bk_series_enable``: keep one row of integer sums per book in device memory - over the book's whole series of
+        level-2 records: counts, sums of twice the mid, of the spread and its square, of the touch volumes and the traded
+        volume, of the mid's step-to-step change ``d`` up to its fourth power, of ``d * d_prev`` and ``|d| * |d_prev|``, and
+        the extremes (``SERIES_DTYPE``; include/bourse_amd.h states what one record adds).  ``fold_series()`` folds the
+        steps run since the last fold from the history ring, on the env's stream; nothing leaves the device until
+        ``series()`` is read.  Needs ``history_capacity > 0``; works with ``run`` on every pipeline, ``step``, the device
+        ingress and markets.  Steps before the call are not counted.  The reference has no counterpart."""
+        check(self._L.bk_series_enable(self._h))
+
+    def fold_series(self, sync: bool = False):
+        """``bk_series_fold``: queue the fold of every step run since the last fold (no new step: no launch).  Raises if
+        one of them is no longer retained by the ring - more than ``history_capacity`` steps since the last fold, or
+        ``clear_history()`` - naming how many were lost; rows and cursor are then unchanged and ``clear_series()`` starts
+        again."""
+        check(self._L.bk_series_fold(self._h))
+        if sync:
+            self.sync()
+
+    def series(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array
+        (``SERIES_DTYPE``).  Waits for the env's stream; does NOT fold."""
+        n = self.n_books - int(first_book) if n_books is None else int(n_books)
+        if int(first_book) < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        out = np.zeros(n, dtype=_lib.SERIES_DTYPE)
+        check(self._L.bk_get_series(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def series_device_ptr(self) -> int:
+        """Device address of the table, ``bk_series_row[n_books]`` (for on-device consumers)."""
+        out = C.c_void_p()
+        check(self._L.bk_series_device_ptr(self._h, C.byref(out)))
+        return int(out.value)
+
+    def series_view(self) -> "SeriesView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, 24)``, the words in
+        ``SERIES_DTYPE``'s order (unsigned words read as int64: the same bits).  ``torch.as_tensor(env.series_view(),
+        device="cuda")`` is a zero-copy tensor that every later fold updates; it is written on the env's stream, so read
+        it there (or after ``sync()``)."""
+        return SeriesView(self, self.series_device_ptr(), (self.n_books, 24), self._stream)
+
+    def clear_series(self, mask=None, sync: bool = True):
+        """With a ``mask`` (one entry per BOOK): fold what is outstanding (raising as ``fold_series`` does), then clear the
+        rows of the books with ``mask[b]`` set, carry included.  ``None``: clear every row and count from the current step
+        on without folding - the way on after lost steps.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
+        (``bk_series_clear`` / ``bk_series_clear_device``).  ``reset_books`` / ``reset_ingress_books`` fold and then cut only
+        the carry of the books they reset: the sums go on across episodes and no return spans a reset."""
+        if mask is None:
+            check(self._L.bk_series_clear_device(self._h, None))
+        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
+            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
+            if n != self.n_books:
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_series_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask))
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError("mask: a bool or uint8 array is needed")
+            m = m.astype(np.uint8, copy=False)
+            if m.shape != (self.n_books,):
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(self._L.bk_series_clear(self._h, m.ctypes.data_as(C.c_void_p)))
+        if sync:
+            self.sync()
+
+    def run_series(self, n_steps: int, chunk: Optional[int] = None):
+        """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
+        ``history_capacity``) until ``n_steps`` are run: the way to run more steps than the ring holds.  Nothing waits
+        between the chunks, or at the end."""
+        c = self.history_capacity if chunk is None else int(chunk)
+        if not 1 <= c <= self.history_capacity:
+            raise ValueError("run_series needs 1 <= chunk <= history_capacity")
+        self.fold_series()  # (steps run before the call are not pushed out of the ring by the first chunk)
+        left = int(n_steps)
+        while left > 0:
+            n = min(c, left)
+            self.run(n, sync=False)
+            self.fold_series()
+            left -= n
+
     # ------------------------------------------------------------ open orders of an env with the device ingress
     OPEN_SUMMARY_DTYPE = _lib.OPEN_SUMMARY_DTYPE
     OPEN_ORDER_DTYPE = _lib.OPEN_ORDER_DTYPE
@@ -1395,6 +1479,10 @@ class AccountsView:
 
 class TradeBarsView(AccountsView):
     """``ManyBookEnv.trade_bars_view()``: the ring of trade bars where it lives, read the same way."""
+
+
+class SeriesView(AccountsView):
+    """``ManyBookEnv.series_view()``: the table of series moments where it lives, read the same way."""
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):

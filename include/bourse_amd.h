@@ -684,6 +684,80 @@ int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host);
  * on the env's stream.  (No counterpart in the reference.) */
 int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev);
 
+/* ------------------------------------------------------ per-book series moments of the level-2 history */
+/* An opt-in table series[n_books] in DEVICE memory: one row of integer sums per book over the book's whole SERIES of
+ * level-2 records - what a sweep or a calibration wants back from every book (mean and variance of the spread, moments of
+ * the mid-price returns, their lag-1 autocovariance and that of their magnitudes, traded volume, depth) - folded on the
+ * env's stream from the history ring that the stepping kernels already write, with no host wait and without the history
+ * ever leaving the device (bourse_amd/csrc/series.hpp, series_fold.hpp).  It serves every flow that writes
+ * the ring - bk_run on all pipelines, bk_step, the device ingress, markets - and touches no stepping kernel.  The
+ * reference has no counterpart for any of these entries.
+ *
+ * What one record adds.  Of the record of step s and book b only the first five words are read, {trade_vol, bid_price,
+ * ask_price, ask_vol, bid_vol}; an empty side reads bid_price == 0 / ask_price == 0xFFFFFFFF, trade_vol is the step's own.
+ * The book's carry is {have_m, m_prev, have_d, d_prev}.
+ *   always:            n_steps += 1, sum_trade_vol += tv, sum_trade_vol_sq += tv * tv, n_trade_steps += (tv > 0),
+ *                      sum_bid_vol += bid_vol, sum_ask_vol += ask_vol;
+ *   two-sided (bid != 0 && ask != 0xFFFFFFFF), m = bid + ask (TWICE the mid), sp = ask - bid (u32 wrapping):
+ *                      n_two_sided += 1, sum_m += m, sum_spread += sp, sum_spread_sq += sp * sp, min_m, max_m;
+ *   two-sided and have_m, d = m - m_prev (signed, |d| < 2^33), a = |d|:
+ *                      n_ret += 1, sum_d += d, sum_abs_d += a, sum_d2 += a * a, sum_d4 += a^4 (a 128-bit pair, the power
+ *                      exact modulo 2^128), max_abs_d;
+ *   and have_d:        n_pairs += 1, sum_dd += d * d_prev (signed), sum_abs_dd += a * |d_prev|;
+ *   then the carry:    two-sided: m_prev = m, have_m = 1, and have_d = 1, d_prev = d if there was a return, else have_d = 0;
+ *                      one-sided: have_m = have_d = 0.  A word whose have_ bit is clear is 0.
+ * A one-sided step breaks the chain: a return exists only between two CONSECUTIVE two-sided steps, a pair only over three.
+ * All 64-bit words are sums modulo 2^64, sum_d4 a sum modulo 2^128; signed words are two's complement.  The carry words
+ * exist so that folding steps [x, y) and then [y, z) leaves the same row as one fold over [x, z), for every split. */
+typedef struct bk_series_row { /* 192 B, twelve 16-byte vectors, little-endian */
+  uint64_t n_steps, n_two_sided;
+  uint64_t sum_m, sum_spread, sum_spread_sq; /* of two-sided steps; m = bid + ask, twice the mid */
+  uint64_t sum_bid_vol, sum_ask_vol;         /* of every step */
+  uint64_t sum_trade_vol, sum_trade_vol_sq, n_trade_steps;
+  uint64_t n_ret;
+  int64_t sum_d;
+  uint64_t sum_abs_d, sum_d2, sum_d4_lo, sum_d4_hi, max_abs_d;
+  uint64_t n_pairs;
+  int64_t sum_dd;
+  uint64_t sum_abs_dd;
+  uint64_t min_m, max_m; /* 2^64 - 1 and 0 before the first two-sided step */
+  uint64_t carry_m;      /* m_prev, bit 63 = have_m, bit 62 = have_d */
+  int64_t carry_d;       /* d_prev */
+} bk_series_row;
+/* Enabling.  Accepted on any env with history_capacity > 0, at any time, once.  Allocates the rows (arrays of their own:
+ * the state block, checkpoints and snapshots are unchanged), clears every row - all zeros except min_m = 2^64 - 1 - and
+ * sets the env's step cursor series_seen, a host integer as bk_steps_done is, to bk_steps_done: earlier steps are not
+ * counted.  A refusal - here and in the entries below: a null env, history_capacity == 0, a second call, any other entry
+ * before this one - returns BK_INVALID_ARGUMENT, leaves the env unchanged and puts the reason in bk_last_error().
+ *
+ * bk_reset_books* and bk_ingress_reset_books* on such an env first fold what is outstanding (and refuse the reset if
+ * steps were lost, see bk_series_fold), then zero only the carry words of the books they reset (every book of a masked
+ * market): the sums go on across episodes and no return spans a reset; clear by mask if a new row is wanted.
+ * bk_checkpoint_load clears every row and sets the cursor to the restored step count.  bk_load_book is refused.  bk_warm
+ * writes no history and restores the counter: unaffected.  An env without the table launches nothing new.  (No counterpart
+ * in the reference.) */
+int bk_series_enable(bk_env* env);
+/* Queues, on the env's stream and without any host wait, the fold of steps [series_seen, bk_steps_done) of every book;
+ * then series_seen = bk_steps_done.  No new step: no launch.  If a step of that range is no longer retained by the ring -
+ * it wrapped (more than history_capacity steps since the last fold), or bk_clear_history was called - returns
+ * BK_INVALID_ARGUMENT with the number of lost steps in bk_last_error() and leaves rows and cursor unchanged: a lost step
+ * is never silent and needs no flag bit.  bk_series_clear with a NULL mask is the way on.  (No counterpart in the reference.) */
+int bk_series_fold(bk_env* env);
+/* Clearing.  mask [n_books] bytes, one per BOOK.  With a mask: folds what is outstanding first (refusing as bk_series_fold
+ * does), then clears the rows, carry included, of the books b with mask[b] != 0.  NULL: clears every row and sets the
+ * cursor to bk_steps_done WITHOUT folding.  From a HOST mask: staged on the env's stream and waited for, the clear itself
+ * stays asynchronous.  (No counterpart in the reference.) */
+int bk_series_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: at most
+ * two launches on the env's stream.  (No counterpart in the reference.) */
+int bk_series_clear_device(bk_env* env, const uint8_t* mask_dev);
+/* Device pointer of the table, bk_series_row[n_books], for on-device consumers; valid for the env's life, written on the
+ * env's stream.  (No counterpart in the reference.) */
+int bk_series_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory.  Waits for the env's stream; does NOT fold.
+ * (No counterpart in the reference.) */
+int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out);
+
 /* ------------------------------------------------------ open orders of a device-ingress env */
 /* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
  * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or

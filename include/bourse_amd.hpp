@@ -291,6 +291,29 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_trade_bars_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-book series moments of the level-2 history (bk_series_enable): one row of integer sums per book over its whole
+  // series, folded on the device from the history ring (needs history_capacity > 0); the reference has no counterpart
+  void enable_series() { check(bk_series_enable(h_)); }
+  // queue the fold of the steps run since the last fold (no host wait); throws, naming the count, if steps were lost
+  void fold_series() { check(bk_series_fold(h_)); }
+  // rows of books [first_book, first_book + n_books) (waits for the env's stream; does not fold)
+  std::vector<bk_series_row> series(uint32_t first_book, uint32_t n_books) {
+    std::vector<bk_series_row> rows(n_books);
+    check(bk_get_series(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<bk_series_row> series() { return series(0, n_books_); }
+  // the table in device memory, bk_series_row[n_books]
+  bk_series_row* series_device_ptr() {
+    void* p = nullptr;
+    check(bk_series_device_ptr(h_, &p));
+    return static_cast<bk_series_row*>(p);
+  }
+  // a mask (one byte per book): fold, then clear those books' rows; an empty mask: clear every row without folding
+  void clear_series(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_series_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
   // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
   void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
