@@ -201,6 +201,17 @@ RANDOM_AGENTS_DTYPE = np.dtype(
     {"names": ["n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate"],
      "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<f4"], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 28})
 
+# bk_agent_desc (AgentDesc) the same way: the rows of ManyBookEnv.retune_agents' table; as 4-byte words a row is 26 of them,
+# so device code can address the fields of an int32 [n_units, n_members, 26] tensor (word = offset // 4)
+AGENT_DESC_DTYPE = np.dtype(
+    {"names": ["type", "n_agents", "tick_lo", "tick_hi", "vol_lo", "vol_hi", "tick_size", "activity_rate", "agent_id_start",
+               "p_limit", "p_market", "p_cancel", "trade_vol", "reserved", "price_dist_mu", "price_dist_sigma", "decay",
+               "demand", "scale", "order_ratio"],
+     "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<f4", "<u4", "<f4", "<f4", "<f4", "<u4", "<u4", "<f8", "<f8",
+                 "<f8", "<f8", "<f8", "<f8"],
+     "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64, 72, 80, 88, 96], "itemsize": 104})
+
+
 class IngressArrays(C.Structure):
     """bk_ingress_arrays: the pinned staging arrays of the next bk_submit_instructions_host call."""
     _fields_ = [("capacity", C.c_uint64), ("book_offsets", C.c_void_p), ("action", C.c_void_p), ("side", C.c_void_p),
@@ -248,6 +259,11 @@ SIGNATURES = {
     "bk_set_random_agents_per_book": (_i32, [_vp, _u32, _vp, _p32]),
     "bk_set_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc)]),
     "bk_set_agents_per_book": (_i32, [_vp, _u32, C.POINTER(AgentDesc), _p32]),
+    "bk_retune_random_agents_device": (_i32, [_vp, _u32, _vp, _vp, _vp]),
+    "bk_retune_random_agents": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_retune_agents_device": (_i32, [_vp, _u32, _vp, _vp, _vp]),
+    "bk_retune_agents": (_i32, [_vp, _u32, _vp, _vp]),
+    "bk_retune_rejected": (_i32, [_vp, _p64]),
     "bk_set_market_agents": (_i32, [_vp, _u32, C.POINTER(AgentDesc), _p32]),
     "bk_run": (_i32, [_vp, _u64]),
     "bk_l2_width": (_u32, [_vp]),

@@ -14,20 +14,10 @@
 #include <vector>
 
 #include "../../include/bourse_amd.h"
+#include "agent_rows.hpp"  // Group, MixedDesc and the checks and arithmetic of one entry (shared with retune.hpp)
 #include "host_math.hpp"
 
 namespace bkd {
-
-struct Group {  // RandomAgents::new, host-preprocessed
-  uint32_t n;          // agents in the group
-  uint32_t thr;        // activity: (u32 >> 8) < thr  <=>  f32 draw < activity_rate (exact, see host)
-  uint32_t tick_lo, tick_rng, tick_zone;
-  uint32_t vol_lo, vol_rng, vol_zone;
-  uint32_t tick_size;  // the agents' tick size
-  uint32_t asset;      // RandomMarketAgents: the asset (book of the market) the group trades
-  uint32_t pad[2];
-};
-static_assert(sizeof(Group) == 48, "Group: 48-byte records (the per-unit table is read as three 16-byte loads)");
 
 // FNV-1a of n records (the checkpoint header's agent-set hash)
 inline uint64_t groups_hash(const Group* g, size_t n) {
@@ -50,27 +40,16 @@ inline int make_groups(const bk_random_agents* rows, uint32_t n_groups, const ui
   };
   for (uint32_t g = 0; g < n_groups; ++g) {
     const bk_random_agents& r = rows[g];
-    if (r.tick_lo >= r.tick_hi || r.vol_lo >= r.vol_hi)
-      return fail(BK_INVALID_ARGUMENT, g, "empty tick/vol range");  // gen_range asserts low < high
-    // every sampled price tick * tick_size must pass create_order's tick check (else `.unwrap()` panics,
-    // random_agent.rs:103-110)
     const uint32_t asset = assets ? assets[g] : 0u;
-    if (asset >= M) return fail(BK_INVALID_ARGUMENT, g, "group asset index out of range");
-    if (r.tick_size % asset_tick[asset] != 0)
-      return fail(BK_PRICE_NOT_TICK_MULTIPLE, g, "agent tick_size must be a multiple of the env tick_size");
-    if (static_cast<uint64_t>(r.tick_hi - 1) * r.tick_size >= 0xFFFFFFFFull || r.tick_lo == 0)
-      return fail(BK_INVALID_ARGUMENT, g, "limit prices must lie in (0, u32::MAX)");
-    Group G{};
-    G.n = r.n_agents;
-    G.thr = activity_threshold(r.activity_rate);
-    G.tick_lo = r.tick_lo;
-    G.tick_rng = r.tick_hi - r.tick_lo;
-    G.tick_zone = sample_zone(G.tick_rng);
-    G.vol_lo = r.vol_lo;
-    G.vol_rng = r.vol_hi - r.vol_lo;
-    G.vol_zone = sample_zone(G.vol_rng);
-    G.tick_size = r.tick_size;
-    G.asset = asset;
+    Group G;
+    uint32_t why = 0;
+    if (int rc = agent_rows::group_row(r, asset, asset < M ? asset_tick[asset] : 0u, &G, &why)) {  // (agent_rows.hpp)
+      const char* m = why == agent_rows::WHY_EMPTY_RANGE     ? "empty tick/vol range"
+                      : why == agent_rows::WHY_ASSET         ? "group asset index out of range"
+                      : why == agent_rows::WHY_TICK_MULTIPLE ? "agent tick_size must be a multiple of the env tick_size"
+                                                       : "limit prices must lie in (0, u32::MAX)";
+      return fail(rc, g, m);
+    }
     *total += r.n_agents;
     out[g] = G;
   }
@@ -115,19 +94,6 @@ constexpr int MAX_MEMBERS = 4;
 constexpr int MAX_INGRESS_MEMBERS = 8;
 constexpr int MAX_ASSETS = 8;  // books per market (MarketEnv<ASSETS>)
 
-struct MixedDesc {
-  uint32_t type;  // 0 RandomAgents, 1 NoiseAgent, 2 MomentumAgent
-  uint32_t n;
-  uint32_t thr, tick_lo, tick_rng, tick_zone, vol_lo, vol_rng, vol_zone, tick_size;  // RandomAgents (see Group)
-  uint32_t thr_limit, thr_market;  // NoiseAgent: (u32 >> 8) < thr  <=>  gen::<f32>() < p
-  int32_t keep_thr;                // cancel_live_orders keeps an order iff (u32 >> 8) > keep_thr  <=>  gen::<f32>() > p_cancel
-  uint32_t trade_vol;
-  uint32_t slot_base;              // RandomAgents: first fixed slot
-  uint32_t pad;
-  double mu, sigma, decay, demand, scale, order_ratio, n_f, tick_f;
-};
-static_assert(sizeof(MixedDesc) == 128, "MixedDesc layout");
-
 // FNV-1a over bytes, continuing from h
 inline uint64_t fnv1a_bytes(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
   const unsigned char* c = static_cast<const unsigned char*>(p);
@@ -160,44 +126,16 @@ inline int make_mixed_descs(const bk_agent_desc* members, uint32_t n_members, co
     uint32_t& fixed = fixed_a[as];  // fixed RandomAgents slots are counted per book
     const bk_agent_desc& m = members[i];
     MixedDesc D;
-    std::memset(&D, 0, sizeof(D));
-    D.type = m.type;
-    D.n = m.n_agents;
-    if (m.tick_size == 0 || m.tick_size % asset_tick[as] != 0)
-      return fail(BK_PRICE_NOT_TICK_MULTIPLE, i, "member tick_size must be a non-zero multiple of the env tick_size");
-    if (m.type == BK_AGENT_RANDOM) {
-      if (m.tick_lo >= m.tick_hi || m.vol_lo >= m.vol_hi || m.tick_lo == 0 ||
-          static_cast<uint64_t>(m.tick_hi - 1) * m.tick_size >= 0xFFFFFFFFull)
-        return fail(BK_INVALID_ARGUMENT, i, "bad RandomAgents ranges");
-      D.thr = activity_threshold(m.activity_rate);
-      D.tick_lo = m.tick_lo;
-      D.tick_rng = m.tick_hi - m.tick_lo;
-      D.tick_zone = sample_zone(D.tick_rng);
-      D.vol_lo = m.vol_lo;
-      D.vol_rng = m.vol_hi - m.vol_lo;
-      D.vol_zone = sample_zone(D.vol_rng);
-      D.tick_size = m.tick_size;
-      D.slot_base = fixed;
-      fixed += m.n_agents;
-    } else if (m.type == BK_AGENT_NOISE || m.type == BK_AGENT_MOMENTUM) {
-      if (m.n_agents > 0xFFFFu) return fail(BK_INVALID_ARGUMENT, i, "n_agents is a u16 in the reference");
-      if (!(m.price_dist_sigma >= 0.0) || !std::isfinite(m.price_dist_sigma) || !std::isfinite(m.price_dist_mu))
-        return fail(BK_INVALID_ARGUMENT, i, "LogNormal::new(mu, sigma) needs finite mu and sigma >= 0");  // .unwrap()
-      D.thr_limit = activity_threshold(m.p_limit);
-      D.thr_market = activity_threshold(m.p_market);
-      D.keep_thr = keep_threshold(m.p_cancel);
-      D.trade_vol = m.trade_vol;
-      D.mu = m.price_dist_mu;
-      D.sigma = m.price_dist_sigma;
-      D.decay = m.decay;
-      D.demand = m.demand;
-      D.scale = m.scale;
-      D.order_ratio = m.order_ratio;
-      D.n_f = static_cast<double>(m.n_agents);
-      D.tick_f = static_cast<double>(m.tick_size);
-    } else {
-      return fail(BK_INVALID_ARGUMENT, i, "unknown agent type");
+    uint32_t why = 0;
+    if (int rc = agent_rows::mixed_row(m, asset_tick[as], fixed, &D, &why)) {  // (agent_rows.hpp)
+      const char* t = why == agent_rows::WHY_TICK_MULTIPLE   ? "member tick_size must be a non-zero multiple of the env tick_size"
+                      : why == agent_rows::WHY_RANDOM_RANGES ? "bad RandomAgents ranges"
+                      : why == agent_rows::WHY_N_U16         ? "n_agents is a u16 in the reference"
+                      : why == agent_rows::WHY_LOGNORMAL     ? "LogNormal::new(mu, sigma) needs finite mu and sigma >= 0"
+                                                       : "unknown agent type";
+      return fail(rc, i, t);
     }
+    if (m.type == BK_AGENT_RANDOM) fixed += m.n_agents;
     out[i] = D;
   }
   return BK_OK;

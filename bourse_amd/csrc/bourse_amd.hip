@@ -57,6 +57,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "open_orders.hpp"
 #include "open_queue.hpp"
 #include "quotes_ingress.hpp"
+#include "retune.hpp"
 
 using namespace bkd;
 
@@ -210,6 +211,15 @@ struct bk_env {
   DevBuf<bk_u32x4> quote_stage;
   bk_quote* quote_pin = nullptr;
   hipEvent_t quote_copied = nullptr;
+  // bk_retune_*: the count of refused units (device), the members' installed first trader ids as the kernel compares them
+  // (uploaded by the per-unit install, synchronously like its table), and the host forms' staging: caller -> pinned (before the call
+  // returns) -> device (on the env's stream), rows then mask, made at the first call and grown only by a wider table
+  DevBuf<unsigned long long> retune_count;
+  DevBuf<uint32_t> retune_id0;  // [units][n_mixed], uploaded by bk_set_agents_per_book beside the table
+  DevBuf<unsigned char> retune_stage;
+  unsigned char* retune_pin = nullptr;
+  size_t retune_pin_bytes = 0;
+  hipEvent_t retune_copied = nullptr;
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -1077,6 +1087,8 @@ void bk_env_destroy(bk_env* env) {
   if (env->hi.out) (void)hipStreamSynchronize(env->hi.out);
   if (env->mods_flag_host) (void)hipHostFree(env->mods_flag_host);
   if (env->quote_pin) (void)hipHostFree(env->quote_pin);
+  if (env->retune_pin) (void)hipHostFree(env->retune_pin);
+  if (env->retune_copied) (void)hipEventDestroy(env->retune_copied);
   if (env->quote_copied) (void)hipEventDestroy(env->quote_copied);
   for (auto& r : env->hi.retired) (void)hipHostFree(r.pin);
   env->hi.retired.clear();
@@ -2240,6 +2252,167 @@ int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc*
   if (int rc = install_members(env, row0, n_members, assets, fixed_a, std::move(t))) return rc;
   env->member_id0.resize(n);
   for (size_t k = 0; k < n; ++k) env->member_id0[k] = members[k].agent_id_start;
+  // ... and on the device for bk_retune_agents*, which compare a row's agent_id_start with them (member_id0_dev is the
+  // ingress path's own copy, made only at a device-ingress env's first update)
+  HIPCHK(env->retune_id0.alloc(n));
+  HIPCHK(hipMemcpy(env->retune_id0.p, env->member_id0.data(), n * 4, hipMemcpyHostToDevice));
+  return BK_OK;
+}
+
+// ------------------------------------------------------------------ retune: the installed per-unit table, in place
+// bk_retune_*: the parameter records of the masked units of the installed per-unit table are replaced on the device
+// (retune.hpp).  Books, RNG states, held ids, member lists, momentum state, the stale marks,
+// agent_installs and agents_hash stay: the hash goes on naming the install, whose shape a retune cannot change, so
+// checkpoints and snapshot slots taken on either side of a retune stay usable - they hold no parameters.  The host's
+// table / mtable keep the INSTALLED records: they are read for emptiness, for the hash and for the fixed fields only.
+static int retune_ok(bk_env* env, const void* rows, bool members, uint32_t width) {
+  if (!env || !rows) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (members) {
+    if (env->mtable.empty())
+      return fail(BK_INVALID_ARGUMENT, env->n_mixed ? "a retune rewrites the per-unit table: install the members with "
+                                                      "bk_set_agents_per_book (a table of identical rows costs nothing)"
+                                                    : "no per-unit table of members installed (bk_set_agents_per_book; an "
+                                                      "all-RandomAgents table is bk_retune_random_agents')");
+    if (width != env->n_mixed) return fail(BK_INVALID_ARGUMENT, "n_members differs from the installed table's");
+  } else {
+    if (env->table.empty())
+      return fail(BK_INVALID_ARGUMENT, !env->groups.empty() ? "a retune rewrites the per-unit table: install the groups with "
+                                                              "bk_set_random_agents_per_book (a table of identical rows costs "
+                                                              "nothing)"
+                                                            : "no per-unit table of RandomAgents groups installed "
+                                                              "(bk_set_random_agents_per_book)");
+    if (width != env->groups.size()) return fail(BK_INVALID_ARGUMENT, "n_groups differs from the installed table's");
+  }
+  return BK_OK;
+}
+
+// the one launch; the counter is made at the first call, everything else at the install
+static int launch_retune(bk_env* env, bool members, uint32_t width, const void* rows_dev, const uint8_t* mask_dev,
+                         uint32_t* status_dev) {
+  if (reinterpret_cast<uintptr_t>(rows_dev) & (members ? 7u : 3u))
+    return fail(BK_INVALID_ARGUMENT, members ? "rows must be 8-byte aligned" : "rows must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(status_dev) & 3u) return fail(BK_INVALID_ARGUMENT, "status must be 4-byte aligned");
+  if (int rc = use_device(env)) return rc;
+  if (!env->retune_count.p) {
+    HIPCHK(env->retune_count.alloc(1));
+    HIPCHK(hipMemsetAsync(env->retune_count.p, 0, 8, env->stream));
+  }
+  retune::Args g{};
+  g.rows = rows_dev;
+  g.table = members ? static_cast<void*>(env->dmtable.p) : static_cast<void*>(env->dtable.p);
+  g.mask = mask_dev;
+  g.status = status_dev;
+  g.rejected = env->retune_count.p;
+  g.id_start = env->retune_id0.p;
+  g.n_units = env->cfg.n_books / env->M;
+  g.width = width;
+  for (int i = 0; i < MAX_ASSETS; ++i) g.asset_tick[i] = env->asset_tick[i] ? env->asset_tick[i] : env->asset_tick[0];
+  for (uint32_t j = 0; j < width && members; ++j) g.member_assets |= static_cast<uint64_t>(env->member_asset[j]) << (8u * j);
+  const dim3 grid((g.n_units + retune::UNITS_PER_BLOCK - 1) / retune::UNITS_PER_BLOCK), block(64 * retune::WAVES);
+  if (members)
+    hipLaunchKernelGGL(retune::k_members, grid, block, 0, env->stream, g);
+  else
+    hipLaunchKernelGGL(retune::k_groups, grid, block, 0, env->stream, g);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+// Hold NO host synchronisation and, after the first call, no allocation: one launch on the env's stream.
+int bk_retune_random_agents_device(bk_env* env, uint32_t n_groups, const bk_random_agents* rows_dev, const uint8_t* mask_dev,
+                                   uint32_t* status_dev) {
+  if (int rc = retune_ok(env, rows_dev, false, n_groups)) return rc;
+  return launch_retune(env, false, n_groups, rows_dev, mask_dev, status_dev);
+}
+
+int bk_retune_agents_device(bk_env* env, uint32_t n_members, const bk_agent_desc* rows_dev, const uint8_t* mask_dev,
+                            uint32_t* status_dev) {
+  if (int rc = retune_ok(env, rows_dev, true, n_members)) return rc;
+  return launch_retune(env, true, n_members, rows_dev, mask_dev, status_dev);
+}
+
+// the host forms' rows (and mask) through the env's pinned and device staging into the same kernel
+static int retune_from_host(bk_env* env, bool members, uint32_t width, const void* rows, size_t row_bytes, const uint8_t* mask) {
+  if (int rc = use_device(env)) return rc;
+  const size_t n_units = env->cfg.n_books / env->M;
+  const size_t rows_bytes = (n_units * width * row_bytes + 15u) & ~size_t(15);
+  const size_t bytes = rows_bytes + n_units;
+  if (bytes > env->retune_pin_bytes) {
+    if (env->retune_copied) HIPCHK(hipEventSynchronize(env->retune_copied));
+    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier retune may still read the staging replaced here)
+    DevBuf<unsigned char> stage;
+    HIPCHK(stage.alloc(bytes));
+    void* pin = nullptr;
+    HIPCHK(hipHostMalloc(&pin, bytes, hipHostMallocDefault));
+    if (!env->retune_copied && hipEventCreateWithFlags(&env->retune_copied, hipEventDisableTiming) != hipSuccess) {
+      (void)hipHostFree(pin);
+      return fail(BK_HIP_ERROR, "hipEventCreateWithFlags failed");
+    }
+    if (env->retune_pin) (void)hipHostFree(env->retune_pin);
+    env->retune_pin = static_cast<unsigned char*>(pin);
+    env->retune_pin_bytes = bytes;
+    std::swap(env->retune_stage.p, stage.p), std::swap(env->retune_stage.n, stage.n);
+  } else {
+    HIPCHK(hipEventSynchronize(env->retune_copied));  // the call before this one has been uploaded: the pinned rows are free
+  }
+  std::memcpy(env->retune_pin, rows, n_units * width * row_bytes);  // the caller's table may be reused on return
+  if (mask) std::memcpy(env->retune_pin + rows_bytes, mask, n_units);
+  HIPCHK(hipMemcpyAsync(env->retune_stage.p, env->retune_pin, mask ? bytes : rows_bytes, hipMemcpyHostToDevice, env->stream));
+  HIPCHK(hipEventRecord(env->retune_copied, env->stream));
+  return launch_retune(env, members, width, env->retune_stage.p, mask ? env->retune_stage.p + rows_bytes : nullptr, nullptr);
+}
+
+// The masked units are checked on the host first, with the installs' row builders: on the first failure nothing changes.
+int bk_retune_random_agents(bk_env* env, uint32_t n_groups, const bk_random_agents* rows, const uint8_t* mask) {
+  if (int rc = retune_ok(env, rows, false, n_groups)) return rc;
+  const uint32_t n_units = env->cfg.n_books / env->M;
+  uint32_t assets[MAX_GROUPS];
+  for (uint32_t g = 0; g < n_groups; ++g) assets[g] = env->groups[g].asset;
+  std::vector<Group> rec(n_groups);
+  std::string msg;
+  for (uint32_t u = 0; u < n_units; ++u) {
+    if (mask && !mask[u]) continue;
+    const std::string where = "unit " + std::to_string(u) + ", ";
+    uint64_t total = 0;
+    const size_t row = static_cast<size_t>(u) * n_groups;
+    if (int rc = make_groups(rows + row, n_groups, assets, env->M, env->asset_tick, rec.data(), &total, &msg, where))
+      return fail(rc, msg);
+    for (uint32_t g = 0; g < n_groups; ++g)
+      if (int rc = agent_rows::group_fixed_ok(rec[g], env->table[row + g]))
+        return fail(rc, where + "group " + std::to_string(g) + ": n_agents differs from the installed value (a retune keeps the pool layout)");
+  }
+  return retune_from_host(env, false, n_groups, rows, sizeof(bk_random_agents), mask);
+}
+
+int bk_retune_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* rows, const uint8_t* mask) {
+  if (int rc = retune_ok(env, rows, true, n_members)) return rc;
+  const uint32_t n_units = env->cfg.n_books / env->M;
+  std::vector<MixedDesc> rec(n_members);
+  uint32_t fixed_a[MAX_ASSETS];
+  std::string msg;
+  for (uint32_t u = 0; u < n_units; ++u) {
+    if (mask && !mask[u]) continue;
+    const std::string where = "unit " + std::to_string(u) + ", ";
+    const size_t row = static_cast<size_t>(u) * n_members;
+    if (int rc = make_mixed_descs(rows + row, n_members, env->member_asset, env->asset_tick, rec.data(), fixed_a, &msg, where))
+      return fail(rc, msg);
+    for (uint32_t i = 0; i < n_members; ++i)
+      if (int rc = agent_rows::mixed_fixed_ok(rec[i], env->mtable[row + i], rows[row + i].agent_id_start, env->member_id0[row + i]))
+        return fail(rc, where + "member " + std::to_string(i) +
+                            ": type, n_agents or agent_id_start differs from the installed value (a retune keeps the members' kinds, "
+                            "pool layout and trader ids)");
+  }
+  return retune_from_host(env, true, n_members, rows, sizeof(bk_agent_desc), mask);
+}
+
+int bk_retune_rejected(bk_env* env, uint64_t* out) {
+  if (!env || !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = 0;
+  if (!env->retune_count.p) return BK_OK;  // (no retune yet)
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  unsigned long long n = 0;
+  HIPCHK(hipMemcpy(&n, env->retune_count.p, 8, hipMemcpyDeviceToHost));
+  *out = n;
   return BK_OK;
 }
 

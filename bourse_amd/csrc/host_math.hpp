@@ -6,7 +6,8 @@
 #include <cstdint>
 #include <vector>
 
-// the seeding is ONE text for the host (bk_env_create) and the device (book_reset.hpp): under hipcc it compiles for both
+// the seeding is ONE text for the host (bk_env_create) and the device (book_reset.hpp), and so are the thresholds and the
+// zone below (the installs and retune.hpp, through agent_rows.hpp): under hipcc they compile for both
 #if defined(__HIPCC__)
 #define BKD_HOST_DEVICE __host__ __device__
 #else
@@ -31,7 +32,7 @@ BKD_HOST_DEVICE inline void seed_from_u64(uint64_t seed, uint64_t& s0, uint64_t&
 
 // `gen::<f32>() < rate` with gen = (u32 >> 8) * 2^-24 (App. B.5) as an integer threshold on k = (u32 >> 8):
 // k * 2^-24 < rate  <=>  k < rate * 2^24 (exact in double)  <=>  k < ceil(rate * 2^24).
-inline uint32_t activity_threshold(float rate) {
+BKD_HOST_DEVICE inline uint32_t activity_threshold(float rate) {
   if (!(rate > 0.0f)) return 0;  // also NaN
   const double x = static_cast<double>(rate) * 16777216.0;
   if (x >= 16777216.0) return 16777216u;
@@ -40,14 +41,14 @@ inline uint32_t activity_threshold(float rate) {
 
 // cancel_live_orders keeps an order iff `gen::<f32>() > p_cancel` (common.rs:68): k * 2^-24 > p  <=>  k > floor(p * 2^24).
 // Returned as a signed bound: keep iff (int32)k > keep_threshold(p).
-inline int32_t keep_threshold(float p_cancel) {
+BKD_HOST_DEVICE inline int32_t keep_threshold(float p_cancel) {
   if (p_cancel != p_cancel) return 1 << 24;  // NaN: never kept
   const double y = std::floor(static_cast<double>(p_cancel) * 16777216.0);
   return y < 0.0 ? -1 : (y > 16777216.0 ? (1 << 24) : static_cast<int32_t>(y));
 }
 
 // UniformInt<u32>::sample_single's acceptance zone for `range` (App. B.3): accept iff lo32(x * range) <= zone
-inline uint32_t sample_zone(uint32_t range) { return (range << __builtin_clz(range)) - 1u; }
+BKD_HOST_DEVICE inline uint32_t sample_zone(uint32_t range) { return (range << __builtin_clz(range)) - 1u; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Jump-ahead of Xoroshiro128StarStar (rand_xoshiro 0.6.0).  The state transition T is linear over

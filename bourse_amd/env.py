@@ -632,13 +632,104 @@ class ManyBookEnv:
         n = len(rows[0]) if rows else 0
         if n == 0 or any(len(r) != n for r in rows):
             raise ValueError("every row of the table needs the same number (>= 1) of members")
-        arr = (AgentDesc * (n_units * n))()
-        for u, row in enumerate(rows):
-            for i, m in enumerate(row):
-                _fill_agent_desc(arr[u * n + i], m)
+        arr = _members_array(rows, n_units)
         as_arr = None if assets is None else np.asarray(assets, dtype=np.uint32)
         check(self._L.bk_set_agents_per_book(self._h, n, arr, None if as_arr is None else _lib.p32(as_arr)))
         self.members = None
+
+    # ------------------------------------------------------------ retune: the installed per-unit table, in place
+    def retune_random_agents(self, table, mask=None, status=None, sync: bool = True):
+        """Replace the RandomAgents parameters of the books ``mask`` names in the table ``set_random_agents_per_book``
+        installed, in place on the device (``bk_retune_random_agents`` / ``bk_retune_random_agents_device``): the same
+        agents, holding the same resting orders, draw from the new ``activity_rate``, ranges and tick size from the next
+        ``run`` / ``update_agents`` on.  Nothing else changes - books, RNG states, held ids, snapshots and checkpoints (which
+        hold no parameters: a reset or restore brings none back).  ``n_agents`` must stay what was installed.
+
+        ``table``: what ``set_random_agents_per_book`` takes (the host entry: every masked book is checked first, and
+        on the first bad entry nothing changes and the install's error is raised) - or a torch CUDA tensor /
+        ``__cuda_array_interface__`` object of the raw ``RANDOM_AGENTS_DTYPE`` rows ``[n_books, n_groups]`` (28 B each,
+        e.g. an int32 ``[n_books, n_groups, 7]`` tensor) written on the env's stream (the device entry: nothing passes
+        through the host, a book with a bad entry keeps its whole row).  ``mask`` (bool / uint8 per book, ``None`` = every
+        book) and ``status`` (4-byte ints, 2 per book: ``{code, first failing group}``) must be the same kind of object as
+        the table.  ``retune_rejected()`` counts the refused books.  Queued on the env's stream; ``sync`` waits for it."""
+        if self.assets > 1:
+            raise ValueError("markets take retune_random_market_agents")
+        self._retune(False, table, mask, status, sync,
+                     lambda t: _agents_table(t, self.n_books, lambda g: g.as_tuple() if isinstance(g, RandomAgents) else g))
+
+    def retune_agents(self, table, mask=None, status=None, sync: bool = True):
+        """``retune_random_agents`` for the members' table ``set_agents_per_book`` installed (``bk_retune_agents`` /
+        ``bk_retune_agents_device``): the masked books' Noise / Momentum / RandomAgents members keep their order lists and
+        momentum state and take the new parameters.  A member's kind, ``n`` and ``agent_id_start`` must stay what was
+        installed.  ``table``: ``n_books`` member lists as ``set_agents_per_book`` takes them or a structured array of
+        ``AGENT_DESC_DTYPE`` (host), or a device object of the raw rows ``[n_books, n_members]`` (104 B each, e.g. an int32
+        ``[n_books, n_members, 26]`` tensor)."""
+        if self.assets > 1:
+            raise ValueError("markets take retune_market_agents")
+        self._retune(True, table, mask, status, sync, lambda t: _members_rows(t, self.n_books))
+
+    def retune_rejected(self) -> int:
+        """Units (books, or markets) the retunes of this env have refused so far (``bk_retune_rejected``); waits for the
+        env's stream."""
+        n = C.c_uint64(0)
+        check(self._L.bk_retune_rejected(self._h, C.byref(n)))
+        return int(n.value)
+
+    def _retune(self, members: bool, table, mask, status, sync, host_rows):
+        n_units = self.n_books // self.assets
+        itemsize = 104 if members else 28
+        dev_entry = self._L.bk_retune_agents_device if members else self._L.bk_retune_random_agents_device
+        host_entry = self._L.bk_retune_agents if members else self._L.bk_retune_random_agents
+
+        def is_dev(x):
+            return hasattr(x, "data_ptr") or hasattr(x, "__cuda_array_interface__")
+
+        def dev_bytes(x, name):
+            if hasattr(x, "data_ptr"):
+                if not x.is_cuda or not x.is_contiguous():
+                    raise ValueError(f"{name}: a contiguous CUDA tensor is needed")
+                return C.c_void_p(x.data_ptr()), int(x.numel()) * int(x.element_size())
+            cai = x.__cuda_array_interface__
+            if cai.get("strides"):
+                raise ValueError(f"{name}: a contiguous device array is needed")
+            return C.c_void_p(cai["data"][0]), int(np.prod(cai["shape"])) * np.dtype(cai["typestr"]).itemsize
+
+        for name, x in (("mask", mask), ("status", status)):
+            if x is not None and is_dev(x) != is_dev(table):
+                raise ValueError(f"table and {name} must both be host arrays or both be device arrays")
+        if is_dev(table):
+            ptr, nbytes = dev_bytes(table, "table")
+            if nbytes == 0 or nbytes % (n_units * itemsize):
+                raise ValueError(f"table: {n_units} x width rows of {itemsize} bytes are needed, got {nbytes} bytes")
+            width = nbytes // (n_units * itemsize)
+            m_ptr = s_ptr = None
+            if mask is not None:
+                m_ptr, mb = dev_bytes(mask, "mask")
+                if mb != n_units:
+                    raise ValueError(f"mask: {n_units} one-byte elements are needed (one per book, or per market)")
+            if status is not None:
+                s_ptr, sb = dev_bytes(status, "status")
+                if sb != n_units * 8:
+                    raise ValueError(f"status: {2 * n_units} four-byte elements are needed (two per book, or per market)")
+            check(dev_entry(self._h, width, ptr, m_ptr, s_ptr))
+        else:
+            arr = host_rows(table)
+            m = None
+            if mask is not None:
+                m = np.ascontiguousarray(np.asarray(mask))
+                if m.dtype != np.bool_ and m.dtype != np.uint8:
+                    raise ValueError("mask: a bool or uint8 array is needed")
+                m = m.astype(np.uint8, copy=False)
+                if m.shape != (n_units,):
+                    raise ValueError(f"mask: {n_units} elements are needed (one per book, or per market)")
+            if status is not None and (not isinstance(status, np.ndarray) or status.size != 2 * n_units):
+                raise ValueError(f"status: a numpy array of {2 * n_units} elements is needed")
+            check(host_entry(self._h, arr.shape[1], arr.ctypes.data_as(C.c_void_p),
+                             None if m is None else m.ctypes.data_as(C.c_void_p)))
+            if status is not None:
+                status[...] = 0  # (the host entry applies every masked unit or raises)
+        if sync:
+            self.sync()
 
     def set_market_agents(self, members):
         """A ``#[derive(MarketAgentSet)]`` struct: ``[(asset, member), ...]`` with members as in ``set_agents`` — the
@@ -1564,6 +1655,22 @@ class ManyMarketEnv(ManyBookEnv):
             raise ValueError("the members' assets must be the same in every market")
         self._set_members_table([[m for _, m in r] for r in rows], self.n_markets, assets)
 
+    def retune_random_market_agents(self, rows, mask=None, status=None, sync: bool = True):
+        """``retune_random_agents`` per market, for the table ``set_random_market_agents_per_market`` installed: ``rows[m]``
+        as that call takes it (the groups' assets stay what was installed) or a device object of the raw rows
+        ``[n_markets, n_groups]``; ``mask`` / ``status`` hold one element / pair per market."""
+        if not (hasattr(rows, "data_ptr") or hasattr(rows, "__cuda_array_interface__") or isinstance(rows, np.ndarray)):
+            rows = [[(g.as_tuple() if isinstance(g, RandomMarketAgents) else tuple(g))[1:] for g in row] for row in rows]
+        self._retune(False, rows, mask, status, sync, lambda t: _agents_table(t, self.n_markets, lambda g: g))
+
+    def retune_market_agents(self, rows, mask=None, status=None, sync: bool = True):
+        """``retune_agents`` per market, for the table ``set_market_agents_per_market`` installed: ``rows[m]`` is market
+        ``m``'s ``[(asset, member), ...]`` list (the members' assets stay what was installed) or a device object of the raw
+        rows ``[n_markets, n_members]``."""
+        if not (hasattr(rows, "data_ptr") or hasattr(rows, "__cuda_array_interface__") or isinstance(rows, np.ndarray)):
+            rows = [[m for _, m in r] for r in rows]
+        self._retune(True, rows, mask, status, sync, lambda t: _members_rows(t, self.n_markets))
+
     # Market::save_json / load_json (market.rs:367-390): {"order_books": [OrderBook; ASSETS]}
     def market_state(self, market: int, trading: bool = True) -> dict:
         return {"order_books": [self.book_state(self.book(market, a), trading) for a in range(self.assets)]}
@@ -1613,6 +1720,34 @@ def _fill_agent_desc(d, m: tuple):
         else:
             d.decay, d.demand = float(p["decay"]), float(p["demand"])
             d.scale, d.order_ratio = float(p["scale"]), float(p["order_ratio"])
+
+
+def _members_array(rows, n_units: int):
+    """The flat AgentDesc array (unit-major) of ``n_units`` equally long rows of member tuples."""
+    n = len(rows[0])
+    arr = (AgentDesc * (n_units * n))()
+    for u, row in enumerate(rows):
+        for i, m in enumerate(row):
+            _fill_agent_desc(arr[u * n + i], m)
+    return arr
+
+
+def _members_rows(table, n_units: int) -> np.ndarray:
+    """A contiguous (n_units, n_members) AGENT_DESC_DTYPE array from a structured array or per-unit member lists in
+    ``set_agents``' format; the shape is checked here (ValueError) before the library sees it."""
+    if isinstance(table, np.ndarray) and table.dtype.names is not None:
+        if table.ndim != 2 or table.shape[0] != n_units or table.shape[1] == 0:
+            raise ValueError(f"the table must be (n_units = {n_units}, n_members >= 1), got {table.shape}")
+        if table.dtype != _lib.AGENT_DESC_DTYPE:
+            table = table.astype(_lib.AGENT_DESC_DTYPE)
+        return np.ascontiguousarray(table)
+    rows = [[_member_tuple(m) for m in row] for row in table]
+    if len(rows) != n_units:
+        raise ValueError(f"the table needs one row of members per unit: {n_units} rows, got {len(rows)}")
+    n = len(rows[0]) if rows else 0
+    if n == 0 or any(len(r) != n for r in rows):
+        raise ValueError("every row of the table needs the same number (>= 1) of members")
+    return np.frombuffer(_members_array(rows, n_units), dtype=_lib.AGENT_DESC_DTYPE).reshape(n_units, n).copy()
 
 
 def _agents_table(table, n_units: int, as_tuple) -> np.ndarray:

@@ -357,6 +357,50 @@ int bk_set_market_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* m
  * bk_set_random_agents_per_book's.  On a failure the installed agents stay.  Replaces the installed agent set; a later
  * bk_set_agents / bk_set_random_agents / bk_set_random_agents_per_book replaces (and frees) the table. */
 int bk_set_agents_per_book(bk_env* env, uint32_t n_members, const bk_agent_desc* members, const uint32_t* assets);
+/* RETUNE: replace, for the units a mask names, the parameter records of the installed per-unit table, in place on the
+ * device (a unit is a book, or a market when assets > 1).  In the reference's terms the fields of unit u's agent objects
+ * are assigned between two `update` calls: the next bk_run, bk_warm, bk_update_agents, bk_update_members or
+ * bk_update_market_* queued behind the call steps unit u as the reference would.  NOTHING ELSE CHANGES: the books and
+ * the RNG states, the RandomAgents' fixed slots and held ids, the members' order lists, lengths and momentum state
+ * (last_price, momentum), the "re-make at the next update" marks of an install, the count of installs and the agent-set
+ * hash of checkpoints and snapshot slots all stay.
+ *   - Needs an installed per-unit table of the same kind and width: bk_set_random_agents_per_book with the same n_groups
+ *     for the RandomAgents entries, bk_set_agents_per_book with the same n_members for the members' (an all-RandomAgents
+ *     members table is bk_set_random_agents_per_book's, and so is its retune).  A uniform install is refused with
+ *     BK_INVALID_ARGUMENT: install a per-unit table of identical rows, which costs nothing.
+ *   - rows[u * width + j] is entry j of unit u, in the install's own structs; rows of unmasked units are not read.
+ *     mask: one byte per unit, NULL = every unit.
+ *   - Every entry is checked as the install checks one, with the install's status codes (ranges, tick_lo != 0, the price
+ *     bound, tick_size a multiple of the asset's tick, finite mu, sigma >= 0).  In addition n_agents - and a member's type
+ *     and agent_id_start - must equal the installed values (BK_INVALID_ARGUMENT).  The asset and a RandomAgents member's
+ *     first fixed slot are no inputs: they stay what the install wrote.
+ *   - All or nothing per unit: a unit with any failing entry keeps its whole row.
+ *   - Never silent: status_dev (optional; 2 u32 per unit, as bk_submit_instructions_device's) receives {bk_status, index
+ *     of the first failing group / member}, {BK_OK, 0} for an applied or an unmasked unit; and the env counts the refused
+ *     units on the device: bk_retune_rejected waits for the env's stream and reads the count, cumulative over the env's life.
+ *   - The _device entries are ONE kernel on the env's stream, ordered like bk_reset_books_device: no host synchronisation
+ *     and, after the env's first retune (which makes the counter), no allocation.  rows_dev must be 4-byte
+ *     (bk_random_agents) / 8-byte (bk_agent_desc) aligned.
+ *   - The host entries check the masked units on the host first, with the installs' row builder: on the first failure
+ *     nothing at all changes, the status is the install's and bk_last_error() names the unit and the group or member.
+ *     Otherwise the rows go through pinned and device staging of the env's own (made at the first call) into the same
+ *     kernel; the caller's arrays are free on return.
+ *   - Checkpoints and snapshot slots hold no parameters and are not invalidated: a reset or a restore brings no
+ *     parameters back (who restores retunes again for the old values), and one taken before a retune is usable after it
+ *     and the other way round - the agent-set hash goes on naming the install, whose shape a retune cannot change.
+ *     Conversely a checkpoint taken AFTER a retune restores only into an env that repeats the original install (the hash
+ *     covers the installed records, thresholds and ranges included), and that env then runs the installed parameters: who
+ *     wants to resume with the retuned ones retunes again after bk_checkpoint_load.
+ * Refusals (BK_INVALID_ARGUMENT, the env unchanged): null env or rows, no matching per-unit table, a width mismatch, a
+ * misaligned device pointer.  Envs with the agents' order log, device-ingress envs, markets and envs with snapshots held
+ * all take it.  No counterpart in the reference beyond the assignment itself. */
+int bk_retune_random_agents_device(bk_env* env, uint32_t n_groups, const bk_random_agents* rows_dev, const uint8_t* mask_dev,
+                                   uint32_t* status_dev);
+int bk_retune_random_agents(bk_env* env, uint32_t n_groups, const bk_random_agents* rows, const uint8_t* mask);
+int bk_retune_agents_device(bk_env* env, uint32_t n_members, const bk_agent_desc* rows_dev, const uint8_t* mask_dev,
+                            uint32_t* status_dev);
+int bk_retune_agents(bk_env* env, uint32_t n_members, const bk_agent_desc* rows, const uint8_t* mask);
+int bk_retune_rejected(bk_env* env, uint64_t* out);
 /* sim_runner's loop body n_steps times for every book: agents.update(env, rng); env.step(rng)
  * (crates/step_sim/src/runner.rs:53-68), sharing each book's RNG between agents and shuffle. */
 int bk_run(bk_env* env, uint64_t n_steps);

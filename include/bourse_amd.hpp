@@ -197,6 +197,34 @@ class ManyEnv {
     }
     check(bk_set_agents_per_book(h_, static_cast<uint32_t>(n_members), flat.data(), nullptr));
   }
+  // retune: the parameters of the books mask[b] != 0 names (empty mask: every book) in the installed per-book table, in
+  // place - the agents keep what they hold, nothing else changes (bk_retune_random_agents / bk_retune_agents).  rows is
+  // flat, book-major: rows[b * width + j]; on the first bad entry of a masked book nothing changes and Error is thrown.
+  void retune_random_agents(uint32_t n_groups, const std::vector<bk_random_agents>& rows, const std::vector<uint8_t>& mask = {}) {
+    if (rows.size() != static_cast<size_t>(n_books_) * n_groups || (!mask.empty() && mask.size() != n_books_))
+      throw Error(BK_INVALID_ARGUMENT, "retune: n_books x n_groups rows and one mask byte per book are needed");
+    check(bk_retune_random_agents(h_, n_groups, rows.data(), mask.empty() ? nullptr : mask.data()));
+  }
+  void retune_agents(uint32_t n_members, const std::vector<bk_agent_desc>& rows, const std::vector<uint8_t>& mask = {}) {
+    if (rows.size() != static_cast<size_t>(n_books_) * n_members || (!mask.empty() && mask.size() != n_books_))
+      throw Error(BK_INVALID_ARGUMENT, "retune: n_books x n_members rows and one mask byte per book are needed");
+    check(bk_retune_agents(h_, n_members, rows.data(), mask.empty() ? nullptr : mask.data()));
+  }
+  // ... from device memory, one kernel on the env's stream with no host synchronisation (bk_retune_*_device): a book with
+  // a bad entry keeps its row, status_dev (nullable, 2 u32 per book) and retune_rejected() say so
+  void retune_random_agents_device(uint32_t n_groups, const bk_random_agents* rows_dev, const uint8_t* mask_dev = nullptr,
+                                   uint32_t* status_dev = nullptr) {
+    check(bk_retune_random_agents_device(h_, n_groups, rows_dev, mask_dev, status_dev));
+  }
+  void retune_agents_device(uint32_t n_members, const bk_agent_desc* rows_dev, const uint8_t* mask_dev = nullptr,
+                            uint32_t* status_dev = nullptr) {
+    check(bk_retune_agents_device(h_, n_members, rows_dev, mask_dev, status_dev));
+  }
+  uint64_t retune_rejected() {
+    uint64_t n = 0;
+    check(bk_retune_rejected(h_, &n));
+    return n;
+  }
   // agents.update(env, rng) of the RandomAgents into the device-resident queues (bk_update_agents; the env has the device
   // ingress, bk_device_ingress_enable(handle(), ..), then the agents): the next step() trades them with the submitted
   // instructions.  Asynchronous on the env's stream.
