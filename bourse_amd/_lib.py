@@ -309,6 +309,7 @@ SIGNATURES = {
     "bk_pipeline_fallbacks": (_i32, [_vp, _p64]),
     "bk_order_counts": (_i32, [_vp, _p64]),
     "bk_event_steps_keyed": (_i32, [_vp, _p64]),
+    "bk_stamp_compactions": (_i32, [_vp, _p64]),
     "bk_checkpoint_bytes": (_u64, [_vp]),
     "bk_checkpoint_save": (_i32, [_vp, _vp, _u64]),
     "bk_checkpoint_load": (_i32, [_vp, _vp, _u64]),

@@ -58,6 +58,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "open_queue.hpp"
 #include "quotes_ingress.hpp"
 #include "retune.hpp"
+#include "stamp_compact.hpp"
 
 using namespace bkd;
 
@@ -163,6 +164,7 @@ struct bk_env {
     DevBuf<uint32_t> buf;
     bool used = false;
     uint64_t shape[4] = {0, 0, 0, 0};  // ckpt_header h[2..5]
+    uint64_t stamp_bound = 0;          // the env's stamp_room.bound as it was saved
   } snaps[BK_MAX_SNAPSHOTS];
   DevBuf<uint8_t> reset_mask;    // bk_reset_books: device staging of the host mask / seeds [n_units]
   DevBuf<uint64_t> reset_seeds;
@@ -180,6 +182,7 @@ struct bk_env {
     uint64_t shape[4] = {0, 0, 0, 0};  // ckpt_header h[2..5]
     uint64_t installs = 0;
     uint64_t bytes = 0;
+    uint64_t stamp_bound = 0;  // the env's stamp_room.bound as it was saved
   } isnaps[BK_MAX_SNAPSHOTS];
   DevBuf<uint32_t> reset_list;  // [n_units] the masked units of one ingress reset, then its counter (k_collect_units)
   int reset_blocks = 0;         // k_reset_records' fixed grid: 4 blocks of 4 waves per CU
@@ -359,6 +362,11 @@ struct bk_env {
   uint32_t* mods_flag_dev = nullptr;
   bool device_flow = false;   // bk_run has stepped this env with on-device agents: host-driven orders are refused
   uint64_t steps_done = 0, hist_base = 0;
+  // the books' arrival stamps (H_SEQ, pool field 3) never straddle a wrap: the host's upper bound of the largest H_SEQ,
+  // raised before every launch by the most orders one book can rest in it, and the compaction queued in front of a launch
+  // that could pass the limit (stamp_rows.hpp; reserve_stamps)
+  bkd::stamps::Room stamp_room;
+  uint64_t stamp_compactions = 0;  // launches of the compaction so far (bk_stamp_compactions)
   uint32_t trading = 1;
   size_t ev_capacity = 0;
   // profiling
@@ -490,6 +498,29 @@ auto by_R(int R, F&& f) {
     case 4: return f(std::integral_constant<int, 4>{});
     default: return f(std::integral_constant<int, 8>{});
   }
+}
+
+// stamps::k_compact over every book, on the env's stream: every live stamp becomes its rank, H_SEQ the live count
+int compact_stamps(bk_env* env) {
+  const uint32_t B = env->cfg.n_books;
+  const dim3 grid((B + bkd::stamps::COMPACT_WAVES - 1) / bkd::stamps::COMPACT_WAVES), block(64 * bkd::stamps::COMPACT_WAVES);
+  by_R(env->R, [&](auto r) {
+    hipLaunchKernelGGL(bkd::stamps::k_compact<decltype(r)::value>, grid, block, 0, env->stream, env->state.p, env->stride, B);
+  });
+  HIPCHK(hipGetLastError());
+  env->stamp_room.compacted(static_cast<uint32_t>(env->R) * 64u);
+  env->stamp_compactions += 1;
+  return BK_OK;
+}
+
+// Before a launch in which one book can rest up to `rests` orders: queues the stamp compaction on the env's stream (for
+// the multi-part pipelines that is in front of the fork) when the launch could take a book's H_SEQ past the limit.
+int reserve_stamps(bk_env* env, uint64_t rests) {
+  if (rests == 0) return BK_OK;
+  if (env->stamp_room.needs_compaction(rests))
+    if (int rc = compact_stamps(env)) return rc;
+  env->stamp_room.spend(rests);
+  return BK_OK;
 }
 
 int wave_args(bk_env* env, WaveArgs* wva);
@@ -1045,6 +1076,15 @@ int bk_env_create(const bk_config* cfg, bk_env** out) {
     const int v = std::atoi(mp);
     if (v >= 64) env->min_part = static_cast<uint32_t>(v);
   }
+  // diagnostic knobs of the stamps: the value every fresh book's H_SEQ starts at, and the room a compaction leaves (so
+  // that tests reach the wrap, and the compaction, within a few steps)
+  uint32_t seq_start = 0;
+  if (const char* ss = std::getenv("BOURSE_AMD_SEQ_START")) seq_start = static_cast<uint32_t>(std::strtoull(ss, nullptr, 0));
+  if (const char* sr = std::getenv("BOURSE_AMD_STAMP_ROOM")) {
+    const unsigned long long v = std::strtoull(sr, nullptr, 0);
+    if (v >= 1) env->stamp_room.limit = std::min<uint64_t>(env->stamp_room.limit, static_cast<uint64_t>(R) * 64u + v);
+  }
+  env->stamp_room.bound = seq_start;
   HIPCHK(env->ev_off.alloc(B + 1));
   HIPCHK(hipMemset(env->ev_off.p, 0, (B + 1) * sizeof(uint32_t)));
 
@@ -1061,6 +1101,7 @@ int bk_env_create(const bk_config* cfg, bk_env** out) {
     h[H_S1_LO] = static_cast<uint32_t>(s1);
     h[H_S1_HI] = static_cast<uint32_t>(s1 >> 32);
     h[H_TRADING] = env->trading;
+    h[H_SEQ] = seq_start;
     uint32_t* l = l2.data() + b * env->W;
     l[1] = 0u;           // bid touch of an empty side (side.rs:194-196)
     l[2] = 0xFFFFFFFFu;  // ask touch of an empty side (side.rs:99-104)
@@ -1320,6 +1361,7 @@ int bk_step(bk_env* env) {
   HIPCHK(hipMemcpyAsync(env->ev_off.p, env->off_stage, (NM + 1) * 4, hipMemcpyHostToDevice, env->stream));
   if (total)
     HIPCHK(hipMemcpyAsync(env->ev.p, env->ev_stage, total * sizeof(HostEvent), hipMemcpyHostToDevice, env->stream));
+  if (int rc = reserve_stamps(env, max_queue)) return rc;  // (a New or a re-keying modification takes one stamp)
   const DevArgs a = env->args();
   const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, max_queue); });
   if (rc != BK_OK) return rc;
@@ -1779,6 +1821,7 @@ int bk_step_async(bk_env* env) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->device_ingress) return fail(BK_INVALID_ARGUMENT, "bk_step_async steps the device-resident queues: call bk_device_ingress_enable first");
   if (int rc = use_device(env)) return rc;
+  if (int rc = reserve_stamps(env, env->qcap)) return rc;  // (the queues' lengths are known on the device only)
   const DevArgs a = env->args();
   // (the shuffle permutation's LDS is sized for a full queue: the host does not know the queues' lengths - nothing of this
   // step has been on the host)
@@ -2453,6 +2496,25 @@ int bk_run(bk_env* env, uint64_t n_steps) {
   for (const BookHost& bh : env->books)
     if (!bh.queue.empty() || !bh.orders.empty())
       return fail(BK_INVALID_ARGUMENT, "bk_run cannot be mixed with host-driven orders on the same env");
+  {  // stamps: every agent places at most one order per step.  A run longer than the room holds goes in pieces.
+    uint64_t per_step = env->n_agents_total;
+    if (env->n_mixed) {
+      per_step = 0;
+      for (uint32_t n : env->member_n) per_step += n;
+    }
+    if (per_step && env->stamp_room.needs_compaction(n_steps * per_step)) {
+      const uint64_t most = std::max<uint64_t>(1, env->stamp_room.after_compaction(static_cast<uint32_t>(env->R) * 64u) / per_step);
+      if (n_steps > most) {
+        for (uint64_t left = n_steps; left;) {
+          const uint64_t c = std::min(left, most);
+          if (int rc = bk_run(env, c)) return rc;
+          left -= c;
+        }
+        return BK_OK;
+      }
+    }
+    if (int rc = reserve_stamps(env, n_steps * per_step)) return rc;
+  }
   DevArgs a = env->args();
   if (a.n_groups == 0) {  // no agents: plain steps
     a.groups[0] = Group{};
@@ -2525,11 +2587,13 @@ int bk_warm(bk_env* env, uint64_t n_steps) {
   HIPCHK(hipMemcpyAsync(env->warm_snap.p + sb, env->l2_last.p, lb * 4, hipMemcpyDeviceToDevice, env->stream));
   const uint64_t steps0 = env->steps_done;
   const bool flow0 = env->device_flow;
+  const uint64_t stamps0 = env->stamp_room.bound;  // (the books come back as they are now, their H_SEQ with them)
   env->warming = true;
   const int rc = bk_run(env, n_steps);
   env->warming = false;
   env->steps_done = steps0;
   env->device_flow = flow0;
+  env->stamp_room.bound = stamps0;
   env->wl_valid = false;  // the wave-per-book lists described the scratch steps' pools
   env->ml_valid = false;  // the members' lists described the scratch steps' pool
   // put the books back WHATEVER bk_run returned: a launch that failed half-way (an event record / wait between two kernel
@@ -2892,6 +2956,7 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   hdr[H_T_HI] = static_cast<uint32_t>(t >> 32);
   hdr[H_NEXT_ID] = static_cast<uint32_t>(n_orders);
   hdr[H_SEQ] = static_cast<uint32_t>(act.size());
+  env->stamp_room.raise(act.size());
   hdr[H_TRADES_LO] = static_cast<uint32_t>(n_trades);
   hdr[H_TRADES_HI] = static_cast<uint32_t>(n_trades >> 32);
   hdr[H_TRADE_BASE_LO] = hdr[H_TRADE_BASE_HI] = 0;
@@ -3255,6 +3320,12 @@ int bk_event_steps_keyed(bk_env* env, uint64_t* counts) {
   return gather_header(env, H_EV_KEYED, 1, counts);
 }
 
+int bk_stamp_compactions(bk_env* env, uint64_t* out) {
+  if (!env || !out) return fail(BK_INVALID_ARGUMENT, env ? "null argument" : "null env");
+  *out = env->stamp_compactions;
+  return BK_OK;
+}
+
 // ---------------------------------------------------------------- checkpoint / resume (on-device order flow)
 // The reference cannot resume a running simulation (Env, agents and RNG are not serialisable);
 // here the whole simulation state IS the per-book device block (pool, clock, counters, RNG), so a checkpoint
@@ -3331,6 +3402,8 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
   hipLaunchKernelGGL(k_book_service, dim3((B + 255) / 256), dim3(256), 0, env->stream, env->state.p, env->stride, B, 0,
                      0u);
   HIPCHK(hipGetLastError());
+  // the image's stamps are whatever its env had reached: compacted here, the bound starts again at the pool size
+  if (int rc = compact_stamps(env)) return rc;
   if (env->series) {  // series moments are no part of a checkpoint: every row starts again at the restored step
     launch_series_clear(env, nullptr, 1, false);
     HIPCHK(hipGetLastError());
@@ -3380,6 +3453,7 @@ int bk_snapshot_save(bk_env* env, uint32_t slot) {
   uint64_t h[CKPT_HDR];
   ckpt_header(env, h);
   for (int i = 0; i < 4; ++i) s.shape[i] = h[2 + i];
+  s.stamp_bound = env->stamp_room.bound;
   s.used = true;
   return BK_OK;
 }
@@ -3465,6 +3539,7 @@ int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, c
   }
   launch_reset_books(env, env->snaps[slot].buf.p, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
+  env->stamp_room.raise(env->snaps[slot].stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
   // which books changed is known on the device only: the members' lists of every book are rebuilt from the owner tags
   env->ml_valid = false;
   env->wl_valid = false;
@@ -3598,6 +3673,7 @@ int bk_ingress_snapshot_save(bk_env* env, uint32_t slot) {
   ckpt_header(env, h);
   for (int i = 0; i < 4; ++i) s.shape[i] = h[2 + i];
   s.installs = env->agent_installs;
+  s.stamp_bound = env->stamp_room.bound;
   s.used = true;
   return BK_OK;
 }
@@ -3649,6 +3725,7 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
   }
   launch_reset_books(env, s.buf.p, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
+  env->stamp_room.raise(s.stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
   uint32_t* counter = env->reset_list.p + n_units;
   HIPCHK(hipMemsetAsync(counter, 0, 4, env->stream));
   // (after a bk_set_*agents* call and before the next update the env's own rows are stale and are re-made by that update;

@@ -914,6 +914,12 @@ class ManyBookEnv:
         check(self._L.bk_event_steps_keyed(self._h, _lib.p64(out)))
         return out
 
+    def stamp_compactions(self) -> int:
+        """How many times this env has queued the stamp compaction (a diagnostic; ``bk_stamp_compactions``)."""
+        out = C.c_uint64(0)
+        check(self._L.bk_stamp_compactions(self._h, C.byref(out)))
+        return int(out.value)
+
     def time(self, book: int = 0) -> int:
         out = C.c_uint64(0)
         check(self._L.bk_time(self._h, book, C.byref(out)))

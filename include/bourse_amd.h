@@ -529,6 +529,11 @@ int bk_order_counts(bk_env* env, uint64_t* totals /* [n_books] */);
  * modifications whose events fit one per pool slot, on a trading book, with prices and arrival stamps inside the key window
  * (bourse_amd/csrc/step_events.hpp step_events_keyed); the others ran the event-by-event loop.  Results never depend on it. */
 int bk_event_steps_keyed(bk_env* env, uint64_t* counts /* [n_books] */);
+/* A diagnostic of the stamp compaction (bourse_amd/csrc/stamp_rows.hpp): how many times this env has queued
+ * it so far - in front of a launch that could have taken a book's arrival-stamp counter past 2^32 - 1 (or past the room
+ * BOURSE_AMD_STAMP_ROOM leaves), and once per bk_checkpoint_load.  Results never depend on it.  (No counterpart in the
+ * reference.) */
+int bk_stamp_compactions(bk_env* env, uint64_t* out);
 
 /* ------------------------------------------------------ checkpoint / resume */
 /* Dump / restore the complete simulation state of an on-device-order-flow env (pool, clock, counters, per-book
