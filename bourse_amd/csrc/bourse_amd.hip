@@ -139,6 +139,53 @@ struct DevBuf {
     if (count == 0) return hipSuccess;
     return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
   }
+  // Replace this buffer by a freshly made one: `other` leaves with the previous block and frees it at its scope's exit.
+  void swap(DevBuf& other) {
+    std::swap(p, other.p);
+    std::swap(n, other.n);
+  }
+};
+
+// A host table on its way to a kernel of the env's stream: caller -> pinned block (before the call returns) -> device block
+// (on the stream).  `copied` is recorded behind every upload: once it has passed, the pinned block may be written again.
+struct HostStage {
+  DevBuf<unsigned char> dev;
+  unsigned char* pin = nullptr;
+  size_t bytes = 0;  // of either block
+  hipEvent_t copied = nullptr;
+  ~HostStage() {
+    if (pin) (void)hipHostFree(pin);
+    if (copied) (void)hipEventDestroy(copied);
+  }
+  // Room for n bytes in both blocks, the pinned one free to write.  Blocks that are too small are replaced (they only grow);
+  // `drain`: an earlier call's kernel on `stream` may still read the device block replaced here, so wait for the stream.
+  int reserve(size_t n, hipStream_t stream, bool drain) {
+    if (n <= bytes) {
+      HIPCHK(hipEventSynchronize(copied));  // the call before this one has been uploaded: the pinned rows are free
+      return BK_OK;
+    }
+    if (copied) HIPCHK(hipEventSynchronize(copied));
+    if (drain) HIPCHK(hipStreamSynchronize(stream));
+    DevBuf<unsigned char> fresh;
+    HIPCHK(fresh.alloc(n));
+    void* fresh_pin = nullptr;
+    HIPCHK(hipHostMalloc(&fresh_pin, n, hipHostMallocDefault));
+    if (!copied && hipEventCreateWithFlags(&copied, hipEventDisableTiming) != hipSuccess) {
+      (void)hipHostFree(fresh_pin);
+      return fail(BK_HIP_ERROR, "hipEventCreateWithFlags failed");
+    }
+    if (pin) (void)hipHostFree(pin);
+    pin = static_cast<unsigned char*>(fresh_pin);
+    bytes = n;
+    dev.swap(fresh);
+    return BK_OK;
+  }
+  // the first n bytes of the pinned block -> the device block, on `stream`
+  int upload(size_t n, hipStream_t stream) {
+    HIPCHK(hipMemcpyAsync(dev.p, pin, n, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(copied, stream));
+    return BK_OK;
+  }
 };
 
 }  // namespace
@@ -209,20 +256,14 @@ struct bk_env {
   uint32_t open_traders = 0, open_depth = 0;  // open_traders == 0: no view
   // bk_open_queue_enable: the queue position of every entry above, recomputed right behind them (open_queue.hpp)
   DevBuf<bk_u32x4> open_queue;  // [n_books][open_traders][open_depth][2]; empty: no queue view
-  // bk_submit_quotes: the host table goes caller -> pinned staging (before the call returns) -> device staging (on the
-  // env's stream); [n_books][open_traders] rows each, made at the first call; quote_copied: the last upload has left the pinned rows
-  DevBuf<bk_u32x4> quote_stage;
-  bk_quote* quote_pin = nullptr;
-  hipEvent_t quote_copied = nullptr;
+  // bk_submit_quotes: the host table's staging, [n_books][open_traders] rows, made at the first call
+  HostStage quote_stage;
   // bk_retune_*: the count of refused units (device), the members' installed first trader ids as the kernel compares them
-  // (uploaded by the per-unit install, synchronously like its table), and the host forms' staging: caller -> pinned (before the call
-  // returns) -> device (on the env's stream), rows then mask, made at the first call and grown only by a wider table
+  // (uploaded by the per-unit install, synchronously like its table), and the host forms' staging: rows then mask, made at the
+  // first call and grown only by a wider table
   DevBuf<unsigned long long> retune_count;
   DevBuf<uint32_t> retune_id0;  // [units][n_mixed], uploaded by bk_set_agents_per_book beside the table
-  DevBuf<unsigned char> retune_stage;
-  unsigned char* retune_pin = nullptr;
-  size_t retune_pin_bytes = 0;
-  hipEvent_t retune_copied = nullptr;
+  HostStage retune_stage;
   uint64_t agent_installs = 0;  // bk_set_*agents* calls: each marks the held ids / the members' lists stale
   DevBuf<uint4> jump_tabs;      // k_agents_wave: T^256 (block jump) then T^(4 << b), b = 0..5 (lane offsets): 7 x 8 KB
   DevBuf<uint32_t> wcache;      // k_agents_wave: per-book lane states of the RNG block in progress
@@ -498,6 +539,12 @@ auto by_R(int R, F&& f) {
     case 4: return f(std::integral_constant<int, 4>{});
     default: return f(std::integral_constant<int, 8>{});
   }
+}
+
+// A table kernel that gives every book one wave, `waves` of them per block, on the env's stream (g: its argument struct)
+template <typename K, typename A>
+void launch_wave_per_book(bk_env* env, K kernel, uint32_t waves, const A& g) {
+  hipLaunchKernelGGL(kernel, dim3((g.n_books + waves - 1) / waves), dim3(64 * waves), 0, env->stream, g);
 }
 
 // stamps::k_compact over every book, on the env's stream: every live stamp becomes its rank, H_SEQ the live count
@@ -908,6 +955,33 @@ int check_book(bk_env* env, uint32_t book) {
   return BK_OK;
 }
 
+// books [first_book, first_book + n_books) of the readers: all of them exist (an empty range may start behind the last)
+int book_range_ok(const bk_env* env, uint32_t first_book, uint32_t n_books) {
+  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
+    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  return BK_OK;
+}
+
+// The rows of a book range of an enabled per-book table -> host, behind the table's own check: range, null, device, a wait
+// for the env's stream, then one copy per table (`book_bytes` each book; only the first `out` is required, a null or
+// empty one behind it is left out).
+struct BookRows {
+  const void* table;
+  size_t book_bytes;
+  void* out;
+};
+int get_book_rows(bk_env* env, uint32_t first_book, uint32_t n_books, std::initializer_list<BookRows> tables) {
+  if (int rc = book_range_ok(env, first_book, n_books)) return rc;
+  if (n_books && !tables.begin()->out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  for (const BookRows& t : tables)
+    if (n_books && t.out && t.book_bytes)
+      HIPCHK(hipMemcpy(t.out, static_cast<const char*>(t.table) + first_book * t.book_bytes, n_books * t.book_bytes,
+                       hipMemcpyDeviceToHost));
+  return BK_OK;
+}
+
 int refresh_log(bk_env* env, uint32_t book) {
   BookHost& bh = env->books[book];
   if (bh.log_fresh) return BK_OK;
@@ -1127,10 +1201,6 @@ void bk_env_destroy(bk_env* env) {
   if (env->hi.in) (void)hipStreamSynchronize(env->hi.in);
   if (env->hi.out) (void)hipStreamSynchronize(env->hi.out);
   if (env->mods_flag_host) (void)hipHostFree(env->mods_flag_host);
-  if (env->quote_pin) (void)hipHostFree(env->quote_pin);
-  if (env->retune_pin) (void)hipHostFree(env->retune_pin);
-  if (env->retune_copied) (void)hipEventDestroy(env->retune_copied);
-  if (env->quote_copied) (void)hipEventDestroy(env->quote_copied);
   for (auto& r : env->hi.retired) (void)hipHostFree(r.pin);
   env->hi.retired.clear();
   for (int i = 0; i < bk_env::HostIngress::SLOTS; ++i) {
@@ -1717,8 +1787,7 @@ static void launch_accounts_fold(bk_env* env) {
   g.seen = env->acct_seen.p;
   // (the last fold of a step consumes for both: the bars' fold runs in front of this one and leaves the records alone)
   g.consume = env->acct_consume || env->bars_consume ? 1u : 0u;
-  const uint32_t blocks = (g.n_books + accounts::FOLD_WAVES - 1) / accounts::FOLD_WAVES;
-  hipLaunchKernelGGL(accounts::k_fold, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, accounts::k_fold, accounts::FOLD_WAVES, g);
 }
 
 // the step the env's counter reads k -> slot k % window of every book; in front of the accounts' fold, which then consumes
@@ -1735,8 +1804,7 @@ static void launch_bars_fold(bk_env* env) {
   g.prev_slot = (g.slot + env->bars_window - 1u) % env->bars_window;
   g.seen = env->bars_seen.p;
   g.consume = !env->acct_traders && env->bars_consume ? 1u : 0u;
-  const uint32_t blocks = (g.n_books + trade_bars::FOLD_WAVES - 1) / trade_bars::FOLD_WAVES;
-  hipLaunchKernelGGL(trade_bars::k_fold, dim3(blocks), dim3(64 * trade_bars::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, trade_bars::k_fold, trade_bars::FOLD_WAVES, g);
 }
 
 // rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
@@ -1750,8 +1818,7 @@ static void launch_bars_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M) 
   g.bars = env->bars.p;
   g.window = env->bars_window;
   g.seen = env->bars_seen.p;
-  const uint32_t blocks = (g.n_books + trade_bars::FOLD_WAVES - 1) / trade_bars::FOLD_WAVES;
-  hipLaunchKernelGGL(trade_bars::k_clear, dim3(blocks), dim3(64 * trade_bars::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, trade_bars::k_clear, trade_bars::FOLD_WAVES, g);
 }
 
 // rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
@@ -1765,8 +1832,7 @@ static void launch_accounts_clear(bk_env* env, const uint8_t* mask_dev, uint32_t
   g.acct = env->acct.p;
   g.n_traders = env->acct_traders;
   g.seen = env->acct_seen.p;
-  const uint32_t blocks = (g.n_books + accounts::FOLD_WAVES - 1) / accounts::FOLD_WAVES;
-  hipLaunchKernelGGL(accounts::k_clear, dim3(blocks), dim3(64 * accounts::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, accounts::k_clear, accounts::FOLD_WAVES, g);
 }
 
 // the open-order rows of the masked books (one mask byte per M books; nullptr: every book) from their pools as they are at
@@ -1785,11 +1851,7 @@ static void launch_open_orders_refresh(bk_env* env, const uint8_t* mask_dev, uin
   g.n_traders = env->open_traders;
   g.depth = env->open_depth;
   g.depth_inv = g.depth ? ((1u << 24) + g.depth - 1u) / g.depth : 0u;
-  const uint32_t blocks = (g.n_books + open_orders::REFRESH_WAVES - 1) / open_orders::REFRESH_WAVES;
-  by_R(env->R, [&](auto r) {
-    hipLaunchKernelGGL(open_orders::k_refresh<decltype(r)::value>, dim3(blocks), dim3(64 * open_orders::REFRESH_WAVES), 0,
-                       env->stream, g);
-  });
+  by_R(env->R, [&](auto r) { launch_wave_per_book(env, open_orders::k_refresh<decltype(r)::value>, open_orders::REFRESH_WAVES, g); });
 }
 
 // the queue rows of the masked books from their pools and the entries the open-order refresh in front of it wrote: one
@@ -1804,11 +1866,7 @@ static void launch_open_queue_refresh(bk_env* env, const uint8_t* mask_dev, uint
   g.entries = env->open_entries.p;
   g.queue = env->open_queue.p;
   g.n_entries = env->open_traders * env->open_depth;  // (<= 65536 * 64)
-  const uint32_t blocks = (g.n_books + open_queue::REFRESH_WAVES - 1) / open_queue::REFRESH_WAVES;
-  by_R(env->R, [&](auto r) {
-    hipLaunchKernelGGL(open_queue::k_refresh<decltype(r)::value>, dim3(blocks), dim3(64 * open_queue::REFRESH_WAVES), 0,
-                       env->stream, g);
-  });
+  by_R(env->R, [&](auto r) { launch_wave_per_book(env, open_queue::k_refresh<decltype(r)::value>, open_queue::REFRESH_WAVES, g); });
 }
 
 // both tables of the open-order view: the rows, then - for an env with the queue view - their queue positions
@@ -2138,8 +2196,7 @@ int bk_set_random_agents_per_book(bk_env* env, uint32_t n_groups, const bk_rando
   DevBuf<Group> d;
   HIPCHK(d.alloc(t.size()));
   HIPCHK(hipMemcpy(d.p, t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice));
-  std::swap(env->dtable.p, d.p);  // (the previous table, if any, is freed with `d`)
-  std::swap(env->dtable.n, d.n);
+  env->dtable.swap(d);  // (the previous table, if any, is freed with `d`)
   env->groups.assign(t.begin(), t.begin() + n_groups);
   env->table.swap(t);
   env->n_agents_total = static_cast<uint32_t>(total);
@@ -2250,8 +2307,7 @@ static int install_members(bk_env* env, const std::vector<MixedDesc>& ds, uint32
   env->table.clear();
   (void)env->dtable.alloc(0);
   env->n_agents_total = 0;
-  std::swap(env->dmtable.p, dt.p);  // (the previous table, if any, is freed with `dt`)
-  std::swap(env->dmtable.n, dt.n);
+  env->dmtable.swap(dt);  // (the previous table, if any, is freed with `dt`)
   env->mtable.swap(table);
   env->agents_hash = env->mtable.empty() ? mixed_hash(env->member_asset, ds.data(), ds.size(), n_members)
                                          : mixed_hash(env->member_asset, env->mtable.data(), env->mtable.size(), n_members);
@@ -2379,29 +2435,12 @@ static int retune_from_host(bk_env* env, bool members, uint32_t width, const voi
   const size_t n_units = env->cfg.n_books / env->M;
   const size_t rows_bytes = (n_units * width * row_bytes + 15u) & ~size_t(15);
   const size_t bytes = rows_bytes + n_units;
-  if (bytes > env->retune_pin_bytes) {
-    if (env->retune_copied) HIPCHK(hipEventSynchronize(env->retune_copied));
-    HIPCHK(hipStreamSynchronize(env->stream));  // (an earlier retune may still read the staging replaced here)
-    DevBuf<unsigned char> stage;
-    HIPCHK(stage.alloc(bytes));
-    void* pin = nullptr;
-    HIPCHK(hipHostMalloc(&pin, bytes, hipHostMallocDefault));
-    if (!env->retune_copied && hipEventCreateWithFlags(&env->retune_copied, hipEventDisableTiming) != hipSuccess) {
-      (void)hipHostFree(pin);
-      return fail(BK_HIP_ERROR, "hipEventCreateWithFlags failed");
-    }
-    if (env->retune_pin) (void)hipHostFree(env->retune_pin);
-    env->retune_pin = static_cast<unsigned char*>(pin);
-    env->retune_pin_bytes = bytes;
-    std::swap(env->retune_stage.p, stage.p), std::swap(env->retune_stage.n, stage.n);
-  } else {
-    HIPCHK(hipEventSynchronize(env->retune_copied));  // the call before this one has been uploaded: the pinned rows are free
-  }
-  std::memcpy(env->retune_pin, rows, n_units * width * row_bytes);  // the caller's table may be reused on return
-  if (mask) std::memcpy(env->retune_pin + rows_bytes, mask, n_units);
-  HIPCHK(hipMemcpyAsync(env->retune_stage.p, env->retune_pin, mask ? bytes : rows_bytes, hipMemcpyHostToDevice, env->stream));
-  HIPCHK(hipEventRecord(env->retune_copied, env->stream));
-  return launch_retune(env, members, width, env->retune_stage.p, mask ? env->retune_stage.p + rows_bytes : nullptr, nullptr);
+  HostStage& st = env->retune_stage;
+  if (int rc = st.reserve(bytes, env->stream, true)) return rc;  // (an earlier retune may still read the staging it replaces)
+  std::memcpy(st.pin, rows, n_units * width * row_bytes);  // the caller's table may be reused on return
+  if (mask) std::memcpy(st.pin + rows_bytes, mask, n_units);
+  if (int rc = st.upload(mask ? bytes : rows_bytes, env->stream)) return rc;
+  return launch_retune(env, members, width, st.dev.p, mask ? st.dev.p + rows_bytes : nullptr, nullptr);
 }
 
 // The masked units are checked on the host first, with the installs' row builders: on the first failure nothing changes.
@@ -2616,8 +2655,7 @@ uint32_t bk_l2_width(const bk_env* env) { return env ? env->W : 0; }
 
 int bk_level2(bk_env* env, uint32_t first_book, uint32_t n_books, uint32_t* out) {
   if (!env || !out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (static_cast<uint64_t>(first_book) + n_books > env->cfg.n_books)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (int rc = book_range_ok(env, first_book, n_books)) return rc;
   if (int rc = use_device(env)) return rc;
   HIPCHK(hipStreamSynchronize(env->stream));
   HIPCHK(hipMemcpy(out, env->l2_last.p + static_cast<size_t>(first_book) * env->W,
@@ -2647,8 +2685,7 @@ static int hist_copy(bk_env* env, uint64_t first_step, uint64_t n_steps, uint32_
   if (!env->cfg.history_capacity || first_step < hist_first(env) || first_step > env->steps_done ||
       n_steps > env->steps_done - first_step)
     return fail(BK_INVALID_ARGUMENT, "step range not retained (history is a ring of history_capacity steps)");
-  if (static_cast<uint64_t>(first_book) + n_books > env->cfg.n_books)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
+  if (int rc = book_range_ok(env, first_book, n_books)) return rc;
   if (int rc = use_device(env)) return rc;
   const size_t W = env->W, B = env->cfg.n_books, cap = env->cfg.history_capacity;
   const size_t row = static_cast<size_t>(n_books) * W * 4;
@@ -2734,8 +2771,7 @@ static void launch_series_fold(bk_env* env, uint64_t n) {
   g.slot0 = static_cast<uint32_t>(env->series_seen % env->cfg.history_capacity);
   g.n = static_cast<uint32_t>(n);
   g.rows = env->series_rows.p;
-  const uint32_t blocks = (g.n_books + series::FOLD_WAVES - 1) / series::FOLD_WAVES;
-  hipLaunchKernelGGL(series::k_fold, dim3(blocks), dim3(64 * series::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, series::k_fold, series::FOLD_WAVES, g);
 }
 
 // rows of the masked books (one mask byte per M books; nullptr: every book) -> cleared, or only their carry words -> 0
@@ -2746,8 +2782,7 @@ static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M
   g.n_books = env->cfg.n_books;
   g.carry_only = carry_only ? 1u : 0u;
   g.rows = env->series_rows.p;
-  const uint32_t blocks = (g.n_books + series::FOLD_WAVES - 1) / series::FOLD_WAVES;
-  hipLaunchKernelGGL(series::k_clear, dim3(blocks), dim3(64 * series::FOLD_WAVES), 0, env->stream, g);
+  launch_wave_per_book(env, series::k_clear, series::FOLD_WAVES, g);
 }
 
 // fold what is outstanding (nothing: no launch); a step the ring no longer retains refuses, rows and cursor unchanged
@@ -3504,6 +3539,25 @@ static int stage_mask(bk_env* env, size_t n, const uint8_t* mask_host, DevBuf<ui
   return BK_OK;
 }
 
+// The host form of a table's masked clear behind the table's own check: no mask is the _device form's business, a mask
+// (one byte per book) goes through the table's `staging` into it.
+static int clear_from_host(bk_env* env, const uint8_t* mask_host, DevBuf<uint8_t>& staging,
+                           int (*device_form)(bk_env*, const uint8_t*)) {
+  if (!mask_host) return device_form(env, nullptr);
+  if (int rc = use_device(env)) return rc;
+  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, staging)) return rc;
+  return device_form(env, staging.p);
+}
+
+// The host form of either reset behind its refusals: mask and seeds (one per unit) through the env's staging into the _device form.
+static int reset_from_host(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host,
+                           int (*device_form)(bk_env*, uint32_t, const uint8_t*, const uint64_t*)) {
+  if (int rc = use_device(env)) return rc;
+  const size_t n_units = env->cfg.n_books / env->M;
+  if (int rc = stage_mask(env, n_units, mask_host, env->reset_mask, seeds_host, &env->reset_seeds)) return rc;
+  return device_form(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
+}
+
 // reset::k_reset_books<R> for the units the mask names, from `snap` = [state | l2_last] of a slot, on the env's stream
 static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
   const size_t sb = static_cast<size_t>(env->cfg.n_books) * env->stride;
@@ -3520,26 +3574,29 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
   g.seeds = seeds_dev;
   g.trading = env->trading;
   const dim3 grid((g.n_units + reset::WAVES - 1) / reset::WAVES), block(64 * reset::WAVES);
-  switch (env->R) {
-    case 1: hipLaunchKernelGGL(reset::k_reset_books<1>, grid, block, 0, env->stream, g); break;
-    case 2: hipLaunchKernelGGL(reset::k_reset_books<2>, grid, block, 0, env->stream, g); break;
-    case 4: hipLaunchKernelGGL(reset::k_reset_books<4>, grid, block, 0, env->stream, g); break;
-    default: hipLaunchKernelGGL(reset::k_reset_books<8>, grid, block, 0, env->stream, g); break;
+  by_R(env->R, [&](auto r) { hipLaunchKernelGGL(reset::k_reset_books<decltype(r)::value>, grid, block, 0, env->stream, g); });
+}
+
+// What both resets open with, on the env's stream: the masked units' books go back to `snap` = [state | l2_last] of a slot
+// whose save kept `stamp_bound`.
+static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bound, const uint8_t* mask_dev,
+                            const uint64_t* seeds_dev) {
+  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
+    if (int rc = series_fold_outstanding(env)) return rc;
+    launch_series_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
   }
+  launch_reset_books(env, snap, mask_dev, seeds_dev);
+  HIPCHK(hipGetLastError());
+  env->stamp_room.raise(stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
+  return BK_OK;
 }
 
 // Holds NO host synchronisation: one launch on the env's stream - no stream wait, no host read of the mask, no allocation.
 int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, const uint64_t* seeds_dev) {
   if (int rc = reset_ok(env, slot, mask_dev)) return rc;
   if (int rc = use_device(env)) return rc;
-  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
-    if (int rc = series_fold_outstanding(env)) return rc;
-    launch_series_clear(env, mask_dev, env->M, true);
-    HIPCHK(hipGetLastError());
-  }
-  launch_reset_books(env, env->snaps[slot].buf.p, mask_dev, seeds_dev);
-  HIPCHK(hipGetLastError());
-  env->stamp_room.raise(env->snaps[slot].stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
+  if (int rc = reset_books_from(env, env->snaps[slot].buf.p, env->snaps[slot].stamp_bound, mask_dev, seeds_dev)) return rc;
   // which books changed is known on the device only: the members' lists of every book are rebuilt from the owner tags
   env->ml_valid = false;
   env->wl_valid = false;
@@ -3548,10 +3605,7 @@ int bk_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mask_dev, c
 
 int bk_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host) {
   if (int rc = reset_ok(env, slot, mask_host)) return rc;
-  if (int rc = use_device(env)) return rc;
-  const size_t n_units = env->cfg.n_books / env->M;
-  if (int rc = stage_mask(env, n_units, mask_host, env->reset_mask, seeds_host, &env->reset_seeds)) return rc;
-  return bk_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
+  return reset_from_host(env, slot, mask_host, seeds_host, bk_reset_books_device);
 }
 
 // ---------------------------------------------------------------- the same for a device-ingress env
@@ -3718,14 +3772,7 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
   if (int rc = use_device(env)) return rc;
   const bk_env::IngressSnapshot& s = env->isnaps[slot];
   const uint32_t n_units = env->cfg.n_books / env->M;
-  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
-    if (int rc = series_fold_outstanding(env)) return rc;
-    launch_series_clear(env, mask_dev, env->M, true);
-    HIPCHK(hipGetLastError());
-  }
-  launch_reset_books(env, s.buf.p, mask_dev, seeds_dev);
-  HIPCHK(hipGetLastError());
-  env->stamp_room.raise(s.stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
+  if (int rc = reset_books_from(env, s.buf.p, s.stamp_bound, mask_dev, seeds_dev)) return rc;
   uint32_t* counter = env->reset_list.p + n_units;
   HIPCHK(hipMemsetAsync(counter, 0, 4, env->stream));
   // (after a bk_set_*agents* call and before the next update the env's own rows are stale and are re-made by that update;
@@ -3785,10 +3832,7 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
 
 int bk_ingress_reset_books(bk_env* env, uint32_t slot, const uint8_t* mask_host, const uint64_t* seeds_host) {
   if (int rc = ingress_reset_ok(env, slot, mask_host)) return rc;
-  if (int rc = use_device(env)) return rc;
-  const size_t n_units = env->cfg.n_books / env->M;
-  if (int rc = stage_mask(env, n_units, mask_host, env->reset_mask, seeds_host, &env->reset_seeds)) return rc;
-  return bk_ingress_reset_books_device(env, slot, env->reset_mask.p, seeds_host ? env->reset_seeds.p : nullptr);
+  return reset_from_host(env, slot, mask_host, seeds_host, bk_ingress_reset_books_device);
 }
 
 // ------------------------------------------------------------------ trader accounts of a device-ingress env
@@ -3815,8 +3859,8 @@ int bk_accounts_enable(bk_env* env, uint32_t n_traders, int consume_trades) {
   DevBuf<unsigned long long> seen;
   HIPCHK(rows.alloc(B * n_traders * 2));
   HIPCHK(seen.alloc(B));
-  std::swap(env->acct.p, rows.p), std::swap(env->acct.n, rows.n);
-  std::swap(env->acct_seen.p, seen.p), std::swap(env->acct_seen.n, seen.n);
+  env->acct.swap(rows);
+  env->acct_seen.swap(seen);
   env->acct_traders = n_traders;
   env->acct_consume = consume_trades != 0;
   launch_accounts_clear(env, nullptr, 1);
@@ -3839,15 +3883,7 @@ int bk_accounts_device_ptr(bk_env* env, void** out) {
 
 int bk_get_accounts(bk_env* env, uint32_t first_book, uint32_t n_books, bk_account* out) {
   if (int rc = accounts_ok(env)) return rc;
-  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
-  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (int rc = use_device(env)) return rc;
-  HIPCHK(hipStreamSynchronize(env->stream));
-  if (n_books)
-    HIPCHK(hipMemcpy(out, env->acct.p + static_cast<size_t>(first_book) * env->acct_traders * 2,
-                     static_cast<size_t>(n_books) * env->acct_traders * sizeof(bk_account), hipMemcpyDeviceToHost));
-  return BK_OK;
+  return get_book_rows(env, first_book, n_books, {{env->acct.p, env->acct_traders * sizeof(bk_account), out}});
 }
 
 int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev) {
@@ -3860,10 +3896,7 @@ int bk_accounts_clear_device(bk_env* env, const uint8_t* mask_dev) {
 
 int bk_accounts_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = accounts_ok(env)) return rc;
-  if (!mask_host) return bk_accounts_clear_device(env, nullptr);
-  if (int rc = use_device(env)) return rc;
-  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->acct_mask)) return rc;
-  return bk_accounts_clear_device(env, env->acct_mask.p);
+  return clear_from_host(env, mask_host, env->acct_mask, bk_accounts_clear_device);
 }
 
 // ------------------------------------------------------------------ trade bars of a device-ingress env
@@ -3883,8 +3916,8 @@ int bk_trade_bars_enable(bk_env* env, uint32_t window, int consume_trades) {
   DevBuf<unsigned long long> seen;
   HIPCHK(rows.alloc(B * window * trade_bars::ROW_VECS));
   HIPCHK(seen.alloc(B));
-  std::swap(env->bars.p, rows.p), std::swap(env->bars.n, rows.n);
-  std::swap(env->bars_seen.p, seen.p), std::swap(env->bars_seen.n, seen.n);
+  env->bars.swap(rows);
+  env->bars_seen.swap(seen);
   env->bars_window = window;
   env->bars_consume = consume_trades != 0;
   launch_bars_clear(env, nullptr, 1);
@@ -3914,15 +3947,7 @@ int bk_trade_bars_slot(bk_env* env, uint32_t* out) {
 
 int bk_get_trade_bars(bk_env* env, uint32_t first_book, uint32_t n_books, bk_trade_bar* out) {
   if (int rc = trade_bars_ok(env)) return rc;
-  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
-  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (int rc = use_device(env)) return rc;
-  HIPCHK(hipStreamSynchronize(env->stream));
-  if (n_books)
-    HIPCHK(hipMemcpy(out, env->bars.p + static_cast<size_t>(first_book) * env->bars_window * trade_bars::ROW_VECS,
-                     static_cast<size_t>(n_books) * env->bars_window * sizeof(bk_trade_bar), hipMemcpyDeviceToHost));
-  return BK_OK;
+  return get_book_rows(env, first_book, n_books, {{env->bars.p, env->bars_window * sizeof(bk_trade_bar), out}});
 }
 
 int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev) {
@@ -3935,10 +3960,7 @@ int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev) {
 
 int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = trade_bars_ok(env)) return rc;
-  if (!mask_host) return bk_trade_bars_clear_device(env, nullptr);
-  if (int rc = use_device(env)) return rc;
-  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->bars_mask)) return rc;
-  return bk_trade_bars_clear_device(env, env->bars_mask.p);
+  return clear_from_host(env, mask_host, env->bars_mask, bk_trade_bars_clear_device);
 }
 
 // ------------------------------------------------------------------ per-book series moments: the entries
@@ -3951,7 +3973,7 @@ int bk_series_enable(bk_env* env) {
   if (int rc = use_device(env)) return rc;
   DevBuf<bk_u32x4> rows;
   HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * series::ROW_VECS));
-  std::swap(env->series_rows.p, rows.p), std::swap(env->series_rows.n, rows.n);
+  env->series_rows.swap(rows);
   env->series = true;
   env->series_seen = env->steps_done;
   launch_series_clear(env, nullptr, 1, false);
@@ -3985,11 +4007,8 @@ int bk_series_clear_device(bk_env* env, const uint8_t* mask_dev) {
 
 int bk_series_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = series_ok(env)) return rc;
-  if (!mask_host) return bk_series_clear_device(env, nullptr);
-  if (env->series_seen < hist_first(env)) return series_fold_outstanding(env);  // (refused before the mask is staged)
-  if (int rc = use_device(env)) return rc;
-  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, env->series_mask)) return rc;
-  return bk_series_clear_device(env, env->series_mask.p);
+  if (mask_host && env->series_seen < hist_first(env)) return series_fold_outstanding(env);  // (refused before the mask is staged)
+  return clear_from_host(env, mask_host, env->series_mask, bk_series_clear_device);
 }
 
 int bk_series_device_ptr(bk_env* env, void** out) {
@@ -4001,15 +4020,7 @@ int bk_series_device_ptr(bk_env* env, void** out) {
 
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out) {
   if (int rc = series_ok(env)) return rc;
-  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
-  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (int rc = use_device(env)) return rc;
-  HIPCHK(hipStreamSynchronize(env->stream));
-  if (n_books)
-    HIPCHK(hipMemcpy(out, env->series_rows.p + static_cast<size_t>(first_book) * series::ROW_VECS,
-                     static_cast<size_t>(n_books) * sizeof(bk_series_row), hipMemcpyDeviceToHost));
-  return BK_OK;
+  return get_book_rows(env, first_book, n_books, {{env->series_rows.p, sizeof(bk_series_row), out}});
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env
@@ -4033,8 +4044,8 @@ int bk_open_orders_enable(bk_env* env, uint32_t n_traders, uint32_t depth) {
   DevBuf<bk_u32x4> summary, entries;
   HIPCHK(summary.alloc(rows * 2));
   HIPCHK(entries.alloc(rows * depth));
-  std::swap(env->open_summary.p, summary.p), std::swap(env->open_summary.n, summary.n);
-  std::swap(env->open_entries.p, entries.p), std::swap(env->open_entries.n, entries.n);
+  env->open_summary.swap(summary);
+  env->open_entries.swap(entries);
   env->open_traders = n_traders;
   env->open_depth = depth;
   launch_open_refresh(env, nullptr, 1);
@@ -4068,17 +4079,9 @@ int bk_open_orders_device_ptrs(bk_env* env, void** summary, void** entries) {
 int bk_get_open_orders(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_summary* summary_out,
                        bk_open_order* entries_out) {
   if (int rc = open_orders_ok(env)) return rc;
-  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
-  if (n_books && !summary_out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (int rc = use_device(env)) return rc;
-  HIPCHK(hipStreamSynchronize(env->stream));
-  const size_t first = static_cast<size_t>(first_book) * env->open_traders, rows = static_cast<size_t>(n_books) * env->open_traders;
-  if (rows) HIPCHK(hipMemcpy(summary_out, env->open_summary.p + first * 2, rows * sizeof(bk_open_summary), hipMemcpyDeviceToHost));
-  if (rows && entries_out && env->open_depth)
-    HIPCHK(hipMemcpy(entries_out, env->open_entries.p + first * env->open_depth, rows * env->open_depth * sizeof(bk_open_order),
-                     hipMemcpyDeviceToHost));
-  return BK_OK;
+  const size_t entries = static_cast<size_t>(env->open_traders) * env->open_depth;  // (per book; none with depth == 0)
+  return get_book_rows(env, first_book, n_books, {{env->open_summary.p, env->open_traders * sizeof(bk_open_summary), summary_out},
+                                                  {env->open_entries.p, entries * sizeof(bk_open_order), entries_out}});
 }
 
 // ------------------------------------------------------------------ queue positions of the open orders
@@ -4095,7 +4098,7 @@ int bk_open_queue_enable(bk_env* env) {
   if (int rc = use_device(env)) return rc;
   DevBuf<bk_u32x4> queue;
   HIPCHK(queue.alloc(static_cast<size_t>(env->cfg.n_books) * env->open_traders * env->open_depth * 2));
-  std::swap(env->open_queue.p, queue.p), std::swap(env->open_queue.n, queue.n);
+  env->open_queue.swap(queue);
   launch_open_refresh(env, nullptr, 1);
   HIPCHK(hipGetLastError());
   return BK_OK;
@@ -4116,16 +4119,8 @@ int bk_open_queue_device_ptr(bk_env* env, void** out) {
 
 int bk_get_open_queue(bk_env* env, uint32_t first_book, uint32_t n_books, bk_open_queue* out) {
   if (int rc = open_queue_ok(env)) return rc;
-  if (first_book > env->cfg.n_books || n_books > env->cfg.n_books - first_book)
-    return fail(BK_INVALID_ARGUMENT, "book range out of bounds");
-  if (n_books && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
-  if (int rc = use_device(env)) return rc;
-  HIPCHK(hipStreamSynchronize(env->stream));
-  const size_t per_book = static_cast<size_t>(env->open_traders) * env->open_depth;
-  if (n_books)
-    HIPCHK(hipMemcpy(out, env->open_queue.p + first_book * per_book * 2, n_books * per_book * sizeof(bk_open_queue),
-                     hipMemcpyDeviceToHost));
-  return BK_OK;
+  const size_t entries = static_cast<size_t>(env->open_traders) * env->open_depth;
+  return get_book_rows(env, first_book, n_books, {{env->open_queue.p, entries * sizeof(bk_open_queue), out}});
 }
 
 // ------------------------------------------------------------------ quotes through the device ingress
@@ -4169,25 +4164,13 @@ int bk_submit_quotes_device(bk_env* env, const bk_quote* quotes_dev, uint64_t* o
 int bk_submit_quotes(bk_env* env, const bk_quote* quotes, uint64_t* out_ids_dev, uint32_t* status_dev) {
   if (int rc = submit_quotes_ok(env, quotes)) return rc;
   if (int rc = use_device(env)) return rc;
-  const size_t rows = static_cast<size_t>(env->cfg.n_books) * env->open_traders;
-  if (!env->quote_pin) {  // (the view's shape is fixed once enabled: one size for the env's life)
-    DevBuf<bk_u32x4> stage;
-    HIPCHK(stage.alloc(rows));
-    void* pin = nullptr;
-    HIPCHK(hipHostMalloc(&pin, rows * sizeof(bk_quote), hipHostMallocDefault));
-    if (hipEventCreateWithFlags(&env->quote_copied, hipEventDisableTiming) != hipSuccess) {
-      (void)hipHostFree(pin);
-      return fail(BK_HIP_ERROR, "hipEventCreateWithFlags failed");
-    }
-    env->quote_pin = static_cast<bk_quote*>(pin);
-    std::swap(env->quote_stage.p, stage.p), std::swap(env->quote_stage.n, stage.n);
-  } else {
-    HIPCHK(hipEventSynchronize(env->quote_copied));  // the call before this one has been uploaded: the pinned rows are free
-  }
-  std::memcpy(env->quote_pin, quotes, rows * sizeof(bk_quote));  // the caller's table may be reused on return
-  HIPCHK(hipMemcpyAsync(env->quote_stage.p, env->quote_pin, rows * sizeof(bk_quote), hipMemcpyHostToDevice, env->stream));
-  HIPCHK(hipEventRecord(env->quote_copied, env->stream));
-  return bk_submit_quotes_device(env, reinterpret_cast<const bk_quote*>(env->quote_stage.p), out_ids_dev, status_dev);
+  const size_t bytes = static_cast<size_t>(env->cfg.n_books) * env->open_traders * sizeof(bk_quote);
+  HostStage& st = env->quote_stage;
+  // (the view's shape is fixed once enabled: one size for the env's life, so no block in use is ever replaced)
+  if (int rc = st.reserve(bytes, env->stream, false)) return rc;
+  std::memcpy(st.pin, quotes, bytes);  // the caller's table may be reused on return
+  if (int rc = st.upload(bytes, env->stream)) return rc;
+  return bk_submit_quotes_device(env, reinterpret_cast<const bk_quote*>(st.dev.p), out_ids_dev, status_dev);
 }
 
 uint64_t bk_state_bytes_per_book(const bk_env* env) { return env ? static_cast<uint64_t>(env->stride) * 4 : 0; }

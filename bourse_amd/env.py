@@ -107,6 +107,51 @@ class MomentumAgent:
 _STICKY_MAGIC = b"BKSTICKY"  # trailer of ManyBookEnv.checkpoint(): flag bits already reported to a strict caller
 
 
+# ---------------------------------------------------------------- what the entries ask of their arguments
+def _is_dev(x) -> bool:
+    """A device object - a torch tensor or anything with ``__cuda_array_interface__`` - and not a host array."""
+    return hasattr(x, "data_ptr") or hasattr(x, "__cuda_array_interface__")
+
+
+def _dev_count(x) -> int:
+    """Elements of a device object."""
+    return int(x.numel()) if hasattr(x, "numel") else int(np.prod(x.__cuda_array_interface__["shape"]))
+
+
+def _dev_bytes(x) -> int:
+    """Bytes of a device object, whatever its element type."""
+    if hasattr(x, "data_ptr"):
+        return _dev_count(x) * int(x.element_size())
+    return _dev_count(x) * np.dtype(x.__cuda_array_interface__["typestr"]).itemsize
+
+
+def _host_mask(mask, n: int, per: str, name: str = "mask") -> np.ndarray:
+    """A host mask as the library reads it: contiguous uint8, ``n`` entries (``per``: what an entry stands for)."""
+    m = np.ascontiguousarray(np.asarray(mask))
+    if m.dtype != np.bool_ and m.dtype != np.uint8:
+        raise ValueError("mask: a bool or uint8 array is needed")
+    m = m.astype(np.uint8, copy=False)
+    if m.shape != (n,):
+        raise ValueError(f"{name}: {n} elements are needed ({per})")
+    return m
+
+
+def _raise_on_status(status, unit: str):
+    """``check_status=True``: raise for the first book whose ``status`` pair ``{code, units applied}`` reports a failure -
+    the reference's ``ValueError`` at a bad price, ``CapacityError`` otherwise.  ``unit`` words the message: ``"element"``
+    of a batch (``submit_instructions_device``) or ``"grid position"`` (``submit_quotes``)."""
+    st = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
+    st = st.reshape(-1, 2).view(np.uint32) if st.dtype.itemsize == 4 else st.reshape(-1, 2)
+    bad = np.nonzero(st[:, 0])[0]
+    if len(bad):
+        b, code, applied = int(bad[0]), int(st[bad[0], 0]), int(st[bad[0], 1])
+        if code == _lib.BK_PRICE:
+            price = "a price of its batch" if unit == "element" else "a quoted price"
+            raise ValueError(f"book {b}: {price} was not a multiple of the tick size "
+                             f"({unit} {applied} of the book's batch; earlier {unit.split()[-1]}s are queued)")
+        raise _lib.CapacityError(code, f"book {b}: event queue / id space exhausted after {applied} {unit}s")
+
+
 class ManyBookEnv:
     """B books on one GPU.  ``Env::new(start_time, tick_size, step_size, trading)`` per book."""
 
@@ -140,6 +185,10 @@ class ManyBookEnv:
         check(self._L.bk_env_create(C.byref(cfg), C.byref(self._h)))
         self.width = int(self._L.bk_l2_width(self._h))
         self._stream = None if stream is None else int(stream)  # (None: the env's own stream, which Python never sees)
+        # the device-resident tables this env has enabled (0 / None / False: not enabled)
+        self._n_traders = 0       # enable_accounts
+        self._bars_window = 0     # enable_trade_bars
+        self._open_shape = None   # enable_open_orders: (n_traders, depth)
         self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
         if stream is not None:
             check(self._L.bk_env_set_stream(self._h, C.c_void_p(stream)))
@@ -216,12 +265,8 @@ class ManyBookEnv:
         (``bk_submit_instructions_csr``: stops at the first bad price of any book)."""
         if getattr(self, "_device_ingress", False):
             out, status, bad = self.submit_result(self.submit_instructions_all_async(book_offsets, instructions))
-            if bad is not None:
-                code, applied = int(status[bad, 0]), int(status[bad, 1])
-                if code == _lib.BK_PRICE:
-                    raise ValueError(f"book {bad}: a price of its batch was not a multiple of the tick size "
-                                     f"(element {applied} of the book's batch; earlier elements are queued)")
-                raise _lib.CapacityError(code, f"book {bad}: event queue / id space exhausted after {applied} elements")
+            if bad is not None:  # (the lowest book with a code in `status`)
+                _raise_on_status(status, "element")
             return out
         off, action, sides, vols, traders, prices, order_ids = self._host_batch(book_offsets, instructions)
         out = np.full(len(action), 2**64 - 1, dtype=np.uint64)
@@ -398,6 +443,42 @@ class ManyBookEnv:
             raise ValueError(f"{name}: a contiguous device array of {itemsize}-byte elements is needed")
         return C.c_void_p(cai["data"][0])
 
+    def _device_ptr(self, entry) -> int:
+        """The device address a ``bk_*_device_ptr`` entry hands out."""
+        out = C.c_void_p()
+        check(entry(self._h, C.byref(out)))
+        return int(out.value)
+
+    def _book_range(self, first_book: int, n_books: Optional[int]) -> Tuple[int, int]:
+        """``(first, n)`` of the readers' book range; ``n_books=None``: to the last book.  (The library checks the end.)"""
+        first = int(first_book)
+        n = self.n_books - first if n_books is None else int(n_books)
+        if first < 0 or n < 0:
+            raise ValueError("book range out of bounds")
+        return first, n
+
+    def _book_rows(self, entry, first_book: int, n_books: Optional[int], *tables):
+        """The rows of a book range from a ``bk_get_*`` entry: one zeroed array ``[n, *shape]`` per ``(shape, dtype)`` of
+        ``tables`` for the entry to fill (``None``: a table this env does not keep - the entry is handed a null pointer)."""
+        first, n = self._book_range(first_book, n_books)
+        outs = [None if t is None else np.zeros((n,) + tuple(t[0]), dtype=t[1]) for t in tables]
+        check(entry(self._h, first, n, *(None if o is None else o.ctypes.data_as(C.c_void_p) for o in outs)))
+        return outs
+
+    def _masked_clear(self, device_entry, host_entry, mask, sync):
+        """``clear_accounts``' ``mask`` / ``sync`` for any per-book table: ``None``, a device object or a host array."""
+        if mask is None:
+            check(device_entry(self._h, None))
+        elif _is_dev(mask):
+            if _dev_count(mask) != self.n_books:
+                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            check(device_entry(self._h, self._dev_ptr(mask, 1, "mask")))
+        else:
+            m = _host_mask(mask, self.n_books, "one per book")
+            check(host_entry(self._h, m.ctypes.data_as(C.c_void_p)))
+        if sync:
+            self.sync()
+
     def submit_instructions_device(self, book_offsets, action, side, vol, trader_id, price, order_id, out_ids=None,
                                    status=None, check_status: bool = False):
         """``submit_instructions`` (rust/src/step_sim_numpy.rs:233-275) for every book from DEVICE arrays, nothing passing
@@ -412,8 +493,7 @@ class ManyBookEnv:
         off_ptr = P(book_offsets, 8, "book_offsets")  # (validates the first argument before anything is looked at)
         if action is None:
             raise ValueError("action: a contiguous CUDA tensor of 4-byte elements is needed")
-        n_elem = action.numel() if hasattr(action, "numel") else int(np.prod(action.__cuda_array_interface__["shape"]))
-        if n_elem == 0:  # nothing to submit for any book (an empty device array has no address to hand over)
+        if _dev_count(action) == 0:  # nothing to submit for any book (an empty device array has no address to hand over)
             if status is not None and hasattr(status, "zero_"):
                 status.zero_()
             return out_ids, status
@@ -425,15 +505,7 @@ class ManyBookEnv:
             if status is None:
                 raise ValueError("check_status needs a status array")
             self.sync()
-            st = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
-            st = st.reshape(-1, 2).view(np.uint32) if st.dtype.itemsize == 4 else st.reshape(-1, 2)
-            bad = np.nonzero(st[:, 0])[0]
-            if len(bad):
-                b, code = int(bad[0]), int(st[bad[0], 0])
-                if code == _lib.BK_PRICE:
-                    raise ValueError(f"book {b}: a price of its batch was not a multiple of the tick size "
-                                     f"(element {int(st[b, 1])} of the book's batch; earlier elements are queued)")
-                raise _lib.CapacityError(code, f"book {b}: event queue / id space exhausted after {int(st[b, 1])} elements")
+            _raise_on_status(status, "element")
         return out_ids, status
 
     def flags_summary(self) -> Tuple[int, int]:
@@ -681,47 +753,37 @@ class ManyBookEnv:
         dev_entry = self._L.bk_retune_agents_device if members else self._L.bk_retune_random_agents_device
         host_entry = self._L.bk_retune_agents if members else self._L.bk_retune_random_agents
 
-        def is_dev(x):
-            return hasattr(x, "data_ptr") or hasattr(x, "__cuda_array_interface__")
-
-        def dev_bytes(x, name):
+        def block(x, name):  # (a device object of any element width: its address and its size in bytes)
             if hasattr(x, "data_ptr"):
                 if not x.is_cuda or not x.is_contiguous():
                     raise ValueError(f"{name}: a contiguous CUDA tensor is needed")
-                return C.c_void_p(x.data_ptr()), int(x.numel()) * int(x.element_size())
+                return C.c_void_p(x.data_ptr()), _dev_bytes(x)
             cai = x.__cuda_array_interface__
             if cai.get("strides"):
                 raise ValueError(f"{name}: a contiguous device array is needed")
-            return C.c_void_p(cai["data"][0]), int(np.prod(cai["shape"])) * np.dtype(cai["typestr"]).itemsize
+            return C.c_void_p(cai["data"][0]), _dev_bytes(x)
 
         for name, x in (("mask", mask), ("status", status)):
-            if x is not None and is_dev(x) != is_dev(table):
+            if x is not None and _is_dev(x) != _is_dev(table):
                 raise ValueError(f"table and {name} must both be host arrays or both be device arrays")
-        if is_dev(table):
-            ptr, nbytes = dev_bytes(table, "table")
+        if _is_dev(table):
+            ptr, nbytes = block(table, "table")
             if nbytes == 0 or nbytes % (n_units * itemsize):
                 raise ValueError(f"table: {n_units} x width rows of {itemsize} bytes are needed, got {nbytes} bytes")
             width = nbytes // (n_units * itemsize)
             m_ptr = s_ptr = None
             if mask is not None:
-                m_ptr, mb = dev_bytes(mask, "mask")
+                m_ptr, mb = block(mask, "mask")
                 if mb != n_units:
                     raise ValueError(f"mask: {n_units} one-byte elements are needed (one per book, or per market)")
             if status is not None:
-                s_ptr, sb = dev_bytes(status, "status")
+                s_ptr, sb = block(status, "status")
                 if sb != n_units * 8:
                     raise ValueError(f"status: {2 * n_units} four-byte elements are needed (two per book, or per market)")
             check(dev_entry(self._h, width, ptr, m_ptr, s_ptr))
         else:
             arr = host_rows(table)
-            m = None
-            if mask is not None:
-                m = np.ascontiguousarray(np.asarray(mask))
-                if m.dtype != np.bool_ and m.dtype != np.uint8:
-                    raise ValueError("mask: a bool or uint8 array is needed")
-                m = m.astype(np.uint8, copy=False)
-                if m.shape != (n_units,):
-                    raise ValueError(f"mask: {n_units} elements are needed (one per book, or per market)")
+            m = None if mask is None else _host_mask(mask, n_units, "one per book, or per market")
             if status is not None and (not isinstance(status, np.ndarray) or status.size != 2 * n_units):
                 raise ValueError(f"status: a numpy array of {2 * n_units} elements is needed")
             check(host_entry(self._h, arr.shape[1], arr.ctypes.data_as(C.c_void_p),
@@ -965,15 +1027,11 @@ class ManyBookEnv:
         return {k: int(getattr(s, k)) for k, _ in Stats._fields_}
 
     def stats_device_ptr(self) -> int:
-        out = C.c_void_p()
-        check(self._L.bk_stats_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_stats_device_ptr)
 
     def level2_device_ptr(self) -> int:
         """Device address of the latest level-2 records, u32[n_books][width] (for on-device consumers)."""
-        out = C.c_void_p()
-        check(self._L.bk_level2_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_level2_device_ptr)
 
     def stats_compute_async(self):
         check(self._L.bk_stats_compute(self._h, None))
@@ -1096,29 +1154,20 @@ class ManyBookEnv:
 
     def _masked_reset(self, device_entry, host_entry, mask, seeds, slot, sync):
         n_units = self.n_books // self.assets
-
-        def is_dev(x):
-            return hasattr(x, "data_ptr") or hasattr(x, "__cuda_array_interface__")
-
-        def count(x):
-            return int(x.numel()) if hasattr(x, "numel") else int(np.prod(x.__cuda_array_interface__["shape"]))
-
+        per = "one per book, or per market"
         if mask is None:
             raise ValueError("mask: one bool / uint8 per book (market) is needed")
-        if seeds is not None and is_dev(mask) != is_dev(seeds):
+        if seeds is not None and _is_dev(mask) != _is_dev(seeds):
             raise ValueError("mask and seeds must both be host arrays or both be device arrays")
-        if is_dev(mask):
-            if count(mask) != n_units or (seeds is not None and count(seeds) != n_units):
-                raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
+        if _is_dev(mask):
+            if _dev_count(mask) != n_units or (seeds is not None and _dev_count(seeds) != n_units):
+                raise ValueError(f"mask / seeds: {n_units} elements are needed ({per})")
             check(device_entry(self._h, int(slot), self._dev_ptr(mask, 1, "mask"), self._dev_ptr(seeds, 8, "seeds")))
         else:
-            m = np.ascontiguousarray(np.asarray(mask))
-            if m.dtype != np.bool_ and m.dtype != np.uint8:
-                raise ValueError("mask: a bool or uint8 array is needed")
-            m = m.astype(np.uint8, copy=False)
+            m = _host_mask(mask, n_units, per, name="mask / seeds")
             s = None if seeds is None else np.ascontiguousarray(np.asarray(seeds), dtype=np.uint64)
-            if m.shape != (n_units,) or (s is not None and s.shape != (n_units,)):
-                raise ValueError(f"mask / seeds: {n_units} elements are needed (one per book, or per market)")
+            if s is not None and s.shape != (n_units,):
+                raise ValueError(f"mask / seeds: {n_units} elements are needed ({per})")
             check(host_entry(self._h, int(slot), m.ctypes.data_as(C.c_void_p),
                              None if s is None else s.ctypes.data_as(C.c_void_p)))
         if sync:
@@ -1164,27 +1213,19 @@ class ManyBookEnv:
         self._n_traders = int(n_traders)
 
     def _accounts_traders(self) -> int:
-        n = getattr(self, "_n_traders", 0)
-        if not n:
+        if not self._n_traders:
             raise _lib.BourseError(_lib.BK_INVALID, "this env has no trader accounts: call enable_accounts first")
-        return n
+        return self._n_traders
 
     def accounts(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
         """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
         shape ``[n, n_traders]`` (``ACCOUNT_DTYPE``).  Waits for the env's stream."""
         nt = self._accounts_traders()
-        n = self.n_books - int(first_book) if n_books is None else int(n_books)
-        if int(first_book) < 0 or n < 0:
-            raise ValueError("book range out of bounds")
-        out = np.zeros((n, nt), dtype=_lib.ACCOUNT_DTYPE)
-        check(self._L.bk_get_accounts(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._book_rows(self._L.bk_get_accounts, first_book, n_books, ((nt,), _lib.ACCOUNT_DTYPE))[0]
 
     def accounts_device_ptr(self) -> int:
         """Device address of the table, ``bk_account[n_books][n_traders]`` (for on-device consumers)."""
-        out = C.c_void_p()
-        check(self._L.bk_accounts_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_accounts_device_ptr)
 
     def accounts_view(self) -> "AccountsView":
         """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, n_traders, 4)``, the
@@ -1199,23 +1240,7 @@ class ManyBookEnv:
         CUDA tensor / ``__cuda_array_interface__`` object written on the env's stream (``bk_accounts_clear_device``: no
         host synchronisation).  ``reset_ingress_books`` clears the books it resets by itself.  ``sync`` waits for it."""
         self._accounts_traders()
-        if mask is None:
-            check(self._L.bk_accounts_clear_device(self._h, None))
-        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
-            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
-            if n != self.n_books:
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_accounts_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
-        else:
-            m = np.ascontiguousarray(np.asarray(mask))
-            if m.dtype != np.bool_ and m.dtype != np.uint8:
-                raise ValueError("mask: a bool or uint8 array is needed")
-            m = m.astype(np.uint8, copy=False)
-            if m.shape != (self.n_books,):
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_accounts_clear(self._h, m.ctypes.data_as(C.c_void_p)))
-        if sync:
-            self.sync()
+        self._masked_clear(self._L.bk_accounts_clear_device, self._L.bk_accounts_clear, mask, sync)
 
     # ------------------------------------------------------------ per-step trade bars of an env with the device ingress
     TRADE_BAR_DTYPE = _lib.TRADE_BAR_DTYPE
@@ -1235,27 +1260,19 @@ class ManyBookEnv:
         self._bars_window = int(window)
 
     def _trade_bars_window(self) -> int:
-        n = getattr(self, "_bars_window", 0)
-        if not n:
+        if not self._bars_window:
             raise _lib.BourseError(_lib.BK_INVALID, "this env has no trade bars: call enable_trade_bars first")
-        return n
+        return self._bars_window
 
     def trade_bars(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
         """The rings of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
         shape ``[n, window]`` (``TRADE_BAR_DTYPE``).  Waits for the env's stream."""
         w = self._trade_bars_window()
-        n = self.n_books - int(first_book) if n_books is None else int(n_books)
-        if int(first_book) < 0 or n < 0:
-            raise ValueError("book range out of bounds")
-        out = np.zeros((n, w), dtype=_lib.TRADE_BAR_DTYPE)
-        check(self._L.bk_get_trade_bars(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._book_rows(self._L.bk_get_trade_bars, first_book, n_books, ((w,), _lib.TRADE_BAR_DTYPE))[0]
 
     def trade_bars_device_ptr(self) -> int:
         """Device address of the ring, ``bk_trade_bar[n_books][window]`` (for on-device consumers)."""
-        out = C.c_void_p()
-        check(self._L.bk_trade_bars_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_trade_bars_device_ptr)
 
     def trade_bars_slot(self) -> int:
         """The slot the latest folded step went to, ``(steps_done() - 1) % window``: a host integer, no wait."""
@@ -1276,23 +1293,7 @@ class ManyBookEnv:
         current trade count on and the carried price starts at 0.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
         (``bk_trade_bars_clear`` / ``bk_trade_bars_clear_device``).  ``reset_ingress_books`` clears the books it resets."""
         self._trade_bars_window()
-        if mask is None:
-            check(self._L.bk_trade_bars_clear_device(self._h, None))
-        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
-            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
-            if n != self.n_books:
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_trade_bars_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
-        else:
-            m = np.ascontiguousarray(np.asarray(mask))
-            if m.dtype != np.bool_ and m.dtype != np.uint8:
-                raise ValueError("mask: a bool or uint8 array is needed")
-            m = m.astype(np.uint8, copy=False)
-            if m.shape != (self.n_books,):
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_trade_bars_clear(self._h, m.ctypes.data_as(C.c_void_p)))
-        if sync:
-            self.sync()
+        self._masked_clear(self._L.bk_trade_bars_clear_device, self._L.bk_trade_bars_clear, mask, sync)
 
     # ------------------------------------------------------------ per-book series moments of the level-2 history
     SERIES_DTYPE = _lib.SERIES_DTYPE
@@ -1319,18 +1320,11 @@ class ManyBookEnv:
     def series(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
         """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array
         (``SERIES_DTYPE``).  Waits for the env's stream; does NOT fold."""
-        n = self.n_books - int(first_book) if n_books is None else int(n_books)
-        if int(first_book) < 0 or n < 0:
-            raise ValueError("book range out of bounds")
-        out = np.zeros(n, dtype=_lib.SERIES_DTYPE)
-        check(self._L.bk_get_series(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._book_rows(self._L.bk_get_series, first_book, n_books, ((), _lib.SERIES_DTYPE))[0]
 
     def series_device_ptr(self) -> int:
         """Device address of the table, ``bk_series_row[n_books]`` (for on-device consumers)."""
-        out = C.c_void_p()
-        check(self._L.bk_series_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_series_device_ptr)
 
     def series_view(self) -> "SeriesView":
         """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, 24)``, the words in
@@ -1345,23 +1339,8 @@ class ManyBookEnv:
         on without folding - the way on after lost steps.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
         (``bk_series_clear`` / ``bk_series_clear_device``).  ``reset_books`` / ``reset_ingress_books`` fold and then cut only
         the carry of the books they reset: the sums go on across episodes and no return spans a reset."""
-        if mask is None:
-            check(self._L.bk_series_clear_device(self._h, None))
-        elif hasattr(mask, "data_ptr") or hasattr(mask, "__cuda_array_interface__"):
-            n = int(mask.numel()) if hasattr(mask, "numel") else int(np.prod(mask.__cuda_array_interface__["shape"]))
-            if n != self.n_books:
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_series_clear_device(self._h, self._dev_ptr(mask, 1, "mask")))
-        else:
-            m = np.ascontiguousarray(np.asarray(mask))
-            if m.dtype != np.bool_ and m.dtype != np.uint8:
-                raise ValueError("mask: a bool or uint8 array is needed")
-            m = m.astype(np.uint8, copy=False)
-            if m.shape != (self.n_books,):
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
-            check(self._L.bk_series_clear(self._h, m.ctypes.data_as(C.c_void_p)))
-        if sync:
-            self.sync()
+        # (no check of its own in front: the library refuses an env without the table)
+        self._masked_clear(self._L.bk_series_clear_device, self._L.bk_series_clear, mask, sync)
 
     def run_series(self, n_steps: int, chunk: Optional[int] = None):
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
@@ -1395,10 +1374,9 @@ class ManyBookEnv:
         self._open_shape = (int(n_traders), int(depth))
 
     def _open_orders_shape(self):
-        shape = getattr(self, "_open_shape", None)
-        if shape is None:
+        if self._open_shape is None:
             raise _lib.BourseError(_lib.BK_INVALID, "this env has no open-order view: call enable_open_orders first")
-        return shape
+        return self._open_shape
 
     def refresh_open_orders(self):
         """``bk_open_orders_refresh``: recompute every book's rows now (asynchronous on the env's stream), for callers
@@ -1412,13 +1390,8 @@ class ManyBookEnv:
         or ``None`` with ``depth == 0)``.  A trader's entries are its resting orders in ascending order id; unused slots
         hold ``order_id == 0xFFFFFFFF``.  Waits for the env's stream."""
         nt, depth = self._open_orders_shape()
-        n = self.n_books - int(first_book) if n_books is None else int(n_books)
-        if int(first_book) < 0 or n < 0:
-            raise ValueError("book range out of bounds")
-        summary = np.zeros((n, nt), dtype=_lib.OPEN_SUMMARY_DTYPE)
-        entries = np.zeros((n, nt, depth), dtype=_lib.OPEN_ORDER_DTYPE) if depth else None
-        check(self._L.bk_get_open_orders(self._h, int(first_book), n, summary.ctypes.data_as(C.c_void_p),
-                                         entries.ctypes.data_as(C.c_void_p) if depth else None))
+        summary, entries = self._book_rows(self._L.bk_get_open_orders, first_book, n_books, ((nt,), _lib.OPEN_SUMMARY_DTYPE),
+                                           ((nt, depth), _lib.OPEN_ORDER_DTYPE) if depth else None)
         return summary, entries
 
     def open_orders_device_ptrs(self):
@@ -1467,19 +1440,12 @@ class ManyBookEnv:
         structured array of shape ``[n, n_traders, depth]`` (``OPEN_QUEUE_DTYPE``); row ``[b, t, k]`` belongs to entry
         ``[b, t, k]`` of ``open_orders()``, and an unused entry's row is all zeros.  Waits for the env's stream."""
         nt, depth = self._open_queue_shape()
-        n = self.n_books - int(first_book) if n_books is None else int(n_books)
-        if int(first_book) < 0 or n < 0:
-            raise ValueError("book range out of bounds")
-        out = np.zeros((n, nt, depth), dtype=_lib.OPEN_QUEUE_DTYPE)
-        check(self._L.bk_get_open_queue(self._h, int(first_book), n, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._book_rows(self._L.bk_get_open_queue, first_book, n_books, ((nt, depth), _lib.OPEN_QUEUE_DTYPE))[0]
 
     def open_queue_device_ptr(self) -> int:
         """Device address of the table, ``bk_open_queue[n_books][n_traders][depth]`` (for on-device consumers)."""
         self._open_queue_shape()
-        out = C.c_void_p()
-        check(self._L.bk_open_queue_device_ptr(self._h, C.byref(out)))
-        return int(out.value)
+        return self._device_ptr(self._L.bk_open_queue_device_ptr)
 
     def open_queue_view(self) -> "OpenOrdersView":
         """The table in place as an object with ``__cuda_array_interface__`` (``torch.as_tensor(view, device="cuda")`` is
@@ -1510,13 +1476,11 @@ class ManyBookEnv:
         ``{code, grid positions applied}``.  ``check_status`` behaves as on ``submit_instructions_device``."""
         if check_status and status is None:
             raise ValueError("check_status needs a status array")
-        shape = getattr(self, "_open_shape", None)
-        nt = shape[0] if shape else None  # (without the view the library refuses the call and says why)
+        nt = self._open_shape[0] if self._open_shape else None  # (without the view the library refuses the call and says why)
         P = self._dev_ptr
-        if hasattr(quotes, "data_ptr") or hasattr(quotes, "__cuda_array_interface__"):
+        if _is_dev(quotes):
             ptr = P(quotes, 4, "quotes")
-            n = int(quotes.numel()) if hasattr(quotes, "numel") else int(np.prod(quotes.__cuda_array_interface__["shape"]))
-            if nt is not None and n != self.n_books * nt * 4:
+            if nt is not None and _dev_count(quotes) != self.n_books * nt * 4:
                 raise ValueError(f"quotes: shape (n_books, n_traders, 4) = ({self.n_books}, {nt}, 4) is needed")
             check(self._L.bk_submit_quotes_device(self._h, ptr, P(out_ids, 8, "out_ids"), P(status, 4, "status")))
         else:
@@ -1537,41 +1501,34 @@ class ManyBookEnv:
                                            P(out_ids, 8, "out_ids"), P(status, 4, "status")))
         if check_status:
             self.sync()
-            st = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
-            st = st.reshape(-1, 2).view(np.uint32) if st.dtype.itemsize == 4 else st.reshape(-1, 2)
-            bad = np.nonzero(st[:, 0])[0]
-            if len(bad):
-                b, code = int(bad[0]), int(st[bad[0], 0])
-                if code == _lib.BK_PRICE:
-                    raise ValueError(f"book {b}: a quoted price was not a multiple of the tick size "
-                                     f"(grid position {int(st[b, 1])} of the book's batch; earlier positions are queued)")
-                raise _lib.CapacityError(code, f"book {b}: event queue / id space exhausted after {int(st[b, 1])} grid positions")
+            _raise_on_status(status, "grid position")
         return out_ids, status
 
 
-class OpenOrdersView:
-    """One table of ``ManyBookEnv.open_orders_views()`` where it lives, for ``torch.as_tensor(view, device="cuda")``, cupy
-    and anything else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
+class _DeviceTableView:
+    """A device-resident table of an env where it lives, for ``torch.as_tensor(view, device="cuda")``, cupy and anything
+    else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
 
     def __init__(self, env, ptr: int, shape, typestr: str, stream: Optional[int]):
         self._env = env
-        # (`stream`: as AccountsView spells it - None when unknown, 1 for the legacy default stream, else the handle)
+        # version 3 of the interface: `stream` is the stream the data is written on - None when unknown (an env on its own
+        # stream), 1 for the legacy default stream (whose handle 0 the interface disallows), else the handle
         self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 3, "strides": None,
                                          "stream": None if stream is None else (stream if stream != 0 else 1)}
 
 
-class AccountsView:
+class OpenOrdersView(_DeviceTableView):
+    """One table of ``ManyBookEnv.open_orders_views()`` where it lives, for ``torch.as_tensor(view, device="cuda")``, cupy
+    and anything else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
+
+
+class AccountsView(_DeviceTableView):
     """``ManyBookEnv.accounts_view()``: the accounts table where it lives, for ``torch.as_tensor(view, device="cuda")``,
     cupy and anything else that reads ``__cuda_array_interface__``.  Keeps its env (and so the memory) alive."""
 
     def __init__(self, env, ptr: int, shape, stream: Optional[int]):
-        self._env = env
-        # version 3 of the interface: `stream` is the stream the data is written on - None when unknown (an env on its own
-        # stream), 1 for the legacy default stream (whose handle 0 the interface disallows), else the handle
-        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": "<i8", "data": (int(ptr), False),
-                                         "version": 3, "strides": None,
-                                         "stream": None if stream is None else (stream if stream != 0 else 1)}
+        super().__init__(env, ptr, shape, "<i8", stream)
 
 
 class TradeBarsView(AccountsView):
@@ -1665,7 +1622,7 @@ class ManyMarketEnv(ManyBookEnv):
         """``retune_random_agents`` per market, for the table ``set_random_market_agents_per_market`` installed: ``rows[m]``
         as that call takes it (the groups' assets stay what was installed) or a device object of the raw rows
         ``[n_markets, n_groups]``; ``mask`` / ``status`` hold one element / pair per market."""
-        if not (hasattr(rows, "data_ptr") or hasattr(rows, "__cuda_array_interface__") or isinstance(rows, np.ndarray)):
+        if not (_is_dev(rows) or isinstance(rows, np.ndarray)):
             rows = [[(g.as_tuple() if isinstance(g, RandomMarketAgents) else tuple(g))[1:] for g in row] for row in rows]
         self._retune(False, rows, mask, status, sync, lambda t: _agents_table(t, self.n_markets, lambda g: g))
 
@@ -1673,7 +1630,7 @@ class ManyMarketEnv(ManyBookEnv):
         """``retune_agents`` per market, for the table ``set_market_agents_per_market`` installed: ``rows[m]`` is market
         ``m``'s ``[(asset, member), ...]`` list (the members' assets stay what was installed) or a device object of the raw
         rows ``[n_markets, n_members]``."""
-        if not (hasattr(rows, "data_ptr") or hasattr(rows, "__cuda_array_interface__") or isinstance(rows, np.ndarray)):
+        if not (_is_dev(rows) or isinstance(rows, np.ndarray)):
             rows = [[m for _, m in r] for r in rows]
         self._retune(True, rows, mask, status, sync, lambda t: _members_rows(t, self.n_markets))
 

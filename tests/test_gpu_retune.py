@@ -12,8 +12,8 @@ of chosen units of the installed per-unit table rewritten in place on the device
 4. the oracle's one in-place assignment (AgentSet.set_noise_prob) under bk_run and on the ingress path;
 5. cross-path: bk_run against update_agents + step given the same retune;
 6. refusals inside the kernel: status pairs and the counter are tests/retune_model.py's, refused units keep their rows;
-7. markets; 8. with the masked reset, in one stream order, and across a checkpoint; 9. no wait on the device path;
-10. the API's refusals.
+7. markets; 8. with the masked reset, in one stream order, and across a checkpoint; 8b. the host entry's staging made and
+grown, against the device entry; 9. no wait on the device path; 10. the API's refusals.
 The expected sides share no text with the kernel."""
 import numpy as np
 import pytest
@@ -985,6 +985,31 @@ def test_ingress_reset_and_retune_in_one_stream_order(bk, torch):
         assert np.array_equal(h[:, b], hr[:, b]) and env.rng_state(b) == ref.rng_state(b), b
     env.close()
     ref.close()
+
+
+# ------------------------------------------------------------------ 8b. the host entry's staging, made and then grown
+def test_host_and_device_entries_agree_as_the_table_widens(bk, torch):
+    """Two envs of one seed, retuned with the same rows - one through the host entry, one through the device entry - for a
+    one-group table and then, installed again, for a two-group one: the host entry's staging is made by the first retune and
+    replaced by a larger one at the second, and both times the kernel reads from it what the device entry is handed."""
+    B = 4
+    narrow = (group_rows(B, 11, sizes=(20,)), group_rows(B, 12, sizes=(20,)))
+    wide = (group_rows(B, 13, sizes=(20, 15)), group_rows(B, 14, sizes=(20, 15)))
+    host, device, control = (book_env(bk, B=B, pool=64) for _ in range(3))
+    for installed, rows in (narrow, wide):
+        tab = group_table(bk, rows)
+        for env in (host, device, control):
+            env.set_random_agents_per_book(installed)
+        host.retune_random_agents(tab)
+        device.retune_random_agents(raw(torch, tab))
+    for env in (host, device, control):
+        env.run(3)
+    assert host.retune_rejected() == 0 and device.retune_rejected() == 0
+    assert np.array_equal(host.level2(), device.level2())
+    assert [host.rng_state(b) for b in range(B)] == [device.rng_state(b) for b in range(B)]
+    assert not np.array_equal(host.level2(), control.level2())  # (the retunes took effect: `control` runs the installed rows)
+    for env in (host, device, control):
+        env.close()
 
 
 # ------------------------------------------------------------------ 9. no wait on the device path
