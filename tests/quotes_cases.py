@@ -6,10 +6,12 @@ format), then the grid tests/quotes_model.py::expand makes from open_orders_mode
 and the step's quote table, both through ingress_support.apply_oracle, then step().  A step's quotes name ids that rest on the
 expected side, so it runs first; what happened is counted while it runs."""
 import numpy as np
+import pytest
 
 import open_orders_model as OM
+import oracle_parity as P
 import quotes_model as QM
-from ingress_support import SEED, STEP, apply_oracle, thin_flow
+from ingress_support import SEED, STEP, apply_oracle, dev, submit, thin_flow
 
 KEEP = QM.KEEP
 NO_ID = 0xFFFFFFFFFFFFFFFF
@@ -174,3 +176,69 @@ def assert_busy(plan, pool):
         assert plan.count[w] > 0, (w, plan.count)
     assert plan.partial_keepers > 0 and plan.beyond_depth > 0 and plan.unlisted_stay > 0, vars(plan)
     assert plan.most_live < pool, (plan.most_live, pool)
+
+
+# ------------------------------------------------------------------------------------------------ on the device
+UNTOUCHED = 7  # what out_ids and status hold before a call: neither an id of these runs, nor u64::MAX, nor a status code
+
+
+def outputs(torch, plan):
+    return (torch.full((plan.B, plan.NT, 2), UNTOUCHED, dtype=torch.int64, device="cuda"),
+            torch.full((plan.B, 2), UNTOUCHED, dtype=torch.int32, device="cuda"))
+
+
+def quotes_dev(torch, quotes):
+    return dev(torch, np.ascontiguousarray(quotes, dtype=np.uint32).view(np.int32))
+
+
+# failures, against a twin env that takes the model's grid through submit_instructions_device
+def twin_step(torch, twin, plan, s):
+    """step s on the twin env: the same background, then the model's grid through submit_instructions_device"""
+    bg, _, (off, ins), _ = plan.steps[s]
+    if bg is not None:
+        submit(torch, twin, *bg)
+    n = len(ins[0])
+    ids = torch.full((n,), UNTOUCHED, dtype=torch.int64, device="cuda")
+    status = torch.full((plan.B, 2), UNTOUCHED, dtype=torch.int32, device="cuda")
+    twin.submit_instructions_device(dev(torch, off), *[dev(torch, x) for x in ins], out_ids=ids, status=status)
+    twin.step(sync=False)
+    new_ids = ids.cpu().numpy().view(np.uint64).reshape(plan.B, plan.NT, plan.G)[:, :, plan.depth:]
+    return new_ids, status.cpu().numpy()
+
+
+def failing_step(torch, env, twin, plan, quotes, stop, code, raises):
+    """One more step with `quotes`, which book `stop[0]` stops at grid position `stop[1]` with `code`: the expected side
+    applies that book's grid up to there, both device envs must report the same status and ids, and equal the oracle;
+    check_status raises `raises` = (exception, message) once the call is queued."""
+    quotes = np.ascontiguousarray(quotes, dtype=np.uint32)
+    entries = plan.entries()
+    grids = [QM.expand(e, q.tolist(), plan.depth) for e, q in zip(entries, quotes)]
+    want_ids = []
+    for b, (r, g) in enumerate(zip(plan.refs, grids)):
+        n = stop[1] if b == stop[0] else len(g[0])
+        ids = plan.expected_ids(b, tuple(np.where(np.arange(len(x)) < n, x, 0) for x in g))
+        if b == stop[0]:  # from the failing element on, out_ids is not written
+            for i in range(n, len(g[0])):
+                t, at = divmod(i, plan.G)
+                if at >= plan.depth:
+                    ids[t, at - plan.depth] = UNTOUCHED
+        want_ids.append(ids)
+        if b == stop[0] and code == 1:
+            with pytest.raises(ValueError):  # the oracle stops at the bad price, as the reference does
+                apply_oracle(r, 0, len(g[0]), g)
+        else:
+            apply_oracle(r, 0, n, g)
+        r.step()
+    plan.steps.append((None, quotes, join(grids), np.stack(want_ids)))
+    s = len(plan.steps) - 1
+    ids, status = outputs(torch, plan)
+    with pytest.raises(raises[0], match=raises[1]):
+        env.submit_quotes(quotes_dev(torch, quotes), ids, status, check_status=True)
+    env.step(sync=False)
+    got_ids, got_status = ids.cpu().numpy().view(np.uint64), status.cpu().numpy()
+    twin_ids, twin_status = twin_step(torch, twin, plan, s)
+    want_status = [[code, stop[1]] if b == stop[0] else [0, plan.NT * plan.G] for b in range(plan.B)]
+    assert got_status.tolist() == want_status and twin_status.tolist() == want_status, (got_status.tolist(), twin_status.tolist())
+    P.same_array(got_ids, twin_ids, "failing step", "out_ids against the twin's")
+    P.same_array(got_ids, np.stack(want_ids), "failing step", "out_ids against the expected side's")
+    return got_ids
