@@ -164,6 +164,60 @@ def series_moments(rows) -> np.ndarray:
     return out
 
 
+# bk_lag_row: one book's row of one lag of the lag table (ManyBookEnv.lags), 10 words of 8 bytes
+LAG_FIELDS = ("n_pairs", "sum_dd", "sum_abs_dd", "n_h", "sum_h", "sum_abs_h", "sum_h2", "sum_h4_lo", "sum_h4_hi", "max_abs_h")
+LAG_SIGNED = ("sum_dd", "sum_h")
+LAG_DTYPE = np.dtype(
+    {"names": list(LAG_FIELDS), "formats": ["<i8" if n in LAG_SIGNED else "<u8" for n in LAG_FIELDS],
+     "offsets": [8 * i for i in range(10)], "itemsize": 80})
+MAX_LAGS = 64
+
+LAG_MOMENTS_DTYPE = np.dtype([(n, "<f8") for n in ("acf_return", "acf_abs_return", "var_h", "kurtosis_h", "variance_ratio")])
+
+
+def lag_moments(rows) -> np.ndarray:
+    """``LAG_DTYPE`` rows ``[..., n_lags]`` (``ManyBookEnv.lags()``) -> float64 moments of the same shape
+    (``LAG_MOMENTS_DTYPE``), computed exactly in Python integers and rounded once.  The last axis is the lag: index ``k - 1``
+    is lag / span ``k``.  With ``d`` the step-to-step change of TWICE the mid and ``h`` its change over ``k`` steps:
+
+    ``acf_return[k]`` = (sum_dd / n_pairs - mu^2) / var, with ``mu`` and ``var`` of ``d`` from row 0's span words (the
+    moments of all returns for both factors, as ``series_moments``' ``acf1_return``, which ``k = 1`` equals bit for bit);
+    ``acf_abs_return[k]`` the same of ``|d|``; ``var_h[k]`` = (sum_h2 / n_h - (sum_h / n_h)^2) / 4, the variance of the
+    mid's change over ``k`` steps; ``kurtosis_h[k]`` = n_h sum_h4 / sum_h2^2 - 3, the excess kurtosis ABOUT ZERO;
+    ``variance_ratio[k]`` = var_h[k] / (k var_h[1]).  A division by a zero count or a zero variance gives NaN.  The words
+    are read as they are: a sum that has wrapped modulo 2^64 is not detected."""
+    from fractions import Fraction as F
+
+    rows = np.asarray(rows)
+    if rows.dtype != LAG_DTYPE or rows.ndim < 1:
+        raise ValueError("lag_moments needs LAG_DTYPE rows of shape [..., n_lags]")
+    out = np.full(rows.shape, np.nan, dtype=LAG_MOMENTS_DTYPE)
+    K = rows.shape[-1]
+
+    def put(o, name, x):
+        o[name] = np.nan if x is None else float(x)
+
+    for table, o in zip(rows.reshape(-1, K), out.reshape(-1, K)):
+        w = [{n: int(r[n]) for n in LAG_FIELDS} for r in table]
+        nr = w[0]["n_h"]  # row 0's spans are the returns themselves
+        md = F(w[0]["sum_h"], nr) if nr else None
+        mabs = F(w[0]["sum_abs_h"], nr) if nr else None
+        var_d = None if md is None else F(w[0]["sum_h2"], nr) - md * md
+        var_abs = None if mabs is None else F(w[0]["sum_h2"], nr) - mabs * mabs
+        var_h = []
+        for r in w:
+            mh = F(r["sum_h"], r["n_h"]) if r["n_h"] else None
+            var_h.append(None if mh is None else (F(r["sum_h2"], r["n_h"]) - mh * mh) / 4)
+        for k, r in enumerate(w):
+            npair, h4 = r["n_pairs"], r["sum_h4_lo"] | (r["sum_h4_hi"] << 64)
+            put(o[k], "acf_return", None if not npair or not var_d else (F(r["sum_dd"], npair) - md * md) / var_d)
+            put(o[k], "acf_abs_return", None if not npair or not var_abs else (F(r["sum_abs_dd"], npair) - mabs * mabs) / var_abs)
+            put(o[k], "var_h", var_h[k])
+            put(o[k], "kurtosis_h", None if not r["sum_h2"] else F(r["n_h"] * h4, r["sum_h2"] ** 2) - 3)
+            put(o[k], "variance_ratio", None if var_h[k] is None or not var_h[0] else var_h[k] / ((k + 1) * var_h[0]))
+    return out
+
+
 # bk_open_summary / bk_open_order: one trader's rows of the open-order tables (ManyBookEnv.open_orders)
 OPEN_SUMMARY_DTYPE = np.dtype(
     {"names": ["bid_vol", "ask_vol", "n_bid", "n_ask", "best_bid", "best_ask"], "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
@@ -340,6 +394,12 @@ SIGNATURES = {
     "bk_series_clear_device": (_i32, [_vp, _vp]),
     "bk_series_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_series": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_lags_enable": (_i32, [_vp, _u32]),
+    "bk_lags_fold": (_i32, [_vp]),
+    "bk_lags_clear": (_i32, [_vp, _vp]),
+    "bk_lags_clear_device": (_i32, [_vp, _vp]),
+    "bk_lags_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_lags": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -59,6 +59,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "quotes_ingress.hpp"
 #include "retune.hpp"
 #include "stamp_compact.hpp"
+#include "lags.hpp"
 
 using namespace bkd;
 
@@ -77,6 +78,10 @@ static_assert(sizeof(bk_series_row) == 192 && sizeof(bk_series_row) == series::R
                   sizeof(bk_series_row) == series::ROW_WORDS * 8 && offsetof(bk_series_row, carry_m) == series::CARRY_M * 8 &&
                   offsetof(bk_series_row, min_m) == series::MIN_M * 8 && offsetof(bk_series_row, sum_d4_lo) == series::SUM_D4_LO * 8,
               "bk_series_row layout (series_fold.hpp)");
+static_assert(sizeof(bk_lag_row) == 80 && sizeof(bk_lag_row) == lags::ROW_VECS * sizeof(bk_u32x4) &&
+                  sizeof(bk_lag_row) == lags::ROW_WORDS * 8 && offsetof(bk_lag_row, n_h) == lags::N_H * 8 &&
+                  offsetof(bk_lag_row, sum_h4_lo) == lags::SUM_H4_LO * 8 && offsetof(bk_lag_row, max_abs_h) == lags::MAX_ABS_H * 8,
+              "bk_lag_row layout (lag_fold.hpp)");
 static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
@@ -250,6 +255,14 @@ struct bk_env {
   DevBuf<uint8_t> series_mask;  // bk_series_clear: device staging of the host mask [n_books]
   uint64_t series_seen = 0;     // steps below it are folded (a host integer, as steps_done)
   bool series = false;
+  // bk_lags_enable: n_lags rows per book [n_books][n_lags] of 80 B and the carry [n_books][n_lags + 1], folded from the
+  // history ring (lags.hpp)
+  DevBuf<bk_u32x4> lag_rows;
+  DevBuf<uint64_t> lag_carry;
+  DevBuf<uint8_t> lags_mask;  // bk_lags_clear: device staging of the host mask [n_books]
+  uint64_t lags_seen = 0;     // steps below it are folded (a host integer, as steps_done)
+  uint32_t n_lags = 0;
+  bool lags = false;
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -2806,6 +2819,63 @@ static int series_fold_outstanding(bk_env* env) {
   return BK_OK;
 }
 
+// ------------------------------------------------------------------ per-book lag table of the level-2 history
+// No counterpart in the reference.  lag_rows[n_books][n_lags] rows of 10 u64 words and lag_carry[n_books][n_lags + 1], folded
+// from the history ring by lags::k_fold on the env's stream when bk_lags_fold, a masked clear or a reset asks; lags.hpp,
+// DESIGN.md 2.24.
+// steps [lags_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
+static void launch_lags_fold(bk_env* env, uint64_t n) {
+  lags::FoldArgs g{};
+  g.hist = env->hist.p;
+  g.hist_cap = env->cfg.history_capacity;
+  g.n_books = env->cfg.n_books;
+  g.W = env->W;
+  g.slot0 = static_cast<uint32_t>(env->lags_seen % env->cfg.history_capacity);
+  g.n = static_cast<uint32_t>(n);
+  g.K = env->n_lags;
+  g.rows = env->lag_rows.p;
+  g.carry = env->lag_carry.p;
+  launch_wave_per_book(env, lags::k_fold, lags::FOLD_WAVES, g);
+}
+
+// rows and carry of the masked books (one mask byte per M books; nullptr: every book) -> 0, or only their carry
+static void launch_lags_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
+  lags::ClearArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.n_books = env->cfg.n_books;
+  g.K = env->n_lags;
+  g.carry_only = carry_only ? 1u : 0u;
+  g.rows = env->lag_rows.p;
+  g.carry = env->lag_carry.p;
+  launch_wave_per_book(env, lags::k_clear, lags::FOLD_WAVES, g);
+}
+
+// a step of [lags_seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
+static int lags_lost_check(bk_env* env) {
+  const uint64_t first = hist_first(env);
+  if (env->lags_seen >= first) return BK_OK;
+  char msg[224];
+  std::snprintf(msg, sizeof msg,
+                "%llu step(s) of the lag table were lost: steps [%llu, %llu) are no longer retained by the history ring "
+                "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
+                "bk_lags_clear(env, NULL) starts again",
+                static_cast<unsigned long long>(first - env->lags_seen), static_cast<unsigned long long>(env->lags_seen),
+                static_cast<unsigned long long>(first));
+  return fail(BK_INVALID_ARGUMENT, msg);
+}
+
+// fold what is outstanding (nothing: no launch); lost steps refuse, rows, carry and cursor unchanged
+static int lags_fold_outstanding(bk_env* env) {
+  if (int rc = lags_lost_check(env)) return rc;
+  if (env->lags_seen == env->steps_done) return BK_OK;
+  if (int rc = use_device(env)) return rc;
+  launch_lags_fold(env, env->steps_done - env->lags_seen);
+  HIPCHK(hipGetLastError());
+  env->lags_seen = env->steps_done;
+  return BK_OK;
+}
+
 static int read_hdr(bk_env* env, uint32_t book, int first_dw, int n_dw, uint32_t* out) {
   if (int rc = use_device(env)) return rc;
   HIPCHK(hipStreamSynchronize(env->stream));
@@ -2957,6 +3027,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
                                      "its trade records would pass as the next step's");
   if (env->series)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with series moments (bk_series_enable) is not supported: "
+                                     "the book's next record would pass as the successor of the replaced book's last");
+  if (env->lags)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a lag table (bk_lags_enable) is not supported: "
                                      "the book's next record would pass as the successor of the replaced book's last");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
@@ -3444,6 +3517,11 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
     HIPCHK(hipGetLastError());
     env->series_seen = env->steps_done;
   }
+  if (env->lags) {  // ... and so is the lag table: rows and carry start again at the restored step
+    launch_lags_clear(env, nullptr, 1, false);
+    HIPCHK(hipGetLastError());
+    env->lags_seen = env->steps_done;
+  }
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
 }
@@ -3581,9 +3659,17 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
 // whose save kept `stamp_bound`.
 static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bound, const uint8_t* mask_dev,
                             const uint64_t* seeds_dev) {
+  if (env->lags) {  // the lag table's lost steps refuse the reset before the series launches anything
+    if (int rc = lags_lost_check(env)) return rc;
+  }
   if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
     if (int rc = series_fold_outstanding(env)) return rc;
     launch_series_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->lags) {  // the lag table: fold the old episode's steps, then cut the carry - no span or pair reaches over the reset
+    if (int rc = lags_fold_outstanding(env)) return rc;
+    launch_lags_clear(env, mask_dev, env->M, true);
     HIPCHK(hipGetLastError());
   }
   launch_reset_books(env, snap, mask_dev, seeds_dev);
@@ -4021,6 +4107,79 @@ int bk_series_device_ptr(bk_env* env, void** out) {
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out) {
   if (int rc = series_ok(env)) return rc;
   return get_book_rows(env, first_book, n_books, {{env->series_rows.p, sizeof(bk_series_row), out}});
+}
+
+// ------------------------------------------------------------------ per-book lag table: the entries
+// (the launches and the fold of what is outstanding stand with the history ring above)
+int bk_lags_enable(bk_env* env, uint32_t n_lags) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->cfg.history_capacity)
+    return fail(BK_INVALID_ARGUMENT, "the lag table is folded from the level-2 history ring: history_capacity must be > 0");
+  if (n_lags == 0 || n_lags > lags::MAX_LAGS) return fail(BK_INVALID_ARGUMENT, "n_lags must be in 1..64");
+  if (env->lags) return fail(BK_INVALID_ARGUMENT, "the lag table is already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<uint64_t> carry;
+  HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * n_lags * lags::ROW_VECS));
+  HIPCHK(carry.alloc(static_cast<size_t>(env->cfg.n_books) * (n_lags + 1u)));
+  env->lag_rows.swap(rows);
+  env->lag_carry.swap(carry);
+  env->n_lags = n_lags;
+  env->lags = true;
+  env->lags_seen = env->steps_done;
+  launch_lags_clear(env, nullptr, 1, false);
+  const hipError_t launched = hipGetLastError();
+  if (launched != hipSuccess) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
+    env->lag_rows.swap(rows);
+    env->lag_carry.swap(carry);
+    env->n_lags = 0;
+    env->lags = false;
+    return fail(BK_HIP_ERROR, std::string("bk_lags_enable: the clear could not be launched: ") + hipGetErrorString(launched));
+  }
+  return BK_OK;
+}
+
+static int lags_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->lags) return fail(BK_INVALID_ARGUMENT, "this env has no lag table: call bk_lags_enable first");
+  return BK_OK;
+}
+
+int bk_lags_fold(bk_env* env) {
+  if (int rc = lags_ok(env)) return rc;
+  return lags_fold_outstanding(env);
+}
+
+int bk_lags_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = lags_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  if (mask_dev) {
+    if (int rc = lags_fold_outstanding(env)) return rc;
+  } else {
+    env->lags_seen = env->steps_done;  // every row starts again here: nothing is folded, lost steps are forgotten
+  }
+  launch_lags_clear(env, mask_dev, 1, false);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_lags_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = lags_ok(env)) return rc;
+  if (mask_host)
+    if (int rc = lags_lost_check(env)) return rc;  // (refused before the mask is staged)
+  return clear_from_host(env, mask_host, env->lags_mask, bk_lags_clear_device);
+}
+
+int bk_lags_device_ptr(bk_env* env, void** out) {
+  if (int rc = lags_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->lag_rows.p;
+  return BK_OK;
+}
+
+int bk_get_lags(bk_env* env, uint32_t first_book, uint32_t n_books, bk_lag_row* out) {
+  if (int rc = lags_ok(env)) return rc;
+  return get_book_rows(env, first_book, n_books, {{env->lag_rows.p, env->n_lags * sizeof(bk_lag_row), out}});
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env

@@ -188,6 +188,8 @@ class ManyBookEnv:
         # the device-resident tables this env has enabled (0 / None / False: not enabled)
         self._n_traders = 0       # enable_accounts
         self._bars_window = 0     # enable_trade_bars
+        self._series = False      # enable_series
+        self._n_lags = 0          # enable_lags
         self._open_shape = None   # enable_open_orders: (n_traders, depth)
         self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
         if stream is not None:
@@ -1307,6 +1309,7 @@ class ManyBookEnv:
         ``series()`` is read.  Needs ``history_capacity > 0``; works with ``run`` on every pipeline, ``step``, the device
         ingress and markets.  Steps before the call are not counted.  The reference has no counterpart."""
         check(self._L.bk_series_enable(self._h))
+        self._series = True
 
     def fold_series(self, sync: bool = False):
         """``bk_series_fold``: queue the fold of every step run since the last fold (no new step: no launch).  Raises if
@@ -1345,17 +1348,78 @@ class ManyBookEnv:
     def run_series(self, n_steps: int, chunk: Optional[int] = None):
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
         ``history_capacity``) until ``n_steps`` are run: the way to run more steps than the ring holds.  Nothing waits
-        between the chunks, or at the end."""
+        between the chunks, or at the end.  With ``enable_lags`` the lag table is folded after every chunk too - and alone
+        if only it is enabled."""
         c = self.history_capacity if chunk is None else int(chunk)
         if not 1 <= c <= self.history_capacity:
             raise ValueError("run_series needs 1 <= chunk <= history_capacity")
-        self.fold_series()  # (steps run before the call are not pushed out of the ring by the first chunk)
+        folds = [self.fold_lags] if self._n_lags else []
+        if self._series or not folds:  # (neither table: fold_series raises the library's refusal, as ever)
+            folds.insert(0, self.fold_series)
+        for fold in folds:
+            fold()  # (steps run before the call are not pushed out of the ring by the first chunk)
         left = int(n_steps)
         while left > 0:
             n = min(c, left)
             self.run(n, sync=False)
-            self.fold_series()
+            for fold in folds:
+                fold()
             left -= n
+
+    # ------------------------------------------------------------ per-book lag table of the level-2 history
+    LAG_DTYPE = _lib.LAG_DTYPE
+
+    def enable_lags(self, n_lags: int):
+        """``bk_lags_enable``: keep ``n_lags`` rows (1 .. 64) of integer sums per book in device memory, row ``k - 1`` for
+        lag / span ``k``: the count and sums of ``d_s * d_{s-k}`` and ``|d_s| * |d_{s-k}|`` (``d`` the step-to-step change
+        of twice the mid), and count, sum, absolute sum, second and fourth power and maximum of the change over ``k`` steps
+        (``LAG_DTYPE``; include/bourse_amd.h states what one record adds).  ``fold_lags()`` folds the steps run since the
+        last fold from the history ring, on the env's stream; nothing leaves the device until ``lags()`` is read.  Needs
+        ``history_capacity > 0``; works with ``run`` on every pipeline, ``step``, the device ingress and markets, with or
+        without ``enable_series``.  Steps before the call are not counted.  The reference has no counterpart."""
+        if not 0 <= int(n_lags) <= 0xFFFFFFFF:
+            raise ValueError("n_lags out of range")
+        check(self._L.bk_lags_enable(self._h, int(n_lags)))
+        self._n_lags = int(n_lags)
+
+    def _lags_count(self) -> int:
+        if not self._n_lags:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no lag table: call enable_lags (bk_lags_enable) first")
+        return self._n_lags
+
+    def fold_lags(self, sync: bool = False):
+        """``bk_lags_fold``: queue the fold of every step run since the last fold (no new step: no launch).  Raises if one
+        of them is no longer retained by the ring - more than ``history_capacity`` steps since the last fold, or
+        ``clear_history()`` - naming how many were lost; rows, carry and cursor are then unchanged and ``clear_lags()``
+        starts again."""
+        check(self._L.bk_lags_fold(self._h))
+        if sync:
+            self.sync()
+
+    def lags(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
+        shape ``[n, n_lags]`` (``LAG_DTYPE``).  Waits for the env's stream; does NOT fold."""
+        return self._book_rows(self._L.bk_get_lags, first_book, n_books, ((self._lags_count(),), _lib.LAG_DTYPE))[0]
+
+    def lags_device_ptr(self) -> int:
+        """Device address of the table, ``bk_lag_row[n_books][n_lags]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_lags_device_ptr)
+
+    def lags_view(self) -> "LagsView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, n_lags, 10)``, the
+        words in ``LAG_DTYPE``'s order (unsigned words read as int64: the same bits).  ``torch.as_tensor(env.lags_view(),
+        device="cuda")`` is a zero-copy tensor that every later fold updates; it is written on the env's stream, so read
+        it there (or after ``sync()``)."""
+        return LagsView(self, self.lags_device_ptr(), (self.n_books, self._lags_count(), 10), self._stream)
+
+    def clear_lags(self, mask=None, sync: bool = True):
+        """With a ``mask`` (one entry per BOOK): fold what is outstanding (raising as ``fold_lags`` does), then clear the
+        rows and the carry of the books with ``mask[b]`` set.  ``None``: clear everything and count from the current step
+        on without folding - the way on after lost steps.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
+        (``bk_lags_clear`` / ``bk_lags_clear_device``).  ``reset_books`` / ``reset_ingress_books`` fold and then cut only
+        the carry of the books they reset: the sums go on across episodes and no span or pair reaches over a reset."""
+        # (no check of its own in front: the library refuses an env without the table)
+        self._masked_clear(self._L.bk_lags_clear_device, self._L.bk_lags_clear, mask, sync)
 
     # ------------------------------------------------------------ open orders of an env with the device ingress
     OPEN_SUMMARY_DTYPE = _lib.OPEN_SUMMARY_DTYPE
@@ -1537,6 +1601,10 @@ class TradeBarsView(AccountsView):
 
 class SeriesView(AccountsView):
     """``ManyBookEnv.series_view()``: the table of series moments where it lives, read the same way."""
+
+
+class LagsView(AccountsView):
+    """``ManyBookEnv.lags_view()``: the lag table where it lives, read the same way."""
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):

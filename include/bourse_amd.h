@@ -807,6 +807,79 @@ int bk_series_device_ptr(bk_env* env, void** out);
  * (No counterpart in the reference.) */
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out);
 
+/* ------------------------------------------------------ per-book lag table of the level-2 history */
+/* An opt-in table lags[n_books][n_lags] in DEVICE memory, n_lags = K, 1 <= K <= 64: per book and lag k = 1 .. K the sums
+ * behind the autocorrelation of the mid's step-to-step change and of its magnitude at lag k (volatility clustering), and
+ * behind the variance and kurtosis of the change over a SPAN of k steps (aggregational Gaussianity, the variance ratio) -
+ * the multi-lag sibling of bk_series_*, folded on the env's stream from the same history ring with no host wait
+ * (bourse_amd/csrc/lags.hpp, lag_fold.hpp).  It serves every flow that writes the ring - bk_run on all
+ * pipelines, bk_step, the device ingress, markets - and touches no stepping kernel.  Neither table needs the other.  The
+ * reference has no counterpart for any of these entries.
+ *
+ * What one record adds.  Of the record of step s and book b only bid_price and ask_price are read (words 1 and 2); an empty
+ * side reads bid_price == 0 / ask_price == 0xFFFFFFFF.
+ *   two_s = bid != 0 && ask != 0xFFFFFFFF;  m_s = bid + ask (TWICE the mid, a u64);
+ *   a step in front of the table's START - the enable, a clear of that book, or a cut by a reset - is not two-sided;
+ *   r_s = two_s && two_{s-1};  d_s = m_s - m_{s-1} (signed, |d| < 2^33).
+ * Step s adds to row k - 1, for every k in 1 .. K:
+ *   SPAN k, if two_s && two_{s-k}, with h = m_s - m_{s-k} and a = |h| (only the two end points must be two-sided):
+ *                      n_h += 1, sum_h += h, sum_abs_h += a, sum_h2 += a * a, sum_h4 += a^4 (a 128-bit pair, the power
+ *                      exact modulo 2^128), max_abs_h = max(max_abs_h, a);
+ *   LAG k, if r_s && r_{s-k}:
+ *                      n_pairs += 1, sum_dd += d_s * d_{s-k} (signed), sum_abs_dd += |d_s| * |d_{s-k}|.
+ * All 64-bit words are sums modulo 2^64, sum_h4 a sum modulo 2^128; signed words are two's complement; a cleared row is all
+ * zeros.  Row 0 is by construction bk_series_row's n_pairs, sum_dd, sum_abs_dd, n_ret, sum_d, sum_abs_d, sum_d2, sum_d4 and
+ * max_abs_d over the same steps and cuts.
+ *
+ * The carry.  d_{s-k} needs m_{s-k-1}: a fold must know the K + 1 records in front of its first step, which the ring may no
+ * longer hold.  The env keeps lag_carry[n_books][K + 1] u64, an array of its own beside the table: entry j is the record of
+ * step lags_seen - 1 - j - bit 63 = two, the low bits = m - and the whole word is 0 when that step is one-sided or lies in
+ * front of the start.  So folding steps [x, y) and then [y, z) leaves the same rows and carry as one fold over [x, z), for
+ * every split. */
+typedef struct bk_lag_row { /* 80 B, five 16-byte vectors, little-endian */
+  uint64_t n_pairs;
+  int64_t sum_dd;
+  uint64_t sum_abs_dd;
+  uint64_t n_h;
+  int64_t sum_h;
+  uint64_t sum_abs_h, sum_h2, sum_h4_lo, sum_h4_hi, max_abs_h;
+} bk_lag_row;
+/* Enabling.  Accepted on any env with history_capacity > 0, at any time, once; n_lags in 1 .. 64.  Allocates the rows and
+ * the carry (arrays of their own: the state block, checkpoints and snapshots are unchanged), clears both and sets the env's
+ * step cursor lags_seen, a host integer as bk_steps_done is and independent of the series' cursor, to bk_steps_done: earlier
+ * steps are not counted.  A refusal - here and in the entries below: a null env, history_capacity == 0, n_lags outside
+ * 1 .. 64, a second call, any other entry before this one - returns BK_INVALID_ARGUMENT, leaves the env unchanged and puts
+ * the reason in bk_last_error().
+ *
+ * bk_reset_books* and bk_ingress_reset_books* on such an env first fold what is outstanding (and refuse the reset if steps
+ * were lost, see bk_lags_fold; with bk_series_enable on the same env both tables are checked before either folds), then
+ * zero only the CARRY of the books they reset (every book of a masked market): the sums go on across episodes and no span
+ * or pair reaches over a reset; clear by mask if new rows are wanted.  bk_checkpoint_load clears every row and carry and
+ * sets the cursor to the restored step count.  bk_load_book is refused.  bk_warm writes no history and restores the counter:
+ * unaffected.  An env without the table launches nothing new.  (No counterpart in the reference.) */
+int bk_lags_enable(bk_env* env, uint32_t n_lags);
+/* Queues, on the env's stream and without any host wait, the fold of steps [lags_seen, bk_steps_done) of every book; then
+ * lags_seen = bk_steps_done.  No new step: no launch.  If a step of that range is no longer retained by the ring - it
+ * wrapped (more than history_capacity steps since the last fold), or bk_clear_history was called - returns
+ * BK_INVALID_ARGUMENT with the number of lost steps in bk_last_error() and leaves rows, carry and cursor unchanged: a lost
+ * step is never silent and needs no flag bit.  bk_lags_clear with a NULL mask is the way on.  (No counterpart in the
+ * reference.) */
+int bk_lags_fold(bk_env* env);
+/* Clearing.  mask [n_books] bytes, one per BOOK.  With a mask: folds what is outstanding first (refusing as bk_lags_fold
+ * does), then clears the rows and the carry of the books b with mask[b] != 0.  NULL: clears every row and carry and sets the
+ * cursor to bk_steps_done WITHOUT folding.  From a HOST mask: staged on the env's stream and waited for, the clear itself
+ * stays asynchronous.  (No counterpart in the reference.) */
+int bk_lags_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: at most
+ * two launches on the env's stream.  (No counterpart in the reference.) */
+int bk_lags_clear_device(bk_env* env, const uint8_t* mask_dev);
+/* Device pointer of the table, bk_lag_row[n_books][n_lags], for on-device consumers; valid for the env's life, written on
+ * the env's stream.  (No counterpart in the reference.) */
+int bk_lags_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory, n_books * n_lags rows.  Waits for the env's stream; does
+ * NOT fold.  (No counterpart in the reference.) */
+int bk_get_lags(bk_env* env, uint32_t first_book, uint32_t n_books, bk_lag_row* out);
+
 /* ------------------------------------------------------ open orders of a device-ingress env */
 /* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
  * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or

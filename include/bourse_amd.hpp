@@ -342,6 +342,32 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_series_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-book lag table of the level-2 history (bk_lags_enable): n_lags rows (1 .. 64) of integer sums per book, row k - 1
+  // for lag / span k, folded on the device from the history ring (needs history_capacity > 0); no counterpart in the reference
+  void enable_lags(uint32_t n_lags) {
+    check(bk_lags_enable(h_, n_lags));
+    n_lags_ = n_lags;
+  }
+  // queue the fold of the steps run since the last fold (no host wait); throws, naming the count, if steps were lost
+  void fold_lags() { check(bk_lags_fold(h_)); }
+  // rows [n_books][n_lags] of books [first_book, first_book + n_books) (waits for the env's stream; does not fold)
+  std::vector<bk_lag_row> lags(uint32_t first_book, uint32_t n_books) {
+    std::vector<bk_lag_row> rows(static_cast<size_t>(n_books) * n_lags_);
+    check(bk_get_lags(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<bk_lag_row> lags() { return lags(0, n_books_); }
+  // the table in device memory, bk_lag_row[n_books][n_lags]
+  bk_lag_row* lags_device_ptr() {
+    void* p = nullptr;
+    check(bk_lags_device_ptr(h_, &p));
+    return static_cast<bk_lag_row*>(p);
+  }
+  // a mask (one byte per book): fold, then clear those books' rows and carry; an empty mask: clear all without folding
+  void clear_lags(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_lags_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
   // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
   void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
@@ -401,7 +427,7 @@ class ManyEnv {
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
