@@ -218,6 +218,62 @@ def lag_moments(rows) -> np.ndarray:
     return out
 
 
+# bk_bins_config: the configuration of the bin table (ManyBookEnv.enable_bins), nine u32
+BINS_CONFIG_DTYPE = np.dtype(
+    {"names": ["n_bins", "n_spans", "spans", "ret_width", "spread_width", "vol_width"],
+     "formats": ["<u4", "<u4", ("<u4", (4,)), "<u4", "<u4", "<u4"], "offsets": [0, 4, 8, 24, 28, 32], "itemsize": 36})
+
+def _bins_cfg(cfg):
+    """(n_bins, spans, ret_width, spread_width, vol_width) of a ``BINS_CONFIG_DTYPE`` record or of a mapping with its names"""
+    names = cfg.dtype.names if getattr(cfg, "dtype", None) is not None else tuple(cfg)
+    spans = [int(k) for k in np.asarray(cfg["spans"]).reshape(-1)]
+    if "n_spans" in names:  # (the record's four slots: only the first n_spans are used)
+        spans = spans[:int(cfg["n_spans"])]
+    return int(cfg["n_bins"]), tuple(spans), int(cfg["ret_width"]), int(cfg["spread_width"]), int(cfg["vol_width"])
+
+
+def bin_edges(cfg) -> np.ndarray:
+    """The LOWER edges of the bins of every channel of a bin table, float64 ``[n_spans + 2, n_bins]``; ``cfg`` is
+    ``ManyBookEnv.bins_config()`` (a ``BINS_CONFIG_DTYPE`` record) or a mapping with ``n_bins``, ``spans``, ``ret_width``,
+    ``spread_width`` and ``vol_width``.  A return channel's edges are in MID-PRICE units: bin ``i`` starts at
+    ``(i - n_bins / 2) * ret_width / 2`` (the table counts the change of twice the mid); the spread's and the volume's bin
+    ``i`` starts at ``i * width``.  Every bin is ``width`` wide (a return's ``ret_width / 2``), half-open at its upper edge;
+    the first return bin also holds everything below it and the last bin of every channel everything above."""
+    B, spans, rw, sw, vw = _bins_cfg(cfg)
+    i = np.arange(B, dtype=np.float64)
+    return np.stack([(i - B // 2) * rw / 2.0] * len(spans) + [i * float(sw), i * float(vw)])
+
+
+def bin_quantiles(counts, edges, width, q) -> np.ndarray:
+    """Quantiles of binned values: per row of ``counts [..., n_bins]`` and per ``q`` (a scalar or a sequence, each in
+    (0, 1]) the UPPER edge ``edges[i] + width`` of the first bin ``i`` at which the cumulative share of the counts reaches
+    ``q`` - so the ``inverted_cdf`` quantile of the values lies in ``[that - width, that)`` unless it was clamped into an end
+    bin.  ``edges`` are the channel's lower edges (``bin_edges(cfg)[c]``), ``width`` its bin width in the same units
+    (``ret_width / 2`` for a return channel).  Shape ``counts.shape[:-1] + np.shape(q)``; NaN where the total is zero.  The
+    counts are summed in Python integers; ``q * total`` is one float product, as ``numpy.quantile`` forms its index."""
+    counts = np.asarray(counts)
+    edges = np.asarray(edges, dtype=np.float64)
+    if counts.ndim < 1 or edges.shape != counts.shape[-1:]:
+        raise ValueError("bin_quantiles needs counts [..., n_bins] and edges [n_bins]")
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if ((qs <= 0) | (qs > 1)).any():
+        raise ValueError("bin_quantiles needs 0 < q <= 1")
+    out = np.full((int(np.prod(counts.shape[:-1], dtype=np.int64)), qs.size), np.nan)
+    for r, row in enumerate(counts.reshape(-1, counts.shape[-1])):
+        c = [int(x) for x in row]
+        total = sum(c)
+        if not total:
+            continue
+        for k, qq in enumerate(qs.reshape(-1)):
+            need, cum = float(qq) * total, 0
+            for i, x in enumerate(c):
+                cum += x
+                if cum >= need:
+                    out[r, k] = edges[i] + width
+                    break
+    return out.reshape(counts.shape[:-1] + np.shape(q))
+
+
 # bk_open_summary / bk_open_order: one trader's rows of the open-order tables (ManyBookEnv.open_orders)
 OPEN_SUMMARY_DTYPE = np.dtype(
     {"names": ["bid_vol", "ask_vol", "n_bid", "n_ask", "best_bid", "best_ask"], "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
@@ -400,6 +456,13 @@ SIGNATURES = {
     "bk_lags_clear_device": (_i32, [_vp, _vp]),
     "bk_lags_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_lags": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_bins_enable": (_i32, [_vp, _vp]),
+    "bk_bins_config_get": (_i32, [_vp, _vp]),
+    "bk_bins_fold": (_i32, [_vp]),
+    "bk_bins_clear": (_i32, [_vp, _vp]),
+    "bk_bins_clear_device": (_i32, [_vp, _vp]),
+    "bk_bins_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_bins": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

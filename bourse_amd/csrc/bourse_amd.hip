@@ -60,6 +60,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "retune.hpp"
 #include "stamp_compact.hpp"
 #include "lags.hpp"
+#include "bins.hpp"
 
 using namespace bkd;
 
@@ -82,6 +83,9 @@ static_assert(sizeof(bk_lag_row) == 80 && sizeof(bk_lag_row) == lags::ROW_VECS *
                   sizeof(bk_lag_row) == lags::ROW_WORDS * 8 && offsetof(bk_lag_row, n_h) == lags::N_H * 8 &&
                   offsetof(bk_lag_row, sum_h4_lo) == lags::SUM_H4_LO * 8 && offsetof(bk_lag_row, max_abs_h) == lags::MAX_ABS_H * 8,
               "bk_lag_row layout (lag_fold.hpp)");
+static_assert(sizeof(bk_bins_config) == 36 && offsetof(bk_bins_config, spans) == 8 && offsetof(bk_bins_config, ret_width) == 24 &&
+                  sizeof(static_cast<bk_bins_config*>(nullptr)->spans) == bins::MAX_SPANS * 4,
+              "bk_bins_config layout (bin_fold.hpp)");
 static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
@@ -263,6 +267,15 @@ struct bk_env {
   uint64_t lags_seen = 0;     // steps below it are folded (a host integer, as steps_done)
   uint32_t n_lags = 0;
   bool lags = false;
+  // bk_bins_enable: (n_spans + 2) rows of n_bins counts per book [n_books][C][B] and the carry [n_books][bins_kmax], folded
+  // from the history ring (bins.hpp)
+  DevBuf<uint64_t> bin_rows;
+  DevBuf<uint64_t> bins_carry;
+  DevBuf<uint8_t> bins_mask;  // bk_bins_clear: device staging of the host mask [n_books]
+  uint64_t bins_seen = 0;     // steps below it are folded (a host integer, as steps_done)
+  bk_bins_config bins_cfg{};
+  uint32_t bins_kmax = 0;  // the longest span
+  bool bins = false;
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -2876,6 +2889,71 @@ static int lags_fold_outstanding(bk_env* env) {
   return BK_OK;
 }
 
+// ------------------------------------------------------------------ per-book bin table of the level-2 history
+// No counterpart in the reference.  bin_rows[n_books][n_spans + 2][n_bins] u64 counts and bins_carry[n_books][bins_kmax],
+// folded from the history ring by bins::k_fold on the env's stream when bk_bins_fold, a masked clear or a reset asks;
+// bins.hpp, DESIGN.md 2.25.
+// steps [bins_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
+static void launch_bins_fold(bk_env* env, uint64_t n) {
+  const bk_bins_config& c = env->bins_cfg;
+  bins::FoldArgs g{};
+  g.hist = env->hist.p;
+  g.hist_cap = env->cfg.history_capacity;
+  g.n_books = env->cfg.n_books;
+  g.W = env->W;
+  g.slot0 = static_cast<uint32_t>(env->bins_seen % env->cfg.history_capacity);
+  g.n = static_cast<uint32_t>(n);
+  g.B = c.n_bins;
+  g.S = c.n_spans;
+  g.Kmax = env->bins_kmax;
+  g.spans = c.spans[0] | c.spans[1] << 8 | c.spans[2] << 16 | c.spans[3] << 24;
+  g.ret_width = c.ret_width, g.spread_width = c.spread_width, g.vol_width = c.vol_width;
+  g.rows = env->bin_rows.p;
+  g.carry = env->bins_carry.p;
+  // (a launch of its own: the wave-per-book helper passes no dynamic LDS)
+  hipLaunchKernelGGL(bins::k_fold, dim3((g.n_books + bins::FOLD_WAVES - 1) / bins::FOLD_WAVES), dim3(64 * bins::FOLD_WAVES),
+                     bins::fold_lds_bytes(g.S, g.B), env->stream, g);
+}
+
+// counts and carry of the masked books (one mask byte per M books; nullptr: every book) -> 0, or only their carry
+static void launch_bins_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
+  bins::ClearArgs g{};
+  g.mask = mask_dev;
+  g.M = M;
+  g.n_books = env->cfg.n_books;
+  g.CB = (env->bins_cfg.n_spans + 2u) * env->bins_cfg.n_bins;
+  g.Kmax = env->bins_kmax;
+  g.carry_only = carry_only ? 1u : 0u;
+  g.rows = env->bin_rows.p;
+  g.carry = env->bins_carry.p;
+  launch_wave_per_book(env, bins::k_clear, bins::FOLD_WAVES, g);
+}
+
+// a step of [bins_seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
+static int bins_lost_check(bk_env* env) {
+  const uint64_t first = hist_first(env);
+  if (env->bins_seen >= first) return BK_OK;
+  char msg[224];
+  std::snprintf(msg, sizeof msg,
+                "%llu step(s) of the bin table were lost: steps [%llu, %llu) are no longer retained by the history ring "
+                "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
+                "bk_bins_clear(env, NULL) starts again",
+                static_cast<unsigned long long>(first - env->bins_seen), static_cast<unsigned long long>(env->bins_seen),
+                static_cast<unsigned long long>(first));
+  return fail(BK_INVALID_ARGUMENT, msg);
+}
+
+// fold what is outstanding (nothing: no launch); lost steps refuse, table, carry and cursor unchanged
+static int bins_fold_outstanding(bk_env* env) {
+  if (int rc = bins_lost_check(env)) return rc;
+  if (env->bins_seen == env->steps_done) return BK_OK;
+  if (int rc = use_device(env)) return rc;
+  launch_bins_fold(env, env->steps_done - env->bins_seen);
+  HIPCHK(hipGetLastError());
+  env->bins_seen = env->steps_done;
+  return BK_OK;
+}
+
 static int read_hdr(bk_env* env, uint32_t book, int first_dw, int n_dw, uint32_t* out) {
   if (int rc = use_device(env)) return rc;
   HIPCHK(hipStreamSynchronize(env->stream));
@@ -3030,6 +3108,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
                                      "the book's next record would pass as the successor of the replaced book's last");
   if (env->lags)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a lag table (bk_lags_enable) is not supported: "
+                                     "the book's next record would pass as the successor of the replaced book's last");
+  if (env->bins)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a bin table (bk_bins_enable) is not supported: "
                                      "the book's next record would pass as the successor of the replaced book's last");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
@@ -3522,6 +3603,11 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
     HIPCHK(hipGetLastError());
     env->lags_seen = env->steps_done;
   }
+  if (env->bins) {  // ... and the bin table: counts and carry start again at the restored step
+    launch_bins_clear(env, nullptr, 1, false);
+    HIPCHK(hipGetLastError());
+    env->bins_seen = env->steps_done;
+  }
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
 }
@@ -3659,6 +3745,9 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
 // whose save kept `stamp_bound`.
 static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bound, const uint8_t* mask_dev,
                             const uint64_t* seeds_dev) {
+  if (env->bins) {  // the bin table's lost steps refuse the reset before any table launches anything
+    if (int rc = bins_lost_check(env)) return rc;
+  }
   if (env->lags) {  // the lag table's lost steps refuse the reset before the series launches anything
     if (int rc = lags_lost_check(env)) return rc;
   }
@@ -3670,6 +3759,11 @@ static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bo
   if (env->lags) {  // the lag table: fold the old episode's steps, then cut the carry - no span or pair reaches over the reset
     if (int rc = lags_fold_outstanding(env)) return rc;
     launch_lags_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->bins) {  // the bin table: fold the old episode's steps, then cut the carry - no span reaches over the reset
+    if (int rc = bins_fold_outstanding(env)) return rc;
+    launch_bins_clear(env, mask_dev, env->M, true);
     HIPCHK(hipGetLastError());
   }
   launch_reset_books(env, snap, mask_dev, seeds_dev);
@@ -4180,6 +4274,104 @@ int bk_lags_device_ptr(bk_env* env, void** out) {
 int bk_get_lags(bk_env* env, uint32_t first_book, uint32_t n_books, bk_lag_row* out) {
   if (int rc = lags_ok(env)) return rc;
   return get_book_rows(env, first_book, n_books, {{env->lag_rows.p, env->n_lags * sizeof(bk_lag_row), out}});
+}
+
+// ------------------------------------------------------------------ per-book bin table: the entries
+// (the launches and the fold of what is outstanding stand with the history ring above)
+static const char* bins_config_fault(const bk_bins_config& c) {
+  if (c.n_bins < 2u || c.n_bins > bins::MAX_BINS || c.n_bins % 2u) return "n_bins must be even and in 2..256";
+  if (c.n_spans < 1u || c.n_spans > bins::MAX_SPANS) return "n_spans must be in 1..4";
+  for (uint32_t j = 0; j < c.n_spans; ++j)
+    if (c.spans[j] < 1u || c.spans[j] > bins::MAX_SPAN) return "every used span must be in 1..64";
+  if (!c.ret_width || !c.spread_width || !c.vol_width) return "ret_width, spread_width and vol_width must be >= 1";
+  return nullptr;
+}
+
+int bk_bins_enable(bk_env* env, const bk_bins_config* cfg) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!cfg) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (!env->cfg.history_capacity)
+    return fail(BK_INVALID_ARGUMENT, "the bin table is folded from the level-2 history ring: history_capacity must be > 0");
+  if (const char* why = bins_config_fault(*cfg)) return fail(BK_INVALID_ARGUMENT, why);
+  if (env->bins) return fail(BK_INVALID_ARGUMENT, "the bin table is already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  bk_bins_config c = *cfg;
+  uint32_t kmax = 0;
+  for (uint32_t j = 0; j < bins::MAX_SPANS; ++j) {
+    if (j >= c.n_spans) c.spans[j] = 0u;
+    kmax = std::max(kmax, c.spans[j]);
+  }
+  DevBuf<uint64_t> rows, carry;
+  HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * (c.n_spans + 2u) * c.n_bins));
+  HIPCHK(carry.alloc(static_cast<size_t>(env->cfg.n_books) * kmax));
+  env->bin_rows.swap(rows);
+  env->bins_carry.swap(carry);
+  env->bins_cfg = c;
+  env->bins_kmax = kmax;
+  env->bins = true;
+  env->bins_seen = env->steps_done;
+  launch_bins_clear(env, nullptr, 1, false);
+  const hipError_t launched = hipGetLastError();
+  if (launched != hipSuccess) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
+    env->bin_rows.swap(rows);
+    env->bins_carry.swap(carry);
+    env->bins_cfg = bk_bins_config{};
+    env->bins_kmax = 0;
+    env->bins = false;
+    return fail(BK_HIP_ERROR, std::string("bk_bins_enable: the clear could not be launched: ") + hipGetErrorString(launched));
+  }
+  return BK_OK;
+}
+
+static int bins_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->bins) return fail(BK_INVALID_ARGUMENT, "this env has no bin table: call bk_bins_enable first");
+  return BK_OK;
+}
+
+int bk_bins_config_get(bk_env* env, bk_bins_config* out) {
+  if (int rc = bins_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->bins_cfg;
+  return BK_OK;
+}
+
+int bk_bins_fold(bk_env* env) {
+  if (int rc = bins_ok(env)) return rc;
+  return bins_fold_outstanding(env);
+}
+
+int bk_bins_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = bins_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  if (mask_dev) {
+    if (int rc = bins_fold_outstanding(env)) return rc;
+  } else {
+    env->bins_seen = env->steps_done;  // every count starts again here: nothing is folded, lost steps are forgotten
+  }
+  launch_bins_clear(env, mask_dev, 1, false);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_bins_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = bins_ok(env)) return rc;
+  if (mask_host)
+    if (int rc = bins_lost_check(env)) return rc;  // (refused before the mask is staged)
+  return clear_from_host(env, mask_host, env->bins_mask, bk_bins_clear_device);
+}
+
+int bk_bins_device_ptr(bk_env* env, void** out) {
+  if (int rc = bins_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->bin_rows.p;
+  return BK_OK;
+}
+
+int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out) {
+  if (int rc = bins_ok(env)) return rc;
+  const size_t per_book = static_cast<size_t>(env->bins_cfg.n_spans + 2u) * env->bins_cfg.n_bins * sizeof(uint64_t);
+  return get_book_rows(env, first_book, n_books, {{env->bin_rows.p, per_book, out}});
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env

@@ -190,6 +190,7 @@ class ManyBookEnv:
         self._bars_window = 0     # enable_trade_bars
         self._series = False      # enable_series
         self._n_lags = 0          # enable_lags
+        self._bins_shape = None   # enable_bins: (n_spans + 2, n_bins)
         self._open_shape = None   # enable_open_orders: (n_traders, depth)
         self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
         if stream is not None:
@@ -1348,12 +1349,12 @@ class ManyBookEnv:
     def run_series(self, n_steps: int, chunk: Optional[int] = None):
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
         ``history_capacity``) until ``n_steps`` are run: the way to run more steps than the ring holds.  Nothing waits
-        between the chunks, or at the end.  With ``enable_lags`` the lag table is folded after every chunk too - and alone
-        if only it is enabled."""
+        between the chunks, or at the end.  With ``enable_lags`` / ``enable_bins`` those tables are folded after every chunk
+        too - and alone if only they are enabled."""
         c = self.history_capacity if chunk is None else int(chunk)
         if not 1 <= c <= self.history_capacity:
             raise ValueError("run_series needs 1 <= chunk <= history_capacity")
-        folds = [self.fold_lags] if self._n_lags else []
+        folds = ([self.fold_lags] if self._n_lags else []) + ([self.fold_bins] if self._bins_shape else [])
         if self._series or not folds:  # (neither table: fold_series raises the library's refusal, as ever)
             folds.insert(0, self.fold_series)
         for fold in folds:
@@ -1420,6 +1421,75 @@ class ManyBookEnv:
         the carry of the books they reset: the sums go on across episodes and no span or pair reaches over a reset."""
         # (no check of its own in front: the library refuses an env without the table)
         self._masked_clear(self._L.bk_lags_clear_device, self._L.bk_lags_clear, mask, sync)
+
+    # ------------------------------------------------------------ per-book bin table of the level-2 history
+    BINS_CONFIG_DTYPE = _lib.BINS_CONFIG_DTYPE
+
+    def enable_bins(self, spans=(1,), n_bins: int = 64, ret_width: int = 1, spread_width: int = 1, vol_width: int = 1):
+        """``bk_bins_enable``: keep ``len(spans) + 2`` rows of ``n_bins`` u64 counts per book in device memory - channel
+        ``j`` the change of twice the mid over ``spans[j]`` steps (1 .. 64 each, at most four, any order) in bins of
+        ``ret_width`` centred on zero, then the spread in bins of ``spread_width`` and the traded volume per step in bins of
+        ``vol_width``, both from zero; the end bins hold everything beyond them (include/bourse_amd.h states what one record
+        adds; ``bourse_amd.bin_edges`` gives the edges).  ``n_bins`` is even and in 2 .. 256.  ``fold_bins()`` folds the
+        steps run since the last fold from the history ring, on the env's stream; nothing leaves the device until ``bins()``
+        is read.  Needs ``history_capacity > 0``; works with ``run`` on every pipeline, ``step``, the device ingress and
+        markets, with or without ``enable_series`` / ``enable_lags``.  Steps before the call are not counted.  The reference
+        has no counterpart."""
+        spans = tuple(int(k) for k in spans)
+        slots = (spans + (0, 0, 0, 0))[:4]  # (more than four spans: the library refuses n_spans)
+        words = [int(n_bins), len(spans), *slots, int(ret_width), int(spread_width), int(vol_width)]
+        if any(not 0 <= w <= 0xFFFFFFFF for w in words + list(spans)):
+            raise ValueError("enable_bins: every value is a 32-bit unsigned integer")
+        cfg = np.array(words, dtype=np.uint32)
+        check(self._L.bk_bins_enable(self._h, cfg.ctypes.data_as(C.c_void_p)))
+        self._bins_shape = (len(spans) + 2, int(n_bins))
+
+    def _bins_dims(self) -> Tuple[int, int]:
+        if not self._bins_shape:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no bin table: call enable_bins (bk_bins_enable) first")
+        return self._bins_shape
+
+    def bins_config(self) -> np.ndarray:
+        """``bk_bins_config_get``: the configuration the table was enabled with, a ``BINS_CONFIG_DTYPE`` record (what
+        ``bourse_amd.bin_edges`` takes)."""
+        self._bins_dims()
+        cfg = np.zeros((), dtype=_lib.BINS_CONFIG_DTYPE)
+        check(self._L.bk_bins_config_get(self._h, cfg.ctypes.data_as(C.c_void_p)))
+        return cfg
+
+    def fold_bins(self, sync: bool = False):
+        """``bk_bins_fold``: queue the fold of every step run since the last fold (no new step: no launch).  Raises if one
+        of them is no longer retained by the ring - more than ``history_capacity`` steps since the last fold, or
+        ``clear_history()`` - naming how many were lost; table, carry and cursor are then unchanged and ``clear_bins()``
+        starts again."""
+        check(self._L.bk_bins_fold(self._h))
+        if sync:
+            self.sync()
+
+    def bins(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The counts of books ``[first_book, first_book + n_books)`` (default: to the last book) as a uint64 array of
+        shape ``[n, n_spans + 2, n_bins]``.  Waits for the env's stream; does NOT fold."""
+        return self._book_rows(self._L.bk_get_bins, first_book, n_books, (self._bins_dims(), np.uint64))[0]
+
+    def bins_device_ptr(self) -> int:
+        """Device address of the table, ``uint64_t[n_books][n_spans + 2][n_bins]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_bins_device_ptr)
+
+    def bins_view(self) -> "BinsView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, n_spans + 2,
+        n_bins)`` (the unsigned counts read as int64: the same bits).  ``torch.as_tensor(env.bins_view(), device="cuda")``
+        is a zero-copy tensor that every later fold updates; it is written on the env's stream, so read it there (or after
+        ``sync()``)."""
+        return BinsView(self, self.bins_device_ptr(), (self.n_books,) + self._bins_dims(), self._stream)
+
+    def clear_bins(self, mask=None, sync: bool = True):
+        """With a ``mask`` (one entry per BOOK): fold what is outstanding (raising as ``fold_bins`` does), then clear the
+        counts and the carry of the books with ``mask[b]`` set.  ``None``: clear everything and count from the current step
+        on without folding - the way on after lost steps.  ``mask`` / ``sync`` as ``clear_accounts`` takes them
+        (``bk_bins_clear`` / ``bk_bins_clear_device``).  ``reset_books`` / ``reset_ingress_books`` fold and then cut only
+        the carry of the books they reset: the counts go on across episodes and no span reaches over a reset."""
+        # (no check of its own in front: the library refuses an env without the table)
+        self._masked_clear(self._L.bk_bins_clear_device, self._L.bk_bins_clear, mask, sync)
 
     # ------------------------------------------------------------ open orders of an env with the device ingress
     OPEN_SUMMARY_DTYPE = _lib.OPEN_SUMMARY_DTYPE
@@ -1605,6 +1675,10 @@ class SeriesView(AccountsView):
 
 class LagsView(AccountsView):
     """``ManyBookEnv.lags_view()``: the lag table where it lives, read the same way."""
+
+
+class BinsView(AccountsView):
+    """``ManyBookEnv.bins_view()``: the bin table where it lives, read the same way."""
 
 
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):

@@ -880,6 +880,84 @@ int bk_lags_device_ptr(bk_env* env, void** out);
  * NOT fold.  (No counterpart in the reference.) */
 int bk_get_lags(bk_env* env, uint32_t first_book, uint32_t n_books, bk_lag_row* out);
 
+/* ------------------------------------------------------ per-book bin table of the level-2 history */
+/* An opt-in table bins[n_books][C][B] of u64 counts in DEVICE memory: per book the DISTRIBUTION of the mid's change over S
+ * spans of k_j steps, of the spread and of the traded volume per step - the tails, quantiles and the share of steps without
+ * a trade that the moments of bk_series_* and bk_lags_* do not give.  It is their third sibling, folded on the env's stream
+ * from the same history ring with no host wait (bourse_amd/csrc/bins.hpp, bin_fold.hpp).  It serves every
+ * flow that writes the ring - bk_run on all pipelines, bk_step, the device ingress, markets - and touches no stepping
+ * kernel.  None of the three tables needs another.  The reference has no counterpart for any of these entries.
+ *
+ * The configuration.  B = n_bins is even and in 2 .. 256; S = n_spans is in 1 .. 4; each used span k_j = spans[j], j < S, is
+ * in 1 .. 64, in any order, duplicates allowed (spans[j] for j >= S is ignored and read back as 0); every width is >= 1.
+ * C = S + 2 channels per book: channel j < S is the return over k_j steps, channel S the spread, channel S + 1 the traded
+ * volume.
+ *
+ * What one record adds.  Of the record of step s and book b only trade_vol, bid_price and ask_price are read (words 0 .. 2);
+ * an empty side reads bid_price == 0 / ask_price == 0xFFFFFFFF.
+ *   two_s = bid != 0 && ask != 0xFFFFFFFF;  m_s = bid + ask (TWICE the mid, a u64), as for bk_lags_*;
+ *   a step in front of the table's START - the enable, a clear of that book, or a cut by a reset - is not two-sided.
+ * Step s adds 1 to one bin of
+ *   channel j < S, if two_s && two_{s-k_j} (a one-sided step in between does not matter): with h = m_s - m_{s-k_j} (signed,
+ *                  |h| < 2^33) and q = floor(h / ret_width) - a true floor, -ceil(|h| / ret_width) below zero - the bin
+ *                  clamp(q + B / 2, 0, B - 1).  Bin i covers [(i - B/2) w, (i - B/2 + 1) w) in units of HALF a price step; the
+ *                  two end bins also hold everything beyond them ("at or below", "at or above");
+ *   channel S,     if two_s: the bin min((ask - bid) / spread_width, B - 1), the difference a wrapping u32 as
+ *                  bk_series_row's sum_spread has it;
+ *   channel S + 1, always: the bin min(trade_vol / vol_width, B - 1).
+ * Counts are sums modulo 2^64; a cleared table is all zeros.  By construction the total of channel j is bk_lag_row's n_h at
+ * span k_j, the total of channel S is bk_series_row's n_two_sided and the total of channel S + 1 its n_steps over the same
+ * steps and cuts; with ret_width == 1 and no value clamped, sum_i (i - B/2) * count_i is the lag row's sum_h.
+ *
+ * The carry.  A fold must know the Kmax = max k_j records in front of its first step, which the ring may no longer hold.  The
+ * env keeps bins_carry[n_books][Kmax] u64, an array of its own beside the table: entry i is the record of step
+ * bins_seen - 1 - i - bit 63 = two, the low bits = m - and the whole word is 0 when that step is one-sided or lies in front
+ * of the start.  So folding steps [x, y) and then [y, z) leaves the same table and carry as one fold over [x, z), for every
+ * split. */
+typedef struct bk_bins_config { /* 36 B, nine u32 */
+  uint32_t n_bins;
+  uint32_t n_spans;
+  uint32_t spans[4];
+  uint32_t ret_width, spread_width, vol_width;
+} bk_bins_config;
+/* Enabling.  Accepted on any env with history_capacity > 0, at any time, once.  Allocates the table and the carry (arrays of
+ * their own: the state block, checkpoints and snapshots are unchanged), clears both and sets the env's step cursor
+ * bins_seen, a host integer as bk_steps_done is and independent of the siblings' cursors, to bk_steps_done: earlier steps
+ * are not counted.  A refusal - here and in the entries below: a null env or config, history_capacity == 0, a configuration
+ * outside the bounds above, a second call, any other entry before this one - returns BK_INVALID_ARGUMENT, leaves the env
+ * unchanged and puts the reason in bk_last_error().
+ *
+ * bk_reset_books* and bk_ingress_reset_books* on such an env first fold what is outstanding (and refuse the reset if steps
+ * were lost, see bk_bins_fold; with bk_series_enable or bk_lags_enable on the same env every table is checked before any
+ * folds), then zero only the CARRY of the books they reset (every book of a masked market): the counts go on across episodes
+ * and no span reaches over a reset; clear by mask if a new table is wanted.  bk_checkpoint_load clears every count and carry
+ * and sets the cursor to the restored step count.  bk_load_book is refused.  bk_warm writes no history and restores the
+ * counter: unaffected.  An env without the table launches nothing new.  (No counterpart in the reference.) */
+int bk_bins_enable(bk_env* env, const bk_bins_config* cfg);
+/* The configuration the table was enabled with (spans beyond n_spans read 0).  (No counterpart in the reference.) */
+int bk_bins_config_get(bk_env* env, bk_bins_config* out);
+/* Queues, on the env's stream and without any host wait, the fold of steps [bins_seen, bk_steps_done) of every book; then
+ * bins_seen = bk_steps_done.  No new step: no launch.  If a step of that range is no longer retained by the ring - it
+ * wrapped (more than history_capacity steps since the last fold), or bk_clear_history was called - returns
+ * BK_INVALID_ARGUMENT with the number of lost steps in bk_last_error() and leaves table, carry and cursor unchanged: a lost
+ * step is never silent and needs no flag bit.  bk_bins_clear with a NULL mask is the way on.  (No counterpart in the
+ * reference.) */
+int bk_bins_fold(bk_env* env);
+/* Clearing.  mask [n_books] bytes, one per BOOK.  With a mask: folds what is outstanding first (refusing as bk_bins_fold
+ * does), then clears the counts and the carry of the books b with mask[b] != 0.  NULL: clears every count and carry and sets
+ * the cursor to bk_steps_done WITHOUT folding.  From a HOST mask: staged on the env's stream and waited for, the clear itself
+ * stays asynchronous.  (No counterpart in the reference.) */
+int bk_bins_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: at most
+ * two launches on the env's stream.  (No counterpart in the reference.) */
+int bk_bins_clear_device(bk_env* env, const uint8_t* mask_dev);
+/* Device pointer of the table, uint64_t[n_books][n_spans + 2][n_bins], for on-device consumers; valid for the env's life,
+ * written on the env's stream.  (No counterpart in the reference.) */
+int bk_bins_device_ptr(bk_env* env, void** out);
+/* Counts of books [first_book, first_book + n_books) to host memory, n_books * (n_spans + 2) * n_bins words.  Waits for the
+ * env's stream; does NOT fold.  (No counterpart in the reference.) */
+int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
+
 /* ------------------------------------------------------ open orders of a device-ingress env */
 /* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
  * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or

@@ -368,6 +368,38 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_lags_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-book bin table of the level-2 history (bk_bins_enable): n_spans + 2 rows of n_bins u64 counts per book - the change
+  // of twice the mid over each span, the spread, the traded volume - folded on the device from the history ring (needs
+  // history_capacity > 0); no counterpart in the reference
+  void enable_bins(const bk_bins_config& cfg) {
+    check(bk_bins_enable(h_, &cfg));
+    bins_per_book_ = (cfg.n_spans + 2u) * cfg.n_bins;
+  }
+  bk_bins_config bins_config() {
+    bk_bins_config cfg{};
+    check(bk_bins_config_get(h_, &cfg));
+    return cfg;
+  }
+  // queue the fold of the steps run since the last fold (no host wait); throws, naming the count, if steps were lost
+  void fold_bins() { check(bk_bins_fold(h_)); }
+  // counts [n_books][n_spans + 2][n_bins] of books [first_book, first_book + n_books) (waits for the env's stream; does not fold)
+  std::vector<uint64_t> bins(uint32_t first_book, uint32_t n_books) {
+    std::vector<uint64_t> counts(static_cast<size_t>(n_books) * bins_per_book_);
+    check(bk_get_bins(h_, first_book, n_books, counts.data()));
+    return counts;
+  }
+  std::vector<uint64_t> bins() { return bins(0, n_books_); }
+  // the table in device memory, uint64_t[n_books][n_spans + 2][n_bins]
+  uint64_t* bins_device_ptr() {
+    void* p = nullptr;
+    check(bk_bins_device_ptr(h_, &p));
+    return static_cast<uint64_t*>(p);
+  }
+  // a mask (one byte per book): fold, then clear those books' counts and carry; an empty mask: clear all without folding
+  void clear_bins(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_bins_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
   // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
   void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
@@ -427,7 +459,7 @@ class ManyEnv {
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0, bins_per_book_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
