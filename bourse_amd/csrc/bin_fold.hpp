@@ -13,7 +13,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "lag_fold.hpp"  // lags::word_of, lags::TWO, lags::M_BITS (and series::two_sided behind them)
+#include "hist_cursor.hpp"  // ring::slot_of
+#include "lag_fold.hpp"     // lags::word_of, lags::TWO, lags::M_BITS (and series::two_sided behind them)
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define BKD_BINS_HD __host__ __device__ inline
@@ -29,6 +30,7 @@ constexpr uint32_t MAX_CHANNELS = MAX_SPANS + 2u;
 using lags::M_BITS;
 using lags::TWO;
 using lags::word_of;
+using ring::slot_of;  // the ring slot of step i of a fold whose first step stands at slot0
 
 // floor(h / w) for w >= 1: below zero it is -ceil(|h| / w)
 BKD_BINS_HD int64_t floor_div(int64_t h, uint32_t w) {
@@ -62,12 +64,6 @@ BKD_BINS_HD Where partner(uint32_t i, uint32_t k) { return i >= k ? Where{true, 
 
 // ... and where entry i of the carry BEHIND a fold of n steps comes from: the record of step lo + n - 1 - i
 BKD_BINS_HD Where next_carry(uint32_t n, uint32_t i) { return i < n ? Where{true, n - 1u - i} : Where{false, i - n}; }
-
-// the ring slot of step i of a fold whose first step stands at slot0: slot0 < cap, i < cap - one conditional subtract
-BKD_BINS_HD uint64_t slot_of(uint32_t slot0, uint32_t i, uint64_t cap) {
-  const uint64_t slot = static_cast<uint64_t>(slot0) + i;
-  return slot >= cap ? slot - cap : slot;
-}
 
 }  // namespace bins
 }  // namespace bkd

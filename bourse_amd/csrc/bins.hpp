@@ -24,17 +24,17 @@
 
 #include "bin_fold.hpp"
 #include "book_device.hpp"
+#include "hist_ring.hpp"
 
 namespace bkd {
 namespace bins {
 
 constexpr int FOLD_WAVES = 4;  // waves (books) per block of k_fold / k_clear
 
+using ring::wave_sync;
+
 struct FoldArgs {
-  const uint32_t* hist;  // [hist_cap][n_books][W]
-  uint32_t hist_cap, n_books, W;
-  uint32_t slot0;  // lo % hist_cap
-  uint32_t n;      // steps to fold, 1 .. hist_cap
+  ring::Span ring;
   uint32_t B, S, Kmax;
   uint32_t spans;  // k_j in byte j (a register shift, not an indexed argument)
   uint32_t ret_width, spread_width, vol_width;
@@ -45,15 +45,9 @@ struct FoldArgs {
 // LDS bytes of one block of k_fold
 inline size_t fold_lds_bytes(uint32_t S, uint32_t B) { return static_cast<size_t>(FOLD_WAVES) * (S + 2u) * B * sizeof(uint32_t); }
 
-// what one wave's LDS and global accesses must reach before its other lanes' later ones
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // the window word of step `at` of the fold
 __device__ __forceinline__ uint64_t ring_word(const FoldArgs& g, uint32_t b, uint32_t at) {
-  const uint32_t* rec = g.hist + (static_cast<size_t>(slot_of(g.slot0, at, g.hist_cap)) * g.n_books + b) * g.W;
+  const uint32_t* rec = ring::record(g.ring, slot_of(g.ring.slot0, at, g.ring.hist_cap), b);
   return word_of(rec[1], rec[2]);
 }
 
@@ -62,15 +56,15 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = rfl(threadIdx.x >> 6);
   const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + wave);
-  if (b >= g.n_books) return;  // (no block-wide barrier below: a wave is on its own)
+  if (b >= g.ring.n_books) return;  // (no block-wide barrier below: a wave is on its own)
   const uint32_t B = g.B, S = g.S, CB = (S + 2u) * B;
   uint32_t* cnt = counters + wave * CB;
   uint64_t* carry = g.carry + static_cast<size_t>(b) * g.Kmax;
   for (uint32_t v = lane; v < CB; v += 64u) cnt[v] = 0u;
   wave_sync();
 
-  for (uint32_t i = lane; i < g.n; i += 64u) {  // step lo + i
-    const uint32_t* rec = g.hist + (static_cast<size_t>(slot_of(g.slot0, i, g.hist_cap)) * g.n_books + b) * g.W;
+  for (uint32_t i = lane; i < g.ring.n; i += 64u) {  // step lo + i
+    const uint32_t* rec = ring::record(g.ring, slot_of(g.ring.slot0, i, g.ring.hist_cap), b);
     const uint32_t tv = rec[0], bid = rec[1], ask = rec[2];
     const uint64_t cur = word_of(bid, ask);
     atomicAdd(&cnt[(S + 1u) * B + vol_bin(tv, g.vol_width, B)], 1u);
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
   // the carry behind the fold: every entry is read (ring or old carry) before any is written
   uint64_t mine = 0ull;
   if (lane < g.Kmax) {
-    const Where w = next_carry(g.n, lane);
+    const Where w = next_carry(g.ring.n, lane);
     mine = w.in_ring ? ring_word(g, b, w.at) : carry[w.at];
   }
   wave_sync();
@@ -102,9 +96,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
 }
 
 struct ClearArgs {
-  const uint8_t* mask;  // [n_books / M] device memory; nullptr: every book
-  uint32_t M;           // books per mask byte (the resets' units are markets)
-  uint32_t n_books;
+  ring::Masked books;
   uint32_t CB;          // counts per book, (S + 2) * B
   uint32_t Kmax;
   uint32_t carry_only;  // 1: only the carry (no span reaches over a reset; the counts go on)
@@ -114,9 +106,8 @@ struct ClearArgs {
 
 __global__ __launch_bounds__(64 * FOLD_WAVES) void k_clear(ClearArgs g) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + (threadIdx.x >> 6));
-  if (b >= g.n_books) return;
-  if (g.mask && rfl(static_cast<uint32_t>(g.mask[b / g.M])) == 0u) return;
+  const uint32_t b = ring::masked_book(g.books, FOLD_WAVES);
+  if (b == ring::NO_BOOK) return;
   uint64_t* carry = g.carry + static_cast<size_t>(b) * g.Kmax;
   if (lane < g.Kmax) carry[lane] = 0ull;
   if (g.carry_only) return;

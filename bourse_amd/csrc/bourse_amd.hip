@@ -41,6 +41,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "host_math.hpp"
 #include "agent_table.hpp"
 #include "host_pool.hpp"
+#include "hist_cursor.hpp"
 #include "pipeline_plan.hpp"
 #include "mixed_agents.hpp"
 #include "wave_agents.hpp"
@@ -199,6 +200,29 @@ struct HostStage {
 
 }  // namespace
 
+// One table folded from the level-2 history ring by a host cursor - the series moments, the lag table, the bin table.
+// What the three share is written once over this struct (the cursor's rule is hist_cursor.hpp's); what differs is how a
+// table's fold over a span of the ring and its clear are launched.
+struct HistTable {
+  const char* noun;     // in the lost steps' message: "of the <noun> were lost"
+  const char* name;     // in the guard's: "this env has no <name>"
+  const char* article;  // in bk_load_book's refusal: "with <article><name>"
+  const char* prefix;   // its entries are bk_<prefix>_enable, bk_<prefix>_clear, ..
+  void (*fold)(bk_env*, const ring::Span&);  // steps [seen, seen + n) of every book, all retained
+  // rows (and carry) of the masked books (one mask byte per M books; nullptr: every book) -> cleared, or only their carry
+  void (*clear)(bk_env*, const uint8_t* mask_dev, uint32_t M, bool carry_only);
+  bool on = false;
+  uint64_t seen = 0;     // steps below it are folded (a host integer, as steps_done)
+  DevBuf<uint8_t> mask;  // bk_<prefix>_clear: device staging of the host mask [n_books]
+};
+enum { T_SERIES, T_LAGS, T_BINS, N_HIST_TABLES };
+static void launch_series_fold(bk_env*, const ring::Span&);
+static void launch_series_clear(bk_env*, const uint8_t*, uint32_t, bool);
+static void launch_lags_fold(bk_env*, const ring::Span&);
+static void launch_lags_clear(bk_env*, const uint8_t*, uint32_t, bool);
+static void launch_bins_fold(bk_env*, const ring::Span&);
+static void launch_bins_clear(bk_env*, const uint8_t*, uint32_t, bool);
+
 struct bk_env {
   bk_config cfg{};
   int R = 1;
@@ -254,28 +278,22 @@ struct bk_env {
   DevBuf<uint8_t> bars_mask;  // bk_trade_bars_clear: device staging of the host mask [n_books]
   uint32_t bars_window = 0;   // 0: no bars
   bool bars_consume = false;
-  // bk_series_enable: one row of series moments per book [n_books] of 192 B, folded from the history ring (series.hpp)
+  // the three tables folded from the history ring (HistTable above), and what each keeps on the device:
+  HistTable tables[N_HIST_TABLES] = {
+      {"series", "series moments", "", "series", launch_series_fold, launch_series_clear},
+      {"lag table", "lag table", "a ", "lags", launch_lags_fold, launch_lags_clear},
+      {"bin table", "bin table", "a ", "bins", launch_bins_fold, launch_bins_clear}};
+  // bk_series_enable: one row of series moments per book [n_books] of 192 B (series.hpp)
   DevBuf<bk_u32x4> series_rows;
-  DevBuf<uint8_t> series_mask;  // bk_series_clear: device staging of the host mask [n_books]
-  uint64_t series_seen = 0;     // steps below it are folded (a host integer, as steps_done)
-  bool series = false;
-  // bk_lags_enable: n_lags rows per book [n_books][n_lags] of 80 B and the carry [n_books][n_lags + 1], folded from the
-  // history ring (lags.hpp)
+  // bk_lags_enable: n_lags rows per book [n_books][n_lags] of 80 B and the carry [n_books][n_lags + 1] (lags.hpp)
   DevBuf<bk_u32x4> lag_rows;
   DevBuf<uint64_t> lag_carry;
-  DevBuf<uint8_t> lags_mask;  // bk_lags_clear: device staging of the host mask [n_books]
-  uint64_t lags_seen = 0;     // steps below it are folded (a host integer, as steps_done)
   uint32_t n_lags = 0;
-  bool lags = false;
-  // bk_bins_enable: (n_spans + 2) rows of n_bins counts per book [n_books][C][B] and the carry [n_books][bins_kmax], folded
-  // from the history ring (bins.hpp)
+  // bk_bins_enable: (n_spans + 2) rows of n_bins counts per book [n_books][C][B] and the carry [n_books][bins_kmax] (bins.hpp)
   DevBuf<uint64_t> bin_rows;
   DevBuf<uint64_t> bins_carry;
-  DevBuf<uint8_t> bins_mask;  // bk_bins_clear: device staging of the host mask [n_books]
-  uint64_t bins_seen = 0;     // steps below it are folded (a host integer, as steps_done)
   bk_bins_config bins_cfg{};
   uint32_t bins_kmax = 0;  // the longest span
-  bool bins = false;
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -569,8 +587,12 @@ auto by_R(int R, F&& f) {
 
 // A table kernel that gives every book one wave, `waves` of them per block, on the env's stream (g: its argument struct)
 template <typename K, typename A>
+void launch_wave_per_book(bk_env* env, K kernel, uint32_t waves, uint32_t n_books, const A& g) {
+  hipLaunchKernelGGL(kernel, dim3((n_books + waves - 1) / waves), dim3(64 * waves), 0, env->stream, g);
+}
+template <typename K, typename A>
 void launch_wave_per_book(bk_env* env, K kernel, uint32_t waves, const A& g) {
-  hipLaunchKernelGGL(kernel, dim3((g.n_books + waves - 1) / waves), dim3(64 * waves), 0, env->stream, g);
+  launch_wave_per_book(env, kernel, waves, g.n_books, g);
 }
 
 // stamps::k_compact over every book, on the env's stream: every live stamp becomes its rank, H_SEQ the live count
@@ -2691,9 +2713,7 @@ int bk_level2(bk_env* env, uint32_t first_book, uint32_t n_books, uint32_t* out)
 
 // first retained step of the history ring: the last history_capacity steps, or since the last bk_clear_history()
 static uint64_t hist_first(const bk_env* env) {
-  const uint64_t cap = env->cfg.history_capacity;
-  const uint64_t lo = env->steps_done > cap ? env->steps_done - cap : 0;
-  return std::max(lo, env->hist_base);
+  return ring::first_retained(env->steps_done, env->hist_base, env->cfg.history_capacity);
 }
 
 int bk_history_len(bk_env* env, uint64_t* first_step, uint64_t* n_steps) {
@@ -2784,125 +2804,52 @@ int bk_clear_history(bk_env* env) {
   return BK_OK;
 }
 
-// ------------------------------------------------------------------ per-book series moments of the level-2 history
-// No counterpart in the reference.  series_rows[n_books] rows of 24 u64 words, folded from the history ring by
-// series::k_fold on the env's stream when bk_series_fold, a masked clear or a reset asks; series.hpp, DESIGN.md 2.22.
-// steps [series_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
-static void launch_series_fold(bk_env* env, uint64_t n) {
+// ------------------------------------------------------------------ the tables folded from the level-2 history ring
+// No counterpart in the reference.  Per book: series_rows[n_books] rows of 24 u64 words (series.hpp),
+// lag_rows[n_books][n_lags] rows of 10 u64 words and lag_carry[n_books][n_lags + 1] (lags.hpp, 2.24), and
+// bin_rows[n_books][n_spans + 2][n_bins] u64 counts and bins_carry[n_books][bins_kmax] (bins.hpp, 2.25) - each folded
+// by its k_fold on the env's stream when its bk_*_fold, a masked clear or a reset asks.  The six launches first, then the
+// one contract over HistTable (2.21a).
+static ring::Masked masked_books(const bk_env* env, const uint8_t* mask_dev, uint32_t M) { return {mask_dev, M, env->cfg.n_books}; }
+
+static void launch_series_fold(bk_env* env, const ring::Span& span) {
   series::FoldArgs g{};
-  g.hist = env->hist.p;
-  g.hist_cap = env->cfg.history_capacity;
-  g.n_books = env->cfg.n_books;
-  g.W = env->W;
-  g.slot0 = static_cast<uint32_t>(env->series_seen % env->cfg.history_capacity);
-  g.n = static_cast<uint32_t>(n);
+  g.ring = span;
   g.rows = env->series_rows.p;
-  launch_wave_per_book(env, series::k_fold, series::FOLD_WAVES, g);
+  launch_wave_per_book(env, series::k_fold, series::FOLD_WAVES, span.n_books, g);
 }
 
-// rows of the masked books (one mask byte per M books; nullptr: every book) -> cleared, or only their carry words -> 0
 static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
   series::ClearArgs g{};
-  g.mask = mask_dev;
-  g.M = M;
-  g.n_books = env->cfg.n_books;
+  g.books = masked_books(env, mask_dev, M);
   g.carry_only = carry_only ? 1u : 0u;
   g.rows = env->series_rows.p;
-  launch_wave_per_book(env, series::k_clear, series::FOLD_WAVES, g);
+  launch_wave_per_book(env, series::k_clear, series::FOLD_WAVES, g.books.n_books, g);
 }
 
-// fold what is outstanding (nothing: no launch); a step the ring no longer retains refuses, rows and cursor unchanged
-static int series_fold_outstanding(bk_env* env) {
-  const uint64_t first = hist_first(env);
-  if (env->series_seen < first) {
-    char msg[224];
-    std::snprintf(msg, sizeof msg,
-                  "%llu step(s) of the series were lost: steps [%llu, %llu) are no longer retained by the history ring "
-                  "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
-                  "bk_series_clear(env, NULL) starts again",
-                  static_cast<unsigned long long>(first - env->series_seen), static_cast<unsigned long long>(env->series_seen),
-                  static_cast<unsigned long long>(first));
-    return fail(BK_INVALID_ARGUMENT, msg);
-  }
-  if (env->series_seen == env->steps_done) return BK_OK;
-  if (int rc = use_device(env)) return rc;
-  launch_series_fold(env, env->steps_done - env->series_seen);
-  HIPCHK(hipGetLastError());
-  env->series_seen = env->steps_done;
-  return BK_OK;
-}
-
-// ------------------------------------------------------------------ per-book lag table of the level-2 history
-// No counterpart in the reference.  lag_rows[n_books][n_lags] rows of 10 u64 words and lag_carry[n_books][n_lags + 1], folded
-// from the history ring by lags::k_fold on the env's stream when bk_lags_fold, a masked clear or a reset asks; lags.hpp,
-// DESIGN.md 2.24.
-// steps [lags_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
-static void launch_lags_fold(bk_env* env, uint64_t n) {
+static void launch_lags_fold(bk_env* env, const ring::Span& span) {
   lags::FoldArgs g{};
-  g.hist = env->hist.p;
-  g.hist_cap = env->cfg.history_capacity;
-  g.n_books = env->cfg.n_books;
-  g.W = env->W;
-  g.slot0 = static_cast<uint32_t>(env->lags_seen % env->cfg.history_capacity);
-  g.n = static_cast<uint32_t>(n);
+  g.ring = span;
   g.K = env->n_lags;
   g.rows = env->lag_rows.p;
   g.carry = env->lag_carry.p;
-  launch_wave_per_book(env, lags::k_fold, lags::FOLD_WAVES, g);
+  launch_wave_per_book(env, lags::k_fold, lags::FOLD_WAVES, span.n_books, g);
 }
 
-// rows and carry of the masked books (one mask byte per M books; nullptr: every book) -> 0, or only their carry
 static void launch_lags_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
   lags::ClearArgs g{};
-  g.mask = mask_dev;
-  g.M = M;
-  g.n_books = env->cfg.n_books;
+  g.books = masked_books(env, mask_dev, M);
   g.K = env->n_lags;
   g.carry_only = carry_only ? 1u : 0u;
   g.rows = env->lag_rows.p;
   g.carry = env->lag_carry.p;
-  launch_wave_per_book(env, lags::k_clear, lags::FOLD_WAVES, g);
+  launch_wave_per_book(env, lags::k_clear, lags::FOLD_WAVES, g.books.n_books, g);
 }
 
-// a step of [lags_seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
-static int lags_lost_check(bk_env* env) {
-  const uint64_t first = hist_first(env);
-  if (env->lags_seen >= first) return BK_OK;
-  char msg[224];
-  std::snprintf(msg, sizeof msg,
-                "%llu step(s) of the lag table were lost: steps [%llu, %llu) are no longer retained by the history ring "
-                "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
-                "bk_lags_clear(env, NULL) starts again",
-                static_cast<unsigned long long>(first - env->lags_seen), static_cast<unsigned long long>(env->lags_seen),
-                static_cast<unsigned long long>(first));
-  return fail(BK_INVALID_ARGUMENT, msg);
-}
-
-// fold what is outstanding (nothing: no launch); lost steps refuse, rows, carry and cursor unchanged
-static int lags_fold_outstanding(bk_env* env) {
-  if (int rc = lags_lost_check(env)) return rc;
-  if (env->lags_seen == env->steps_done) return BK_OK;
-  if (int rc = use_device(env)) return rc;
-  launch_lags_fold(env, env->steps_done - env->lags_seen);
-  HIPCHK(hipGetLastError());
-  env->lags_seen = env->steps_done;
-  return BK_OK;
-}
-
-// ------------------------------------------------------------------ per-book bin table of the level-2 history
-// No counterpart in the reference.  bin_rows[n_books][n_spans + 2][n_bins] u64 counts and bins_carry[n_books][bins_kmax],
-// folded from the history ring by bins::k_fold on the env's stream when bk_bins_fold, a masked clear or a reset asks;
-// bins.hpp, DESIGN.md 2.25.
-// steps [bins_seen, steps_done) of every book, read from the ring: n of them, 1 .. history_capacity, all retained
-static void launch_bins_fold(bk_env* env, uint64_t n) {
+static void launch_bins_fold(bk_env* env, const ring::Span& span) {
   const bk_bins_config& c = env->bins_cfg;
   bins::FoldArgs g{};
-  g.hist = env->hist.p;
-  g.hist_cap = env->cfg.history_capacity;
-  g.n_books = env->cfg.n_books;
-  g.W = env->W;
-  g.slot0 = static_cast<uint32_t>(env->bins_seen % env->cfg.history_capacity);
-  g.n = static_cast<uint32_t>(n);
+  g.ring = span;
   g.B = c.n_bins;
   g.S = c.n_spans;
   g.Kmax = env->bins_kmax;
@@ -2911,47 +2858,64 @@ static void launch_bins_fold(bk_env* env, uint64_t n) {
   g.rows = env->bin_rows.p;
   g.carry = env->bins_carry.p;
   // (a launch of its own: the wave-per-book helper passes no dynamic LDS)
-  hipLaunchKernelGGL(bins::k_fold, dim3((g.n_books + bins::FOLD_WAVES - 1) / bins::FOLD_WAVES), dim3(64 * bins::FOLD_WAVES),
+  hipLaunchKernelGGL(bins::k_fold, dim3((span.n_books + bins::FOLD_WAVES - 1) / bins::FOLD_WAVES), dim3(64 * bins::FOLD_WAVES),
                      bins::fold_lds_bytes(g.S, g.B), env->stream, g);
 }
 
-// counts and carry of the masked books (one mask byte per M books; nullptr: every book) -> 0, or only their carry
 static void launch_bins_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
   bins::ClearArgs g{};
-  g.mask = mask_dev;
-  g.M = M;
-  g.n_books = env->cfg.n_books;
+  g.books = masked_books(env, mask_dev, M);
   g.CB = (env->bins_cfg.n_spans + 2u) * env->bins_cfg.n_bins;
   g.Kmax = env->bins_kmax;
   g.carry_only = carry_only ? 1u : 0u;
   g.rows = env->bin_rows.p;
   g.carry = env->bins_carry.p;
-  launch_wave_per_book(env, bins::k_clear, bins::FOLD_WAVES, g);
+  launch_wave_per_book(env, bins::k_clear, bins::FOLD_WAVES, g.books.n_books, g);
 }
 
-// a step of [bins_seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
-static int bins_lost_check(bk_env* env) {
-  const uint64_t first = hist_first(env);
-  if (env->bins_seen >= first) return BK_OK;
+// a step of [seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
+// (`at`: where the cursor's answer goes for a caller that folds next)
+static int table_lost_check(bk_env* env, const HistTable& t, ring::Cursor* at = nullptr) {
+  const ring::Cursor c = ring::cursor(t.seen, env->steps_done, env->hist_base, env->cfg.history_capacity);
+  if (at) *at = c;
+  if (c.kind != ring::CURSOR_LOST) return BK_OK;
   char msg[224];
   std::snprintf(msg, sizeof msg,
-                "%llu step(s) of the bin table were lost: steps [%llu, %llu) are no longer retained by the history ring "
+                "%llu step(s) of the %s were lost: steps [%llu, %llu) are no longer retained by the history ring "
                 "(history_capacity steps, or since bk_clear_history) - fold at least every history_capacity steps; "
-                "bk_bins_clear(env, NULL) starts again",
-                static_cast<unsigned long long>(first - env->bins_seen), static_cast<unsigned long long>(env->bins_seen),
-                static_cast<unsigned long long>(first));
+                "bk_%s_clear(env, NULL) starts again",
+                static_cast<unsigned long long>(c.first - t.seen), t.noun, static_cast<unsigned long long>(t.seen),
+                static_cast<unsigned long long>(c.first), t.prefix);
   return fail(BK_INVALID_ARGUMENT, msg);
 }
 
-// fold what is outstanding (nothing: no launch); lost steps refuse, table, carry and cursor unchanged
-static int bins_fold_outstanding(bk_env* env) {
-  if (int rc = bins_lost_check(env)) return rc;
-  if (env->bins_seen == env->steps_done) return BK_OK;
+// fold what is outstanding (nothing: no launch); lost steps refuse, the table, its carry and its cursor unchanged
+static int table_fold_outstanding(bk_env* env, HistTable& t) {
+  ring::Cursor c;
+  if (int rc = table_lost_check(env, t, &c)) return rc;
+  if (c.kind != ring::CURSOR_FOLD) return BK_OK;
   if (int rc = use_device(env)) return rc;
-  launch_bins_fold(env, env->steps_done - env->bins_seen);
+  t.fold(env, ring::Span{env->hist.p, env->cfg.history_capacity, env->cfg.n_books, env->W, c.slot0, c.n});
   HIPCHK(hipGetLastError());
-  env->bins_seen = env->steps_done;
+  t.seen = env->steps_done;
   return BK_OK;
+}
+
+// the full clear of an enable or a bk_*_clear(env, NULL): every row starts again at this step, lost steps are forgotten
+static void table_start_again(bk_env* env, HistTable& t) {
+  t.seen = env->steps_done;
+  t.clear(env, nullptr, 1, false);
+}
+
+// What a bk_*_enable ends with once the table's blocks and shape stand in the env.  A clear that cannot be launched leaves
+// the table off: the caller then takes its blocks back out.
+static int table_commit_enable(bk_env* env, HistTable& t) {
+  t.on = true;
+  table_start_again(env, t);
+  const hipError_t launched = hipGetLastError();
+  if (launched == hipSuccess) return BK_OK;
+  t.on = false;
+  return fail(BK_HIP_ERROR, std::string("bk_") + t.prefix + "_enable: the clear could not be launched: " + hipGetErrorString(launched));
 }
 
 static int read_hdr(bk_env* env, uint32_t book, int first_dw, int n_dw, uint32_t* out) {
@@ -3103,15 +3067,11 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (env->bars_window)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trade bars (bk_trade_bars_enable) is not supported: "
                                      "its trade records would pass as the next step's");
-  if (env->series)
-    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with series moments (bk_series_enable) is not supported: "
-                                     "the book's next record would pass as the successor of the replaced book's last");
-  if (env->lags)
-    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a lag table (bk_lags_enable) is not supported: "
-                                     "the book's next record would pass as the successor of the replaced book's last");
-  if (env->bins)
-    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a bin table (bk_bins_enable) is not supported: "
-                                     "the book's next record would pass as the successor of the replaced book's last");
+  for (const HistTable& t : env->tables)
+    if (t.on)
+      return fail(BK_INVALID_ARGUMENT, std::string("loading a book into an env with ") + t.article + t.name + " (bk_" + t.prefix +
+                                           "_enable) is not supported: the book's next record would pass as the successor of "
+                                           "the replaced book's last");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
     return fail(BK_INVALID_ARGUMENT, "null argument");
   // (the agents' log holds what k_step_batch_log wrote for every id below the book's counter: a loaded book's orders
@@ -3593,20 +3553,12 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
   HIPCHK(hipGetLastError());
   // the image's stamps are whatever its env had reached: compacted here, the bound starts again at the pool size
   if (int rc = compact_stamps(env)) return rc;
-  if (env->series) {  // series moments are no part of a checkpoint: every row starts again at the restored step
-    launch_series_clear(env, nullptr, 1, false);
+  // the tables folded from the history ring are no part of a checkpoint: every row starts again at the restored step
+  for (HistTable& t : env->tables) {
+    if (!t.on) continue;
+    t.clear(env, nullptr, 1, false);
     HIPCHK(hipGetLastError());
-    env->series_seen = env->steps_done;
-  }
-  if (env->lags) {  // ... and so is the lag table: rows and carry start again at the restored step
-    launch_lags_clear(env, nullptr, 1, false);
-    HIPCHK(hipGetLastError());
-    env->lags_seen = env->steps_done;
-  }
-  if (env->bins) {  // ... and the bin table: counts and carry start again at the restored step
-    launch_bins_clear(env, nullptr, 1, false);
-    HIPCHK(hipGetLastError());
-    env->bins_seen = env->steps_done;
+    t.seen = env->steps_done;
   }
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
@@ -3745,25 +3697,16 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
 // whose save kept `stamp_bound`.
 static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bound, const uint8_t* mask_dev,
                             const uint64_t* seeds_dev) {
-  if (env->bins) {  // the bin table's lost steps refuse the reset before any table launches anything
-    if (int rc = bins_lost_check(env)) return rc;
-  }
-  if (env->lags) {  // the lag table's lost steps refuse the reset before the series launches anything
-    if (int rc = lags_lost_check(env)) return rc;
-  }
-  if (env->series) {  // series moments: the steps so far belong to the old episode (lost steps refuse the reset), then cut the carry
-    if (int rc = series_fold_outstanding(env)) return rc;
-    launch_series_clear(env, mask_dev, env->M, true);
-    HIPCHK(hipGetLastError());
-  }
-  if (env->lags) {  // the lag table: fold the old episode's steps, then cut the carry - no span or pair reaches over the reset
-    if (int rc = lags_fold_outstanding(env)) return rc;
-    launch_lags_clear(env, mask_dev, env->M, true);
-    HIPCHK(hipGetLastError());
-  }
-  if (env->bins) {  // the bin table: fold the old episode's steps, then cut the carry - no span reaches over the reset
-    if (int rc = bins_fold_outstanding(env)) return rc;
-    launch_bins_clear(env, mask_dev, env->M, true);
+  // the tables folded from the history ring: lost steps of any of them refuse the reset before one of them launches anything
+  // (checked bins, lags, series and launched series, lags, bins: the order decides whose message is seen when two have lost steps)
+  for (int i = N_HIST_TABLES - 1; i >= 0; --i)
+    if (env->tables[i].on)
+      if (int rc = table_lost_check(env, env->tables[i])) return rc;
+  // ... then the steps so far belong to the old episode, and no return, span or pair reaches over the reset: cut the carry
+  for (HistTable& t : env->tables) {
+    if (!t.on) continue;
+    if (int rc = table_fold_outstanding(env, t)) return rc;
+    t.clear(env, mask_dev, env->M, true);
     HIPCHK(hipGetLastError());
   }
   launch_reset_books(env, snap, mask_dev, seeds_dev);
@@ -4143,74 +4086,80 @@ int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host) {
   return clear_from_host(env, mask_host, env->bars_mask, bk_trade_bars_clear_device);
 }
 
-// ------------------------------------------------------------------ per-book series moments: the entries
-// (the launches and the fold of what is outstanding stand with the history ring above)
+// ------------------------------------------------------------------ the tables folded from the history ring: the entries
+// (the launches, the lost-step check and the fold of what is outstanding stand with the history ring above)
+// the guard of every entry but the enable
+static int table_ok(bk_env* env, int which) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  const HistTable& t = env->tables[which];
+  if (!t.on) return fail(BK_INVALID_ARGUMENT, std::string("this env has no ") + t.name + ": call bk_" + t.prefix + "_enable first");
+  return BK_OK;
+}
+
+static int table_fold(bk_env* env, int which) {
+  if (int rc = table_ok(env, which)) return rc;
+  return table_fold_outstanding(env, env->tables[which]);
+}
+
+static int table_clear_device(bk_env* env, int which, const uint8_t* mask_dev) {
+  if (int rc = table_ok(env, which)) return rc;
+  if (int rc = use_device(env)) return rc;
+  HistTable& t = env->tables[which];
+  if (mask_dev) {
+    if (int rc = table_fold_outstanding(env, t)) return rc;
+    t.clear(env, mask_dev, 1, false);
+  } else {
+    table_start_again(env, t);  // nothing is folded
+  }
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+static int table_clear(bk_env* env, int which, const uint8_t* mask_host, int (*device_form)(bk_env*, const uint8_t*)) {
+  if (int rc = table_ok(env, which)) return rc;
+  if (mask_host)
+    if (int rc = table_lost_check(env, env->tables[which])) return rc;  // (refused before the mask is staged)
+  return clear_from_host(env, mask_host, env->tables[which].mask, device_form);
+}
+
+// ------------------------------------------------------------------ per-book series moments
 int bk_series_enable(bk_env* env) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->cfg.history_capacity)
     return fail(BK_INVALID_ARGUMENT, "the series moments are folded from the level-2 history ring: history_capacity must be > 0");
-  if (env->series) return fail(BK_INVALID_ARGUMENT, "the series moments are already enabled on this env");
+  if (env->tables[T_SERIES].on) return fail(BK_INVALID_ARGUMENT, "the series moments are already enabled on this env");
   if (int rc = use_device(env)) return rc;
   DevBuf<bk_u32x4> rows;
   HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * series::ROW_VECS));
   env->series_rows.swap(rows);
-  env->series = true;
-  env->series_seen = env->steps_done;
-  launch_series_clear(env, nullptr, 1, false);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
+  const int rc = table_commit_enable(env, env->tables[T_SERIES]);
+  if (rc) env->series_rows.swap(rows);  // the env stays without the table: the new block leaves with `rows`
+  return rc;
 }
 
-static int series_ok(bk_env* env) {
-  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
-  if (!env->series) return fail(BK_INVALID_ARGUMENT, "this env has no series moments: call bk_series_enable first");
-  return BK_OK;
-}
-
-int bk_series_fold(bk_env* env) {
-  if (int rc = series_ok(env)) return rc;
-  return series_fold_outstanding(env);
-}
-
-int bk_series_clear_device(bk_env* env, const uint8_t* mask_dev) {
-  if (int rc = series_ok(env)) return rc;
-  if (int rc = use_device(env)) return rc;
-  if (mask_dev) {
-    if (int rc = series_fold_outstanding(env)) return rc;
-  } else {
-    env->series_seen = env->steps_done;  // every row starts again here: nothing is folded, lost steps are forgotten
-  }
-  launch_series_clear(env, mask_dev, 1, false);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
-}
-
-int bk_series_clear(bk_env* env, const uint8_t* mask_host) {
-  if (int rc = series_ok(env)) return rc;
-  if (mask_host && env->series_seen < hist_first(env)) return series_fold_outstanding(env);  // (refused before the mask is staged)
-  return clear_from_host(env, mask_host, env->series_mask, bk_series_clear_device);
-}
+int bk_series_fold(bk_env* env) { return table_fold(env, T_SERIES); }
+int bk_series_clear_device(bk_env* env, const uint8_t* mask_dev) { return table_clear_device(env, T_SERIES, mask_dev); }
+int bk_series_clear(bk_env* env, const uint8_t* mask_host) { return table_clear(env, T_SERIES, mask_host, bk_series_clear_device); }
 
 int bk_series_device_ptr(bk_env* env, void** out) {
-  if (int rc = series_ok(env)) return rc;
+  if (int rc = table_ok(env, T_SERIES)) return rc;
   if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
   *out = env->series_rows.p;
   return BK_OK;
 }
 
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out) {
-  if (int rc = series_ok(env)) return rc;
+  if (int rc = table_ok(env, T_SERIES)) return rc;
   return get_book_rows(env, first_book, n_books, {{env->series_rows.p, sizeof(bk_series_row), out}});
 }
 
-// ------------------------------------------------------------------ per-book lag table: the entries
-// (the launches and the fold of what is outstanding stand with the history ring above)
+// ------------------------------------------------------------------ per-book lag table
 int bk_lags_enable(bk_env* env, uint32_t n_lags) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
   if (!env->cfg.history_capacity)
     return fail(BK_INVALID_ARGUMENT, "the lag table is folded from the level-2 history ring: history_capacity must be > 0");
   if (n_lags == 0 || n_lags > lags::MAX_LAGS) return fail(BK_INVALID_ARGUMENT, "n_lags must be in 1..64");
-  if (env->lags) return fail(BK_INVALID_ARGUMENT, "the lag table is already enabled on this env");
+  if (env->tables[T_LAGS].on) return fail(BK_INVALID_ARGUMENT, "the lag table is already enabled on this env");
   if (int rc = use_device(env)) return rc;
   DevBuf<bk_u32x4> rows;
   DevBuf<uint64_t> carry;
@@ -4219,65 +4168,32 @@ int bk_lags_enable(bk_env* env, uint32_t n_lags) {
   env->lag_rows.swap(rows);
   env->lag_carry.swap(carry);
   env->n_lags = n_lags;
-  env->lags = true;
-  env->lags_seen = env->steps_done;
-  launch_lags_clear(env, nullptr, 1, false);
-  const hipError_t launched = hipGetLastError();
-  if (launched != hipSuccess) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
+  const int rc = table_commit_enable(env, env->tables[T_LAGS]);
+  if (rc) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
     env->lag_rows.swap(rows);
     env->lag_carry.swap(carry);
     env->n_lags = 0;
-    env->lags = false;
-    return fail(BK_HIP_ERROR, std::string("bk_lags_enable: the clear could not be launched: ") + hipGetErrorString(launched));
   }
-  return BK_OK;
+  return rc;
 }
 
-static int lags_ok(bk_env* env) {
-  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
-  if (!env->lags) return fail(BK_INVALID_ARGUMENT, "this env has no lag table: call bk_lags_enable first");
-  return BK_OK;
-}
-
-int bk_lags_fold(bk_env* env) {
-  if (int rc = lags_ok(env)) return rc;
-  return lags_fold_outstanding(env);
-}
-
-int bk_lags_clear_device(bk_env* env, const uint8_t* mask_dev) {
-  if (int rc = lags_ok(env)) return rc;
-  if (int rc = use_device(env)) return rc;
-  if (mask_dev) {
-    if (int rc = lags_fold_outstanding(env)) return rc;
-  } else {
-    env->lags_seen = env->steps_done;  // every row starts again here: nothing is folded, lost steps are forgotten
-  }
-  launch_lags_clear(env, mask_dev, 1, false);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
-}
-
-int bk_lags_clear(bk_env* env, const uint8_t* mask_host) {
-  if (int rc = lags_ok(env)) return rc;
-  if (mask_host)
-    if (int rc = lags_lost_check(env)) return rc;  // (refused before the mask is staged)
-  return clear_from_host(env, mask_host, env->lags_mask, bk_lags_clear_device);
-}
+int bk_lags_fold(bk_env* env) { return table_fold(env, T_LAGS); }
+int bk_lags_clear_device(bk_env* env, const uint8_t* mask_dev) { return table_clear_device(env, T_LAGS, mask_dev); }
+int bk_lags_clear(bk_env* env, const uint8_t* mask_host) { return table_clear(env, T_LAGS, mask_host, bk_lags_clear_device); }
 
 int bk_lags_device_ptr(bk_env* env, void** out) {
-  if (int rc = lags_ok(env)) return rc;
+  if (int rc = table_ok(env, T_LAGS)) return rc;
   if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
   *out = env->lag_rows.p;
   return BK_OK;
 }
 
 int bk_get_lags(bk_env* env, uint32_t first_book, uint32_t n_books, bk_lag_row* out) {
-  if (int rc = lags_ok(env)) return rc;
+  if (int rc = table_ok(env, T_LAGS)) return rc;
   return get_book_rows(env, first_book, n_books, {{env->lag_rows.p, env->n_lags * sizeof(bk_lag_row), out}});
 }
 
-// ------------------------------------------------------------------ per-book bin table: the entries
-// (the launches and the fold of what is outstanding stand with the history ring above)
+// ------------------------------------------------------------------ per-book bin table
 static const char* bins_config_fault(const bk_bins_config& c) {
   if (c.n_bins < 2u || c.n_bins > bins::MAX_BINS || c.n_bins % 2u) return "n_bins must be even and in 2..256";
   if (c.n_spans < 1u || c.n_spans > bins::MAX_SPANS) return "n_spans must be in 1..4";
@@ -4293,7 +4209,7 @@ int bk_bins_enable(bk_env* env, const bk_bins_config* cfg) {
   if (!env->cfg.history_capacity)
     return fail(BK_INVALID_ARGUMENT, "the bin table is folded from the level-2 history ring: history_capacity must be > 0");
   if (const char* why = bins_config_fault(*cfg)) return fail(BK_INVALID_ARGUMENT, why);
-  if (env->bins) return fail(BK_INVALID_ARGUMENT, "the bin table is already enabled on this env");
+  if (env->tables[T_BINS].on) return fail(BK_INVALID_ARGUMENT, "the bin table is already enabled on this env");
   if (int rc = use_device(env)) return rc;
   bk_bins_config c = *cfg;
   uint32_t kmax = 0;
@@ -4308,68 +4224,36 @@ int bk_bins_enable(bk_env* env, const bk_bins_config* cfg) {
   env->bins_carry.swap(carry);
   env->bins_cfg = c;
   env->bins_kmax = kmax;
-  env->bins = true;
-  env->bins_seen = env->steps_done;
-  launch_bins_clear(env, nullptr, 1, false);
-  const hipError_t launched = hipGetLastError();
-  if (launched != hipSuccess) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
+  const int rc = table_commit_enable(env, env->tables[T_BINS]);
+  if (rc) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
     env->bin_rows.swap(rows);
     env->bins_carry.swap(carry);
     env->bins_cfg = bk_bins_config{};
     env->bins_kmax = 0;
-    env->bins = false;
-    return fail(BK_HIP_ERROR, std::string("bk_bins_enable: the clear could not be launched: ") + hipGetErrorString(launched));
   }
-  return BK_OK;
-}
-
-static int bins_ok(bk_env* env) {
-  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
-  if (!env->bins) return fail(BK_INVALID_ARGUMENT, "this env has no bin table: call bk_bins_enable first");
-  return BK_OK;
+  return rc;
 }
 
 int bk_bins_config_get(bk_env* env, bk_bins_config* out) {
-  if (int rc = bins_ok(env)) return rc;
+  if (int rc = table_ok(env, T_BINS)) return rc;
   if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
   *out = env->bins_cfg;
   return BK_OK;
 }
 
-int bk_bins_fold(bk_env* env) {
-  if (int rc = bins_ok(env)) return rc;
-  return bins_fold_outstanding(env);
-}
-
-int bk_bins_clear_device(bk_env* env, const uint8_t* mask_dev) {
-  if (int rc = bins_ok(env)) return rc;
-  if (int rc = use_device(env)) return rc;
-  if (mask_dev) {
-    if (int rc = bins_fold_outstanding(env)) return rc;
-  } else {
-    env->bins_seen = env->steps_done;  // every count starts again here: nothing is folded, lost steps are forgotten
-  }
-  launch_bins_clear(env, mask_dev, 1, false);
-  HIPCHK(hipGetLastError());
-  return BK_OK;
-}
-
-int bk_bins_clear(bk_env* env, const uint8_t* mask_host) {
-  if (int rc = bins_ok(env)) return rc;
-  if (mask_host)
-    if (int rc = bins_lost_check(env)) return rc;  // (refused before the mask is staged)
-  return clear_from_host(env, mask_host, env->bins_mask, bk_bins_clear_device);
-}
+int bk_bins_fold(bk_env* env) { return table_fold(env, T_BINS); }
+int bk_bins_clear_device(bk_env* env, const uint8_t* mask_dev) { return table_clear_device(env, T_BINS, mask_dev); }
+int bk_bins_clear(bk_env* env, const uint8_t* mask_host) { return table_clear(env, T_BINS, mask_host, bk_bins_clear_device); }
 
 int bk_bins_device_ptr(bk_env* env, void** out) {
-  if (int rc = bins_ok(env)) return rc;
+  if (int rc = table_ok(env, T_BINS)) return rc;
   if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
   *out = env->bin_rows.p;
   return BK_OK;
 }
 
 int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out) {
-  if (int rc = bins_ok(env)) return rc;
+  if (int rc = table_ok(env, T_BINS)) return rc;
   const size_t per_book = static_cast<size_t>(env->bins_cfg.n_spans + 2u) * env->bins_cfg.n_bins * sizeof(uint64_t);
   return get_book_rows(env, first_book, n_books, {{env->bin_rows.p, per_book, out}});
 }

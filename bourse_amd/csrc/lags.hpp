@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "book_device.hpp"
+#include "hist_ring.hpp"
 #include "lag_fold.hpp"
 
 namespace bkd {
@@ -30,50 +31,36 @@ namespace lags {
 constexpr int FOLD_WAVES = 4;      // waves (books) per block of k_fold / k_clear
 constexpr uint32_t ROW_VECS = 5u;  // 16-byte vectors per row
 
+using ring::vec_hi;
+using ring::vec_lo;
+using ring::vec_of;
+using ring::wave_sync;
+
 struct FoldArgs {
-  const uint32_t* hist;  // [hist_cap][n_books][W]
-  uint32_t hist_cap, n_books, W;
-  uint32_t slot0;   // lo % hist_cap
-  uint32_t n;       // steps to fold, 1 .. hist_cap
+  ring::Span ring;
   uint32_t K;       // lags, 1 .. MAX_LAGS
   bk_u32x4* rows;   // [n_books][K][5]
   uint64_t* carry;  // [n_books][K + 1]
 };
-
-// what one wave's LDS writes must reach before its other lanes read them (and the reverse)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint64_t word_lo_hi(const bk_u32x4& v, bool hi) { return hi ? mk64(v.z, v.w) : mk64(v.x, v.y); }
-__device__ __forceinline__ bk_u32x4 vec_of(uint64_t lo, uint64_t hi) {
-  bk_u32x4 v;
-  v.x = static_cast<uint32_t>(lo), v.y = static_cast<uint32_t>(lo >> 32);
-  v.z = static_cast<uint32_t>(hi), v.w = static_cast<uint32_t>(hi >> 32);
-  return v;
-}
 
 __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
   __shared__ uint64_t windows[FOLD_WAVES][WINDOW_WORDS];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = rfl(threadIdx.x >> 6);
   const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + wave);
-  if (b >= g.n_books) return;  // (no block-wide barrier below: a wave is on its own)
+  if (b >= g.ring.n_books) return;  // (no block-wide barrier below: a wave is on its own)
   const uint32_t K = g.K;
   uint64_t* win = windows[wave];
   uint64_t* carry = g.carry + static_cast<size_t>(b) * (K + 1u);
   for (uint32_t j = lane; j <= K; j += 64u) win[carry_at(K, j)] = carry[j];
-  const uint64_t cap = g.hist_cap;
+  const uint64_t cap = g.ring.hist_cap;
 
   Row acc{};
-  for (uint32_t base = 0; base < g.n; base += CHUNK) {
-    const uint32_t cnt = g.n - base < CHUNK ? g.n - base : CHUNK;  // this chunk's steps: wave-uniform
+  for (uint32_t base = 0; base < g.ring.n; base += CHUNK) {
+    const uint32_t cnt = g.ring.n - base < CHUNK ? g.ring.n - base : CHUNK;  // this chunk's steps: wave-uniform
     uint64_t mine = 0;
     if (lane < cnt) {  // step lo + base + lane; base + lane < n <= cap, slot0 < cap: no division
-      uint64_t slot = static_cast<uint64_t>(g.slot0) + base + lane;
-      slot = slot >= cap ? slot - cap : slot;
-      const uint32_t* rec = g.hist + (static_cast<size_t>(slot) * g.n_books + b) * g.W;
+      const uint32_t* rec = ring::record(g.ring, ring::slot_of(g.ring.slot0, base + lane, cap), b);
       mine = word_of(rec[1], rec[2]);
       win[step_at(K, lane)] = mine;
     }
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
 #pragma unroll
     for (uint32_t v = 0; v < ROW_VECS; ++v) {
       const bk_u32x4 x = row[v];
-      r.w[2 * v] = word_lo_hi(x, false), r.w[2 * v + 1] = word_lo_hi(x, true);
+      r.w[2 * v] = vec_lo(x), r.w[2 * v + 1] = vec_hi(x);
     }
     merge(r, acc);
 #pragma unroll
@@ -113,9 +100,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
 }
 
 struct ClearArgs {
-  const uint8_t* mask;  // [n_books / M] device memory; nullptr: every book
-  uint32_t M;           // books per mask byte (the resets' units are markets)
-  uint32_t n_books;
+  ring::Masked books;
   uint32_t K;
   uint32_t carry_only;  // 1: only the carry (no span or pair reaches over a reset; the sums go on)
   bk_u32x4* rows;
@@ -124,9 +109,8 @@ struct ClearArgs {
 
 __global__ __launch_bounds__(64 * FOLD_WAVES) void k_clear(ClearArgs g) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + (threadIdx.x >> 6));
-  if (b >= g.n_books) return;
-  if (g.mask && rfl(static_cast<uint32_t>(g.mask[b / g.M])) == 0u) return;
+  const uint32_t b = ring::masked_book(g.books, FOLD_WAVES);
+  if (b == ring::NO_BOOK) return;
   uint64_t* carry = g.carry + static_cast<size_t>(b) * (g.K + 1u);
   for (uint32_t j = lane; j <= g.K; j += 64u) carry[j] = 0ull;
   if (g.carry_only) return;

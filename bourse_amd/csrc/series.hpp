@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "book_device.hpp"
+#include "hist_ring.hpp"
 #include "series_fold.hpp"
 
 namespace bkd {
@@ -28,11 +29,12 @@ namespace series {
 constexpr int FOLD_WAVES = 4;      // waves (books) per block of k_fold / k_clear
 constexpr uint32_t ROW_VECS = 12u;  // 16-byte vectors per row
 
+using ring::vec_hi;
+using ring::vec_lo;
+using ring::vec_of;
+
 struct FoldArgs {
-  const uint32_t* hist;  // [hist_cap][n_books][W]
-  uint32_t hist_cap, n_books, W;
-  uint32_t slot0;  // lo % hist_cap
-  uint32_t n;      // steps to fold, 1 .. hist_cap
+  ring::Span ring;
   bk_u32x4* rows;  // [n_books][12]
 };
 
@@ -73,39 +75,29 @@ __device__ __forceinline__ uint64_t rdl64(uint64_t v, uint32_t lane) {
   return mk64(rdl(static_cast<uint32_t>(v), lane), rdl(static_cast<uint32_t>(v >> 32), lane));
 }
 
-__device__ __forceinline__ uint64_t vec_lo(const bk_u32x4& v) { return mk64(v.x, v.y); }
-__device__ __forceinline__ uint64_t vec_hi(const bk_u32x4& v) { return mk64(v.z, v.w); }
-__device__ __forceinline__ bk_u32x4 vec_of(uint64_t lo, uint64_t hi) {
-  bk_u32x4 v;
-  v.x = static_cast<uint32_t>(lo), v.y = static_cast<uint32_t>(lo >> 32);
-  v.z = static_cast<uint32_t>(hi), v.w = static_cast<uint32_t>(hi >> 32);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + (threadIdx.x >> 6));
-  if (b >= g.n_books) return;
+  if (b >= g.ring.n_books) return;
   bk_u32x4* row = g.rows + static_cast<size_t>(b) * ROW_VECS;
   const bk_u32x4 cv = row[CARRY_M / 2];  // {carry_m, carry_d}: the values in front of step lo
   const Prev carry = unpack(mk64(rfl(cv.x), rfl(cv.y)), mk64(rfl(cv.z), rfl(cv.w)));
-  const uint64_t cap = g.hist_cap;
+  const uint64_t cap = g.ring.hist_cap;
 
   Row acc = cleared();
   Prev last = carry;  // the values behind this lane's latest step
-  for (uint32_t i = lane; i < g.n; i += 64u) {  // step lo + i; i, slot0 < cap: no division
-    uint64_t slot = static_cast<uint64_t>(g.slot0) + i;
-    slot = slot >= cap ? slot - cap : slot;
-    const uint32_t* rec = g.hist + (static_cast<size_t>(slot) * g.n_books + b) * g.W;
+  for (uint32_t i = lane; i < g.ring.n; i += 64u) {  // step lo + i; i, slot0 < cap: no division
+    const uint64_t slot = ring::slot_of(g.ring.slot0, i, cap);
+    const uint32_t* rec = ring::record(g.ring, slot, b);
     const uint32_t tv = rec[0], bid = rec[1], ask = rec[2], ask_vol = rec[3], bid_vol = rec[4];
     Prev p = carry;
     if (i >= 1u) {
       const uint64_t slot1 = slot == 0u ? cap - 1u : slot - 1u;
-      const uint32_t* rec1 = g.hist + (static_cast<size_t>(slot1) * g.n_books + b) * g.W;
+      const uint32_t* rec1 = ring::record(g.ring, slot1, b);
       Prev before1 = carry;  // (step lo - 1: only have_m and m are read)
       if (i >= 2u) {
         const uint64_t slot2 = slot1 == 0u ? cap - 1u : slot1 - 1u;
-        const uint32_t* rec2 = g.hist + (static_cast<size_t>(slot2) * g.n_books + b) * g.W;
+        const uint32_t* rec2 = ring::record(g.ring, slot2, b);
         before1 = quotes_only(rec2[1], rec2[2]);
       }
       p = prev_of(rec1[1], rec1[2], before1);
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
 
   // one reduction: every lane takes part (a lane without a step holds the cleared row)
   Row sum = cleared();
-  sum.w[N_STEPS] = g.n;
+  sum.w[N_STEPS] = g.ring.n;
   sum.w[N_TWO_SIDED] = wave_sum_u32(static_cast<uint32_t>(acc.w[N_TWO_SIDED]));  // (a lane's counts are below 2^26)
   sum.w[N_TRADE_STEPS] = wave_sum_u32(static_cast<uint32_t>(acc.w[N_TRADE_STEPS]));
   sum.w[N_RET] = wave_sum_u32(static_cast<uint32_t>(acc.w[N_RET]));
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
   sum.w[MIN_M] = wave_umin64(acc.w[MIN_M]);
   sum.w[MAX_M] = wave_umax64(acc.w[MAX_M]);
   // the carry is the last step's: its lane's latest
-  const uint32_t owner = (g.n - 1u) & 63u;
+  const uint32_t owner = (g.ring.n - 1u) & 63u;
   Prev tail;
   tail.have_m = rdl(last.have_m, owner);
   tail.have_d = rdl(last.have_d, owner);
@@ -161,18 +153,15 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold(FoldArgs g) {
 }
 
 struct ClearArgs {
-  const uint8_t* mask;  // [n_books / M] device memory; nullptr: every book
-  uint32_t M;           // books per mask byte (the resets' units are markets)
-  uint32_t n_books;
+  ring::Masked books;
   uint32_t carry_only;  // 1: only the two carry words (no return spans a reset; the sums go on)
   bk_u32x4* rows;
 };
 
 __global__ __launch_bounds__(64 * FOLD_WAVES) void k_clear(ClearArgs g) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t b = rfl(blockIdx.x * FOLD_WAVES + (threadIdx.x >> 6));
-  if (b >= g.n_books) return;
-  if (g.mask && rfl(static_cast<uint32_t>(g.mask[b / g.M])) == 0u) return;
+  const uint32_t b = ring::masked_book(g.books, FOLD_WAVES);
+  if (b == ring::NO_BOOK) return;
   bk_u32x4* row = g.rows + static_cast<size_t>(b) * ROW_VECS;
   // cleared(): all zeros except min_m, the low word of its vector
   static_assert(MIN_M % 2 == 0 && CARRY_M % 2 == 0 && CARRY_D == CARRY_M + 1, "the vectors of min_m and of the carry");

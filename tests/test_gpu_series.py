@@ -6,56 +6,27 @@ history() of the same run - oracle.ManyBooks / ManyMarkets for bk_run, one oracl
 the device-ingress flows - and the device's own history is held against the oracle's through tests/oracle_parity.py where
 the ring still retains it; case 1's rows are literal numbers worked out by hand.  Where a case says something only under a
 condition - one-sided steps, pairs, returns of both signs, a word that wraps - the condition is asserted on the expected
-side before anything is compared."""
+side before anything is compared.
+
+Here: the series' own cases. What it shares with the other two tables is written once: the three scenarios at the end of
+this file in tests/hist_tables.py, the rest - the other flows, lost steps, the ingress reset, a restore, the refusals - in
+tests/test_gpu_hist_tables.py[series]."""
 import numpy as np
 import pytest
 
-import oracle_parity as P
-import series_model as SM
-from ingress_support import ingress_env
-from test_gpu_reset_books import C2, MEMBERS, PIPELINES, STEP, make_env, ref_books
+pytest.register_assert_rewrite("hist_tables")  # (a support module: its asserts report their values too)
+
+import oracle_parity as P  # noqa: E402
+import series_model as SM  # noqa: E402
+from hist_tables import SERIES as TABLE  # noqa: E402
+from hist_tables import bk, lost, masked_clear_folds_first, reset_books_cuts_the_carry, run_env, run_folded_in_three_parts  # noqa: E402,F401 (bk is a fixture)
+from test_gpu_reset_books import C2, PIPELINES, STEP, ref_books  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+same_rows, cleared_rows = TABLE.same, TABLE.cleared
 M64 = (1 << 64) - 1
 MAXU = 0xFFFFFFFF
 SEED = 101
-
-
-@pytest.fixture(scope="module")
-def bk():
-    import bourse_amd
-
-    return bourse_amd
-
-
-def same_rows(got, want, tag):
-    assert got.dtype == want.dtype == SM.SERIES_DTYPE, (got.dtype, want.dtype)
-    assert got.shape == want.shape, f"{tag}: rows {got.shape} vs {want.shape}"
-    for f in SM.FIELDS:
-        P.same_array(got[f], want[f], tag, f"series word {f}")
-
-
-def cleared_rows(n):
-    return np.array([SM.row(SM.cleared())] * n, dtype=SM.SERIES_DTYPE)
-
-
-def lost(bk, call, n):
-    with pytest.raises(bk.BourseError, match=rf"\b{n} step\(s\) of the series were lost") as e:
-        call()
-    assert e.value.code == 5
-
-
-def refused(bk, call, match):
-    with pytest.raises(bk.BourseError, match=match) as e:
-        call()
-    assert e.value.code == 5
-
-
-def run_env(bk, B, cap, groups=C2, members=None, **kw):
-    """an env of test_gpu_reset_books' shape (levels 16, pool 64) with the table on"""
-    env = make_env(bk, B, groups=None if members else groups, members=members, steps=cap, **kw)
-    env.enable_series()
-    return env
 
 
 # ------------------------------------------------------------------------------------------------ 1. by hand
@@ -105,287 +76,16 @@ def test_rows_worked_out_by_hand(bk, oracle):
     env.close()
 
 
-# ------------------------------------------------------------------------------------------------ 2. / 3. bk_run
-@pytest.mark.parametrize("pipeline", [None] + list(PIPELINES))
-def test_run_folded_in_three_parts_equals_the_model_and_one_pass(bk, oracle, pipeline):
-    """5 books (the last block of four waves holds one), a ring of 96: run(70) and fold - a lane's second step for six
-    lanes - run(26) and fold - the ring at its last slots - run(40) and fold - the ring wrapped.  The same under every
-    pipeline: the fold does not depend on who wrote the ring."""
-    B, cap, parts = 5, 96, (70, 26, 40)
-    hist = ref_books(oracle, B, 16, sum(parts), groups=C2).history()
-    final = SM.rows(hist)
-    assert (final["n_two_sided"] < final["n_steps"]).any() and (final["n_pairs"] > 0).all(), final[["n_steps", "n_two_sided", "n_pairs"]]
-    d = np.diff(hist[:, :, 1].astype(np.int64) + hist[:, :, 2].astype(np.int64), axis=0)
-    both = (hist[1:, :, 1] != 0) & (hist[:-1, :, 1] != 0) & (hist[1:, :, 2] != MAXU) & (hist[:-1, :, 2] != MAXU)
-    assert (d[both] > 0).any() and (d[both] < 0).any()
-    env = run_env(bk, B, cap)
-    if pipeline:
-        env.set_pipeline(pipeline)
-    done = 0
-    for n in parts:
-        env.run(n, sync=False)
-        env.fold_series()
-        done += n
-        same_rows(env.series(), SM.rows(hist[:done]), f"after {done} steps ({pipeline})")
-    P.no_flags(env)
-    same_rows(env.series(), final, "three folds against one pass of the model")
-    P.same_history(env.history(), hist[done - cap:])
-    env.close()
-
-
-# ------------------------------------------------------------------------------------------------ 4. members, markets
-def test_noise_and_momentum_members_folded_in_chunks_of_seven(bk, oracle):
-    B, T = 3, 40
-    hist = ref_books(oracle, B, 16, T, members=MEMBERS).history()
-    env = run_env(bk, B, T, members=MEMBERS)
-    for lo in range(0, T, 7):
-        env.run(min(7, T - lo), sync=False)
-        env.fold_series()
-    P.no_flags(env)
-    want = SM.rows(hist)
-    assert (want["n_ret"] > 0).all()
-    same_rows(env.series(), want, "Noise + Momentum")
-    P.same_history(env.history(), hist)
-    env.close()
-
-
-def test_markets_keep_rows_per_book(bk, oracle):
-    NM, ticks, T = 3, [2, 2], 30
-    groups = [(0, 24, (40, 56), (10, 20), 2, 0.8), (1, 24, (40, 56), (10, 20), 2, 0.6), (1, 8, (40, 56), (50, 70), 2, 0.3)]
-    env = bk.ManyMarketEnv(NM, SEED, 0, ticks, STEP, True, levels=10, max_live_orders=64, trade_capacity=4096, history_capacity=T)
-    env.set_random_market_agents(groups)
-    env.enable_series()
-    ref = oracle.ManyMarkets(NM, SEED, 0, ticks, STEP, True, 10, groups)
-    ref.run(T)
-    hist = ref.history()
-    for n in (11, 19):
-        env.run(n, sync=False)
-        env.fold_series()
-    P.no_flags(env)
-    want = SM.rows(hist)
-    assert want.shape == (6,) and (want["n_two_sided"] > 0).all() and len({tuple(r.tolist()) for r in want}) == 6
-    same_rows(env.series(), want, "markets, rows per book")
-    P.same_history(env.history(), hist)
-    env.close()
-
-
-# ------------------------------------------------------------------------------------------------ 5. device ingress
-def test_ingress_folded_after_every_step_equals_one_fold_at_the_end(bk, oracle):
-    """fold_series() behind EVERY step takes the carry path every time (each lane-0 step reads the row's carry words); a twin
-    env folds once at the end.  Bars and accounts run beside the table on the first env and still equal their own models."""
-    import torch
-
-    from test_gpu_accounts import busy_flow
-    from test_gpu_accounts import same_rows as same_accounts
-    from test_gpu_trade_bars import Tape, same_bars
-
-    B, T, tick, NT, W = 4, 9, 2, 5, 3
-    flows = [busy_flow(np.random.default_rng(20 + s), B, tick, idle=(1,) if s in (3, 4) else (), n_lo=30, n_hi=40) for s in range(T)]
-    env = ingress_env(bk, torch, B, T, 256, 0, 64, tick=tick, n_ext=40)
-    twin = ingress_env(bk, torch, B, T, 256, 0, 64, tick=tick, n_ext=40)
-    env.enable_accounts(NT)
-    env.enable_trade_bars(W)
-    env.enable_series()
-    twin.enable_series()
-    tape, other = Tape(oracle, B, tick, env, torch), Tape(oracle, B, tick, twin, torch)
-    for s, f in enumerate(flows):
-        for t in (tape, other):
-            t.submit(*f)
-            t.step()
-        env.fold_series()
-        if s == 4:
-            mid = env.series()
-    twin.fold_series()
-    hist = np.stack([r.history() for r in tape.refs], axis=1)
-    want = SM.rows(hist)
-    assert (want["n_pairs"] > 0).all() and (want["n_trade_steps"] > 0).all()
-    same_rows(mid, SM.rows(hist[:5]), "after step 4")
-    same_rows(env.series(), want, "folded after every step")
-    same_rows(twin.series(), want, "folded once")
-    for e in (env, twin):
-        P.no_flags(e)
-        P.same_history(e.history(), hist)
-    same_bars(env.trade_bars(), tape.bars(W), "the bars beside the series")
-    same_accounts(env.accounts(), tape.want(NT), "the accounts beside the series")
-    env.close()
-    twin.close()
-
-
-# ------------------------------------------------------------------------------------------------ 6. lost steps
-def test_lost_steps_refuse_the_fold_and_a_full_clear_recovers(bk, oracle):
-    B = 3
-    hist = ref_books(oracle, B, 16, 16, groups=C2).history()
-    env = run_env(bk, B, 8)
-    env.run(3)
-    env.fold_series()
-    before = env.series()
-    same_rows(before, SM.rows(hist[:3]), "three steps")
-    env.run(9)  # steps 3 .. 11 into a ring of 8: step 3 is gone
-    lost(bk, env.fold_series, 1)
-    same_rows(env.series(), before, "a refused fold leaves the rows")
-    lost(bk, env.fold_series, 1)  # ... and the cursor
-    lost(bk, lambda: env.clear_series(np.array([1, 0, 0], dtype=bool)), 1)
-    same_rows(env.series(), before, "a refused clear leaves the rows")
-    env.clear_series()
-    same_rows(env.series(), cleared_rows(B), "clear_series() clears every row")
-    env.run(2)
-    env.fold_series()
-    same_rows(env.series(), SM.rows(hist[12:14], first_step=12), "counted from the clear on")
-    # the same through clear_history(): the two steps run since the last fold are no longer retained
-    env.run(2)
-    env.clear_history()
-    lost(bk, env.fold_series, 2)
-    env.clear_series()
-    env.close()
-
-
 # ------------------------------------------------------------------------------------------------ 7. resets
-@pytest.mark.parametrize("kind", ["host", "device"])
-def test_reset_books_cuts_the_carry_of_the_books_it_resets(bk, oracle, kind):
-    """6 steps, save, fold; 5 steps NOT folded; reset books 0, 2, 4 - which folds the five first - then 7 steps.  A reset
-    book replays steps 6 .. 12 of the same seed: its series is the oracle's steps 0 .. 10, a cut, steps 6 .. 12.  The sums
-    go on; no return spans the reset."""
-    B, n, m, k = 5, 6, 5, 7
-    hist = ref_books(oracle, B, 16, n + m + k, groups=C2).history()
-    env = run_env(bk, B, n + m + k, kind=kind)
-    env.run(n)
-    env.save_snapshot()
-    env.fold_series()
-    env.run(m)
-    mask = np.array([1, 0, 1, 0, 1], dtype=bool)
-    if kind == "device":
-        import torch
-
-        env.reset_books(torch.tensor(mask, device="cuda"), sync=False)
-    else:
-        env.reset_books(mask)
-    at_reset = env.series()
-    want = []
-    for b in range(B):
-        s = SM.fold(hist[:n + m, b])
-        want.append(SM.row(SM.cut(s) if mask[b] else s))
-    same_rows(at_reset, np.array(want, dtype=SM.SERIES_DTYPE), "the reset folded the five steps and cut the masked carries")
-    assert not at_reset["carry_m"][mask].any() and not at_reset["carry_d"][mask].any() and at_reset["carry_m"][~mask].any()
-    env.run(k)
-    env.fold_series()
-    want = []
-    for b in range(B):
-        if mask[b]:
-            s = SM.fold(hist[n:n + k, b], cuts=[n + m], first_step=n + m, into=SM.fold(hist[:n + m, b]))
-        else:
-            s = SM.fold(hist[:, b])
-        want.append(SM.row(s))
-    want = np.array(want, dtype=SM.SERIES_DTYPE)
-    assert (want["n_steps"] == n + m + k).all() and (want["n_ret"][mask] > 0).all()
-    same_rows(env.series(), want, f"reset_books ({kind})")
-    P.no_flags(env)
-    env.close()
-
-
 def test_a_reset_is_refused_when_steps_were_lost(bk, oracle):
-    env = run_env(bk, 3, 8)
+    env = run_env(bk, TABLE, 3, 8)
     env.run(2)
     env.save_snapshot()
     env.run(9)
-    lost(bk, lambda: env.reset_books(np.array([1, 0, 0], dtype=bool)), 3)
+    lost(bk, TABLE, lambda: env.reset_books(np.array([1, 0, 0], dtype=bool)), 3)
     assert env.steps_done() == 11
     env.clear_series()
     env.reset_books(np.array([1, 0, 0], dtype=bool))
-    env.close()
-
-
-def test_reset_ingress_books_cuts_the_carry_too(bk, oracle):
-    """3 steps, save, 3 steps, reset books 0 and 2 (a torch CUDA mask; the three steps are folded by the reset), 2 steps.
-    The oracle cannot be rewound: a reset book's quotes after the reset are those of a REPLAY, a fresh oracle env given
-    steps 0 .. 2 again and then the two steps after the reset (tests/test_gpu_accounts.py)."""
-    import torch
-
-    from test_gpu_accounts import Books, busy_flow
-
-    B, tick = 4, 2
-    env = ingress_env(bk, torch, B, 8, 256, 0, 64, tick=tick, n_ext=40)
-    env.enable_series()
-    books = Books(oracle, B, tick, env, torch)
-    flows = [busy_flow(np.random.default_rng(60 + s), B, tick, n_lo=30, n_hi=40) for s in range(8)]
-
-    def run(lo, hi, bs=books):
-        for f in flows[lo:hi]:
-            bs.submit(*f)
-            bs.step()
-
-    run(0, 3)
-    env.save_ingress_snapshot()
-    env.fold_series()
-    run(3, 6)
-    mask = np.array([1, 0, 1, 0], dtype=bool)
-    env.reset_ingress_books(torch.tensor(mask, device="cuda"), sync=False)
-    run(6, 8)
-    env.fold_series()
-    replay = Books(oracle, B, tick)
-    run(0, 3, replay)
-    run(6, 8, replay)
-    want = []
-    for b in range(B):
-        h = books.refs[b].history()
-        if mask[b]:
-            s = SM.fold(replay.refs[b].history()[3:5], cuts=[6], first_step=6, into=SM.fold(h[:6]))
-        else:
-            s = SM.fold(h)
-        want.append(SM.row(s))
-    want = np.array(want, dtype=SM.SERIES_DTYPE)
-    assert (want["n_steps"] == 8).all() and (want["n_two_sided"] > 4).all()
-    same_rows(env.series(), want, "reset_ingress_books")
-    P.no_flags(env)
-    env.close()
-
-
-# ------------------------------------------------------------------------------------------------ 8. clears and views
-@pytest.mark.parametrize("kind", ["host", "device"])
-def test_a_masked_clear_folds_first_and_the_view_is_the_table_in_place(bk, oracle, kind):
-    import torch
-
-    B = 5
-    hist = ref_books(oracle, B, 16, 16, groups=C2).history()
-    env = run_env(bk, B, 16, kind="device")
-    view = torch.as_tensor(env.series_view(), device="cuda")
-    assert tuple(view.shape) == (B, 24) and view.dtype == torch.int64 and view.data_ptr() == env.series_device_ptr()
-    env.run(10, sync=False)  # (not folded: the masked clear folds the ten steps first)
-    mask = np.array([1, 0, 1, 0, 0], dtype=bool)
-    if kind == "host":
-        env.clear_series(mask)
-    else:
-        env.clear_series(torch.tensor(mask, device="cuda"), sync=False)
-    now = env.series()
-    same_rows(now[mask], cleared_rows(2), "the masked rows are cleared, carry included")
-    same_rows(now[~mask], SM.rows(hist[:10])[~mask], "the others hold the ten steps")
-    env.run(6, sync=False)
-    env.fold_series(sync=True)
-    want = SM.rows(hist)
-    want[mask] = SM.rows(hist[10:], first_step=10)[mask]
-    same_rows(env.series(), want, f"after clear_series ({kind})")
-    # the tensor made before any step sees the latest fold without a new call
-    seen = np.ascontiguousarray(view.cpu().numpy()).view(SM.SERIES_DTYPE).reshape(B)
-    same_rows(seen, want, "series_view() as a zero-copy tensor")
-    P.no_flags(env)
-    env.close()
-
-
-# ------------------------------------------------------------------------------------------------ 9. checkpoints
-def test_restore_clears_the_rows_and_rebases_the_cursor(bk, oracle):
-    B = 3
-    hist = ref_books(oracle, B, 16, 16, groups=C2).history()
-    env = run_env(bk, B, 16)
-    env.run(6)
-    env.fold_series()
-    ck = env.checkpoint()
-    env.run(4)  # (outstanding when the checkpoint comes back: forgotten, not folded)
-    env.restore(ck)
-    assert env.steps_done() == 6
-    same_rows(env.series(), cleared_rows(B), "restore clears every row")
-    env.run(5)
-    env.fold_series()
-    same_rows(env.series(), SM.rows(hist[6:11], first_step=6), "counted from the restored step on")
-    P.no_flags(env)
     env.close()
 
 
@@ -429,47 +129,11 @@ def test_extreme_prices_and_volumes(bk, oracle):
     env.close()
 
 
-# ------------------------------------------------------------------------------------------------ 11. refusals
-def test_refusals_leave_the_env_working(bk, oracle):
-    env = make_env(bk, 2, groups=C2, steps=8)
-    for call in (env.fold_series, env.series, env.series_device_ptr, env.series_view, env.clear_series,
-                 lambda: env.clear_series(np.ones(2, dtype=bool))):
-        refused(bk, call, "no series moments: call bk_series_enable first")
-    env.run(2)
-    env.enable_series()
-    refused(bk, env.enable_series, "already enabled")
-    with pytest.raises(ValueError):
-        env.clear_series(np.ones(3, dtype=bool))
-    with pytest.raises(ValueError):
-        env.run_series(4, chunk=9)
-    env.run(3)
-    env.fold_series()
-    hist = ref_books(oracle, 2, 16, 16, groups=C2).history()
-    same_rows(env.series(), SM.rows(hist[2:5], first_step=2), "steps before enable_series() are not counted")
-    env.close()
-    none = make_env(bk, 2, groups=C2, steps=0)
-    refused(bk, none.enable_series, "history_capacity must be > 0")
-    none.run(2)
-    none.close()
-    # a host-driven env: a book cannot be loaded into an env with the table
-    host = bk.ManyBookEnv(2, SEED, 0, 1, STEP, levels=5, max_live_orders=16, max_orders=16, trade_capacity=16, history_capacity=4)
-    host.place_order(0, True, 5, 1, 100)
-    host.step()
-    state = host.book_state(0)
-    host.load_book_state(1, state)
-    host.enable_series()
-    refused(bk, lambda: host.load_book_state(1, state), "series moments")
-    host.step()
-    host.fold_series(sync=True)
-    assert host.series()["n_steps"].tolist() == [1, 1] and host.series()["sum_bid_vol"].tolist() == [5, 5]
-    host.close()
-
-
 # ------------------------------------------------------------------------------------------------ 12. run_series, moments
 def test_run_series_runs_more_steps_than_the_ring_holds(bk, oracle):
     B, T = 5, 50
     hist = ref_books(oracle, B, 16, T, groups=C2).history()
-    env = run_env(bk, B, 16)
+    env = run_env(bk, TABLE, B, 16)
     env.run_series(T, chunk=16)
     assert env.steps_done() == T
     env.sync()
@@ -500,3 +164,20 @@ def test_run_series_runs_more_steps_than_the_ring_holds(bk, oracle):
     none = bk.series_moments(env.series())
     assert all(np.isnan(none[k]).all() for k in none.dtype.names)
     env.close()
+
+
+# ------------------------------------------------------------------------------------------------ 13. the shared scenarios
+# (written once in tests/hist_tables.py for the three tables; the rest of what they share is tests/test_gpu_hist_tables.py)
+@pytest.mark.parametrize("pipeline", [None] + list(PIPELINES))
+def test_run_folded_in_three_parts_equals_the_model_and_one_pass(bk, oracle, pipeline):
+    run_folded_in_three_parts(bk, oracle, TABLE, None, pipeline)
+
+
+@pytest.mark.parametrize("kind", ["host", "device"])
+def test_reset_books_cuts_the_carry_of_the_books_it_resets(bk, oracle, kind):
+    reset_books_cuts_the_carry(bk, oracle, TABLE, kind)
+
+
+@pytest.mark.parametrize("kind", ["host", "device"])
+def test_a_masked_clear_folds_first_and_the_view_is_the_table_in_place(bk, oracle, kind):
+    masked_clear_folds_first(bk, oracle, TABLE, kind)

@@ -299,37 +299,7 @@ def test_the_kernels_stay_out_of_the_baselined_namespace_and_every_launch_sits_b
     fold = open(os.path.join(ROOT, "bourse_amd", "csrc", "lag_fold.hpp")).read()
     assert re.search(r"namespace bkd \{\s*namespace lags \{", fold)
     assert "hip_runtime" not in fold and "asm" not in re.sub(r"//.*", "", fold)
-    # the launches: inside the table's own entries (which lags_ok / bk_lags_enable guard), or in a block of their own behind
-    # one `if (env->lags) {` in the resets' shared opening and the checkpoint load - an env without the table launches
-    # nothing new - and none of them is one of the series' three
-    hip = open(os.path.join(ROOT, "bourse_amd", "csrc", "bourse_amd.hip")).read()
-    fns = re.split(r"\n(?=(?:static )?(?:int|void|uint64_t|uint32_t) \w+\([^;]*\) \{\n)", hip)
-    seen = 0
-    for fn in fns:
-        m0 = re.match(r"(?:static )?\w+ (\w+)\(", fn)
-        name = m0.group(1) if m0 else ""
-        if "lags" in name:
-            assert not re.search(r"\b(launch_series_fold|launch_series_clear|series_fold_outstanding)\(", fn), name
-        for m in re.finditer(r"\b(launch_lags_fold|launch_lags_clear|lags_fold_outstanding|lags_lost_check)\(env", fn):
-            if m.start() < fn.index("{"):
-                continue  # (the definition itself)
-            seen += 1
-            if name in ("bk_lags_fold", "bk_lags_clear", "bk_lags_clear_device"):
-                assert "if (int rc = lags_ok(env)) return rc;" in fn[:m.start()], name
-            elif name == "bk_lags_enable":
-                assert "env->lags = true;" in fn[:m.start()], name
-            elif name == "lags_fold_outstanding":
-                assert m.group(1) in ("launch_lags_fold", "lags_lost_check")
-            else:
-                assert name in ("reset_books_from", "bk_checkpoint_load"), name
-                guard = fn.rfind("if (env->lags) {", 0, m.start())
-                assert guard >= 0 and "}" not in fn[guard + len("if (env->lags) {"):m.start()], (name, m.group(1))
-    assert seen == 11  # every call site there is: the two resets share theirs
-    assert len(re.findall(r"lags::k_(?:fold|clear),", hip)) == 2  # one launch site each
-    # with the series on as well, both tables' lost-step checks stand in front of the first launch of the resets' opening
-    reset = next(fn for fn in fns if fn.startswith("static int reset_books_from("))
-    assert reset.index("lags_lost_check(env)") < reset.index("series_fold_outstanding(env)") < reset.index("launch_series_clear(") < \
-        reset.index("lags_fold_outstanding(env)") < reset.index("launch_lags_clear(") < reset.index("launch_reset_books(")
+    # (where bourse_amd.hip launches them, and behind which guard: tests/test_hist_tables_cpu.py)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_isa_counts as K
 

@@ -270,31 +270,7 @@ def test_the_kernels_stay_out_of_the_baselined_namespace_and_every_launch_sits_b
     fold = open(os.path.join(ROOT, "bourse_amd", "csrc", "series_fold.hpp")).read()
     assert re.search(r"namespace bkd \{\s*namespace series \{", fold)
     assert "hip_runtime" not in fold and "asm" not in re.sub(r"//.*", "", fold)
-    # the new launches: inside the series' own entries (which series_ok / bk_series_enable guard), or behind one
-    # `if (env->series) {` in the resets' shared opening and the checkpoint load - an env without the table launches
-    # nothing new
-    hip = open(os.path.join(ROOT, "bourse_amd", "csrc", "bourse_amd.hip")).read()
-    fns = re.split(r"\n(?=(?:static )?(?:int|void|uint64_t|uint32_t) \w+\([^;]*\) \{\n)", hip)
-    seen = 0
-    for fn in fns:
-        name = re.match(r"(?:static )?\w+ (\w+)\(", fn).group(1) if re.match(r"(?:static )?\w+ (\w+)\(", fn) else ""
-        for m in re.finditer(r"\b(launch_series_fold|launch_series_clear|series_fold_outstanding)\(env", fn):
-            if m.start() < fn.index("{"):
-                continue  # (the definition itself)
-            seen += 1
-            if name in ("bk_series_fold", "bk_series_clear", "bk_series_clear_device"):
-                assert "if (int rc = series_ok(env)) return rc;" in fn[:m.start()], name
-            elif name == "bk_series_enable":
-                assert "env->series = true;" in fn[:m.start()], name
-            elif name == "series_fold_outstanding":
-                assert m.group(1) == "launch_series_fold"
-            else:
-                # (reset_books_from: what bk_reset_books_device and bk_ingress_reset_books_device both open with)
-                assert name in ("reset_books_from", "bk_checkpoint_load"), name
-                guard = fn.rfind("if (env->series) {", 0, m.start())
-                assert guard >= 0 and "}" not in fn[guard + len("if (env->series) {"):m.start()], (name, m.group(1))
-    assert seen == 9  # every call site there is: the two resets share theirs
-    assert len(re.findall(r"series::k_(?:fold|clear),", hip)) == 2  # one launch site each
+    # (where bourse_amd.hip launches them, and behind which guard: tests/test_hist_tables_cpu.py)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_isa_counts as K
 
