@@ -218,6 +218,77 @@ def lag_moments(rows) -> np.ndarray:
     return out
 
 
+# one book of the flow table (ManyBookEnv.flow): eight base words, then n_lags rows of six words (BK_FLOW_* in the header)
+FLOW_BASE_FIELDS = ("n_trades", "n_buy", "sum_vol", "buy_vol", "sum_vol_sq", "notional", "max_vol", "n_lost")
+FLOW_LAG_FIELDS = ("n_pairs", "sum_ss", "sum_resp", "sum_back", "sum_abs_dp", "sum_dp2")
+FLOW_LAG_SIGNED = ("sum_ss", "sum_resp", "sum_back")
+
+
+def flow_dtype(n_lags: int) -> np.dtype:
+    """One book's row of a flow table with ``n_lags`` lags, ``8 * (8 + 6 * n_lags)`` bytes: the base words as u64 fields, then
+    ``lags``, an int64 ``(n_lags, 6)`` sub-array whose row ``k - 1`` holds ``FLOW_LAG_FIELDS`` of lag ``k`` (the unsigned
+    words read as int64: the same bits)."""
+    K = int(n_lags)
+    if not 1 <= K <= MAX_LAGS:
+        raise ValueError("n_lags must be in 1..64")
+    return np.dtype({"names": list(FLOW_BASE_FIELDS) + ["lags"], "formats": ["<u8"] * 8 + [("<i8", (K, 6))],
+                     "offsets": [8 * i for i in range(9)], "itemsize": 8 * (8 + 6 * K)})
+
+
+FLOW_DTYPE = flow_dtype(16)  # (enable_flow's default n_lags; an env's own is ManyBookEnv.flow_dtype())
+FLOW_MOMENTS_BASE = ("buy_share", "sign_mean", "mean_vol", "var_vol", "vwap", "lost_share")
+FLOW_MOMENTS_LAG = ("sign_acf", "response", "back_response", "mean_abs_dp", "variogram")
+
+
+def flow_moments(rows) -> np.ndarray:
+    """``flow_dtype(K)`` rows of any shape (``ManyBookEnv.flow()``) -> float64 moments of the same shape, computed exactly in
+    Python integers and rounded once: the fields ``FLOW_MOMENTS_BASE`` and, each a ``(K,)`` sub-array with index ``k - 1``
+    for lag ``k`` in TRADE time, ``FLOW_MOMENTS_LAG``.
+
+    ``buy_share`` = n_buy / n_trades; ``sign_mean`` = 2 buy_share - 1; ``mean_vol``, ``var_vol`` the mean and variance of the
+    trade size; ``vwap`` = notional / sum_vol; ``lost_share`` = n_lost / (n_trades + n_lost).  Per lag, over its n_pairs:
+    ``sign_acf`` = (sum_ss / n - sign_mean^2) / (1 - sign_mean^2); ``response`` = sum_resp / n, the mean price change k trades
+    AFTER a trade in the direction of that trade; ``back_response`` = sum_back / n, the same before it; ``mean_abs_dp`` =
+    sum_abs_dp / n; ``variogram`` = sum_dp2 / n.  A value is NaN where a count or a denominator is 0.  The words are read
+    as they are: a sum that has wrapped modulo 2^64 is not detected."""
+    from fractions import Fraction as F
+
+    rows = np.asarray(rows)
+    names = rows.dtype.names or ()
+    if tuple(names) != FLOW_BASE_FIELDS + ("lags",) or rows.dtype["lags"].shape[1:] != (6,):
+        raise ValueError("flow_moments needs flow_dtype(K) rows")
+    K = rows.dtype["lags"].shape[0]
+    out = np.full(rows.shape, np.nan, dtype=np.dtype([(n, "<f8") for n in FLOW_MOMENTS_BASE] + [(n, "<f8", (K,)) for n in FLOW_MOMENTS_LAG]))
+    M = (1 << 64) - 1
+    flat_in, flat_out = rows.reshape(-1), out.reshape(-1)
+    for i in range(flat_in.size):
+        r, o = flat_in[i], flat_out[i]
+        w = {n: int(r[n]) for n in FLOW_BASE_FIELDS}
+        n, lost = w["n_trades"], w["n_lost"]
+        mean = None
+        if n:
+            mean = F(2 * w["n_buy"], n) - 1
+            o["buy_share"], o["sign_mean"] = float(F(w["n_buy"], n)), float(mean)
+            mv = F(w["sum_vol"], n)
+            o["mean_vol"], o["var_vol"] = float(mv), float(F(w["sum_vol_sq"], n) - mv * mv)
+        if w["sum_vol"]:
+            o["vwap"] = float(F(w["notional"], w["sum_vol"]))
+        if n + lost:
+            o["lost_share"] = float(F(lost, n + lost))
+        for k in range(K):
+            lw = dict(zip(FLOW_LAG_FIELDS, (int(x) for x in r["lags"][k])))
+            npair = lw["n_pairs"] & M
+            if not npair:
+                continue
+            if mean is not None and mean * mean != 1:
+                o["sign_acf"][k] = float((F(lw["sum_ss"], npair) - mean * mean) / (1 - mean * mean))
+            o["response"][k] = float(F(lw["sum_resp"], npair))
+            o["back_response"][k] = float(F(lw["sum_back"], npair))
+            o["mean_abs_dp"][k] = float(F(lw["sum_abs_dp"] & M, npair))
+            o["variogram"][k] = float(F(lw["sum_dp2"] & M, npair))
+    return out
+
+
 # bk_bins_config: the configuration of the bin table (ManyBookEnv.enable_bins), nine u32
 BINS_CONFIG_DTYPE = np.dtype(
     {"names": ["n_bins", "n_spans", "spans", "ret_width", "spread_width", "vol_width"],
@@ -463,6 +534,14 @@ SIGNATURES = {
     "bk_bins_clear_device": (_i32, [_vp, _vp]),
     "bk_bins_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_bins": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_flow_enable": (_i32, [_vp, _u32, _i32]),
+    "bk_flow_fold": (_i32, [_vp]),
+    "bk_flow_clear": (_i32, [_vp, _vp]),
+    "bk_flow_clear_device": (_i32, [_vp, _vp]),
+    "bk_flow_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_flow_lags": (_i32, [_vp, _p32]),
+    "bk_get_flow": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_get_flow_state": (_i32, [_vp, _u32, _u32, _vp, _vp]),
     "bk_open_orders_enable": (_i32, [_vp, _u32, _u32]),
     "bk_open_orders_refresh": (_i32, [_vp]),
     "bk_open_orders_device_ptrs": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -208,6 +208,16 @@ __device__ __forceinline__ uint32_t wave_add(uint32_t x) {  // wrapping u32 sum
   BK_DPP_REDUCE("v_add_u32_dpp");
   return rdl(x, 63);
 }
+// the exact sum of the wave's 64 words: two 16-bit limbs, each summed in a u32 (64 x 65 535 fits one)
+__device__ __forceinline__ uint64_t wave_sum_u32(uint32_t x) {
+  const uint32_t lo = wave_add(x & 0xFFFFu), hi = wave_add(x >> 16);
+  return static_cast<uint64_t>(lo) + (static_cast<uint64_t>(hi) << 16);
+}
+// the sum of the wave's 64 words modulo 2^64: four 16-bit limbs
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
+  const uint32_t lo = static_cast<uint32_t>(x), hi = static_cast<uint32_t>(x >> 32);
+  return wave_sum_u32(lo) + (wave_sum_u32(hi) << 32);
+}
 
 // The four reductions of the level-2 snapshot (max, min, add, add) interleaved: every DPP op is separated from the
 // previous op on the same register by three others, so the 2 wait states a VGPR-write -> DPP-read needs are filled with

@@ -62,6 +62,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "stamp_compact.hpp"
 #include "lags.hpp"
 #include "bins.hpp"
+#include "flow.hpp"
 
 using namespace bkd;
 
@@ -84,6 +85,10 @@ static_assert(sizeof(bk_lag_row) == 80 && sizeof(bk_lag_row) == lags::ROW_VECS *
                   sizeof(bk_lag_row) == lags::ROW_WORDS * 8 && offsetof(bk_lag_row, n_h) == lags::N_H * 8 &&
                   offsetof(bk_lag_row, sum_h4_lo) == lags::SUM_H4_LO * 8 && offsetof(bk_lag_row, max_abs_h) == lags::MAX_ABS_H * 8,
               "bk_lag_row layout (lag_fold.hpp)");
+static_assert(BK_FLOW_BASE_WORDS == flow::BASE_WORDS && BK_FLOW_LAG_WORDS == flow::LAG_WORDS && BK_FLOW_N_LOST == flow::N_LOST &&
+                  BK_FLOW_SUM_DP2 == flow::SUM_DP2 && flow::BASE_WORDS * 8 == flow::BASE_VECS * sizeof(bk_u32x4) &&
+                  flow::LAG_WORDS * 8 == flow::LAG_VECS * sizeof(bk_u32x4),
+              "the flow table's words (flow_fold.hpp)");
 static_assert(sizeof(bk_bins_config) == 36 && offsetof(bk_bins_config, spans) == 8 && offsetof(bk_bins_config, ret_width) == 24 &&
                   sizeof(static_cast<bk_bins_config*>(nullptr)->spans) == bins::MAX_SPANS * 4,
               "bk_bins_config layout (bin_fold.hpp)");
@@ -278,6 +283,14 @@ struct bk_env {
   DevBuf<uint8_t> bars_mask;  // bk_trade_bars_clear: device staging of the host mask [n_books]
   uint32_t bars_window = 0;   // 0: no bars
   bool bars_consume = false;
+  // bk_flow_enable: 8 + 6 flow_lags words per book [n_books][4 + 3 K] vectors, the carry [n_books][K] and the per-book
+  // cursors (flow.hpp)
+  DevBuf<bk_u32x4> flow_table;
+  DevBuf<uint64_t> flow_carry;
+  DevBuf<unsigned long long> flow_seen;
+  DevBuf<uint8_t> flow_mask;  // bk_flow_clear: device staging of the host mask [n_books]
+  uint32_t flow_lags = 0;     // 0: no flow table
+  bool flow_consume = false;
   // the three tables folded from the history ring (HistTable above), and what each keeps on the device:
   HistTable tables[N_HIST_TABLES] = {
       {"series", "series moments", "", "series", launch_series_fold, launch_series_clear},
@@ -1833,8 +1846,8 @@ static void launch_accounts_fold(bk_env* env) {
   g.acct = env->acct.p;
   g.n_traders = env->acct_traders;
   g.seen = env->acct_seen.p;
-  // (the last fold of a step consumes for both: the bars' fold runs in front of this one and leaves the records alone)
-  g.consume = env->acct_consume || env->bars_consume ? 1u : 0u;
+  // (the last fold of a step consumes for all: the flow's and the bars' folds run in front of this one and leave the records alone)
+  g.consume = env->acct_consume || env->bars_consume || env->flow_consume ? 1u : 0u;
   launch_wave_per_book(env, accounts::k_fold, accounts::FOLD_WAVES, g);
 }
 
@@ -1851,8 +1864,39 @@ static void launch_bars_fold(bk_env* env) {
   g.slot = static_cast<uint32_t>(env->steps_done % env->bars_window);
   g.prev_slot = (g.slot + env->bars_window - 1u) % env->bars_window;
   g.seen = env->bars_seen.p;
-  g.consume = !env->acct_traders && env->bars_consume ? 1u : 0u;
+  g.consume = !env->acct_traders && (env->bars_consume || env->flow_consume) ? 1u : 0u;
   launch_wave_per_book(env, trade_bars::k_fold, trade_bars::FOLD_WAVES, g);
+}
+
+// the flow table: every book's records [its cursor, H_TRADES); `consume`: the fold ends by H_TRADE_BASE = H_TRADES
+static void launch_flow_fold(bk_env* env, bool consume) {
+  flow::FoldArgs g{};
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.n_books = env->cfg.n_books;
+  g.trades = reinterpret_cast<const bk_u32x4*>(env->trades.p);
+  g.trade_cap = env->cfg.trade_capacity;
+  g.K = env->flow_lags;
+  g.table = env->flow_table.p;
+  g.carry = env->flow_carry.p;
+  g.seen = env->flow_seen.p;
+  g.consume = consume ? 1u : 0u;
+  launch_wave_per_book(env, flow::k_fold, flow::FOLD_WAVES, g);
+}
+
+// carry of the masked books (one mask byte per M books; nullptr: every book) -> invalid, their cursors -> the books'
+// H_TRADES; unless carry_only their words -> 0 as well
+static void launch_flow_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
+  flow::ClearArgs g{};
+  g.books = ring::Masked{mask_dev, M, env->cfg.n_books};
+  g.state = env->state.p;
+  g.stride = env->stride;
+  g.K = env->flow_lags;
+  g.carry_only = carry_only ? 1u : 0u;
+  g.table = env->flow_table.p;
+  g.carry = env->flow_carry.p;
+  g.seen = env->flow_seen.p;
+  launch_wave_per_book(env, flow::k_clear, flow::FOLD_WAVES, g.books.n_books, g);
 }
 
 // rows of the masked books (one mask byte per M books; nullptr: every book) -> 0, their cursors -> the books' H_TRADES
@@ -1933,7 +1977,11 @@ int bk_step_async(bk_env* env) {
   // step has been on the host)
   const int rc = by_R(env->R, [&](auto r) { return launch_events<decltype(r)::value>(env, a, env->steps_done, env->qcap); });
   if (rc != BK_OK) return rc;
-  if (env->bars_window) {  // trade bars: this step's new trade records, right behind the event kernel
+  if (env->flow_lags) {  // the flow table: this step's new trade records, right behind the event kernel; it consumes only alone
+    launch_flow_fold(env, env->flow_consume && !env->bars_window && !env->acct_traders);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->bars_window) {  // trade bars: the same records
     launch_bars_fold(env);
     HIPCHK(hipGetLastError());
   }
@@ -3067,6 +3115,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (env->bars_window)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with trade bars (bk_trade_bars_enable) is not supported: "
                                      "its trade records would pass as the next step's");
+  if (env->flow_lags)
+    return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a flow table (bk_flow_enable) is not supported: the "
+                                     "book's trade records would pass as the successors of the replaced book's");
   for (const HistTable& t : env->tables)
     if (t.on)
       return fail(BK_INVALID_ARGUMENT, std::string("loading a book into an env with ") + t.article + t.name + " (bk_" + t.prefix +
@@ -3560,6 +3611,10 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
     HIPCHK(hipGetLastError());
     t.seen = env->steps_done;
   }
+  if (env->flow_lags) {  // nor is the flow table: every word starts again, the cursors at the restored counts
+    launch_flow_clear(env, nullptr, 1, false);
+    HIPCHK(hipGetLastError());
+  }
   HIPCHK(hipStreamSynchronize(env->stream));
   return BK_OK;
 }
@@ -3709,8 +3764,16 @@ static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bo
     t.clear(env, mask_dev, env->M, true);
     HIPCHK(hipGetLastError());
   }
+  if (env->flow_lags) {  // the flow table: the records so far belong to the old episode
+    launch_flow_fold(env, env->flow_consume);
+    HIPCHK(hipGetLastError());
+  }
   launch_reset_books(env, snap, mask_dev, seeds_dev);
   HIPCHK(hipGetLastError());
+  if (env->flow_lags) {  // ... the reset put H_TRADES back: the cursors follow, and no pair reaches over the reset
+    launch_flow_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
   env->stamp_room.raise(stamp_bound);  // (the reset books' H_SEQ is the snapshot's again)
   return BK_OK;
 }
@@ -3945,6 +4008,13 @@ int bk_ingress_reset_books_device(bk_env* env, uint32_t slot, const uint8_t* mas
     launch_bars_clear(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
   }
+  // the flow table's sums go on across episodes: only the cut, the cursor at the restored count.  (reset_books_from has made
+  // this cut already, with the same mask, and nothing between there and here moves H_TRADES: the launch is kept beside the
+  // bars' and the accounts' as the place where whatever this entry later restores of a book's trade count is followed.)
+  if (env->flow_lags) {
+    launch_flow_clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
   if (env->open_traders) {  // the reset books show the snapshot's resting orders before their next step
     launch_open_refresh(env, mask_dev, env->M);
     HIPCHK(hipGetLastError());
@@ -4084,6 +4154,97 @@ int bk_trade_bars_clear_device(bk_env* env, const uint8_t* mask_dev) {
 int bk_trade_bars_clear(bk_env* env, const uint8_t* mask_host) {
   if (int rc = trade_bars_ok(env)) return rc;
   return clear_from_host(env, mask_host, env->bars_mask, bk_trade_bars_clear_device);
+}
+
+// ------------------------------------------------------------------ the flow table of the trade records
+// No counterpart in the reference.  table[n_books][8 + 6 K] u64 words - the base words, then K lag rows in trade time -
+// folded from each book's trade records by flow::k_fold from a per-book device cursor; flow.hpp, DESIGN.md 2.26.
+int bk_flow_enable(bk_env* env, uint32_t n_lags, int consume_trades) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->cfg.trade_capacity)
+    return fail(BK_INVALID_ARGUMENT, "the flow table is folded from the trade records: trade_capacity must be > 0");
+  if (n_lags == 0 || n_lags > flow::MAX_LAGS) return fail(BK_INVALID_ARGUMENT, "n_lags must be in 1..64");
+  if (env->flow_lags) return fail(BK_INVALID_ARGUMENT, "the flow table is already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  const size_t B = env->cfg.n_books;
+  DevBuf<bk_u32x4> table;
+  DevBuf<uint64_t> carry;
+  DevBuf<unsigned long long> seen;
+  HIPCHK(table.alloc(B * flow::book_vecs(n_lags)));
+  HIPCHK(carry.alloc(B * n_lags));
+  HIPCHK(seen.alloc(B));
+  env->flow_table.swap(table);
+  env->flow_carry.swap(carry);
+  env->flow_seen.swap(seen);
+  env->flow_lags = n_lags;
+  env->flow_consume = consume_trades != 0;
+  launch_flow_clear(env, nullptr, 1, false);
+  const hipError_t launched = hipGetLastError();
+  if (launched == hipSuccess) return BK_OK;
+  env->flow_table.swap(table);  // the env stays without the table: the new blocks leave with the locals
+  env->flow_carry.swap(carry);
+  env->flow_seen.swap(seen);
+  env->flow_lags = 0;
+  env->flow_consume = false;
+  return fail(BK_HIP_ERROR, std::string("bk_flow_enable: the clear could not be launched: ") + hipGetErrorString(launched));
+}
+
+static int flow_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->flow_lags) return fail(BK_INVALID_ARGUMENT, "this env has no flow table: call bk_flow_enable first");
+  return BK_OK;
+}
+
+int bk_flow_fold(bk_env* env) {
+  if (int rc = flow_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  launch_flow_fold(env, env->flow_consume);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_flow_clear_device(bk_env* env, const uint8_t* mask_dev) {
+  if (int rc = flow_ok(env)) return rc;
+  if (int rc = use_device(env)) return rc;
+  if (mask_dev) {  // (without a mask nothing is folded: every book starts again at its H_TRADES)
+    launch_flow_fold(env, env->flow_consume);
+    HIPCHK(hipGetLastError());
+  }
+  launch_flow_clear(env, mask_dev, 1, false);
+  HIPCHK(hipGetLastError());
+  return BK_OK;
+}
+
+int bk_flow_clear(bk_env* env, const uint8_t* mask_host) {
+  if (int rc = flow_ok(env)) return rc;
+  return clear_from_host(env, mask_host, env->flow_mask, bk_flow_clear_device);
+}
+
+int bk_flow_device_ptr(bk_env* env, void** out) {
+  if (int rc = flow_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->flow_table.p;
+  return BK_OK;
+}
+
+int bk_flow_lags(bk_env* env, uint32_t* out) {
+  if (int rc = flow_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->flow_lags;
+  return BK_OK;
+}
+
+int bk_get_flow(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out) {
+  if (int rc = flow_ok(env)) return rc;
+  return get_book_rows(env, first_book, n_books, {{env->flow_table.p, flow::table_words(env->flow_lags) * sizeof(uint64_t), out}});
+}
+
+// carry and cursors of books [first_book, first_book + n_books): what a test compares between differently cut folds
+int bk_get_flow_state(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* carry, uint64_t* seen) {
+  if (int rc = flow_ok(env)) return rc;
+  if (!seen) return fail(BK_INVALID_ARGUMENT, "null argument");
+  return get_book_rows(env, first_book, n_books, {{env->flow_seen.p, sizeof(uint64_t), seen},
+                                                  {env->flow_carry.p, env->flow_lags * sizeof(uint64_t), carry}});
 }
 
 // ------------------------------------------------------------------ the tables folded from the history ring: the entries

@@ -38,18 +38,7 @@ struct FoldArgs {
   bk_u32x4* rows;  // [n_books][12]
 };
 
-// the exact sum of the wave's 64 words: two 16-bit limbs, each summed in a u32
-__device__ __forceinline__ uint64_t wave_sum_u32(uint32_t x) {
-  const uint32_t lo = wave_add(x & 0xFFFFu), hi = wave_add(x >> 16);
-  return static_cast<uint64_t>(lo) + (static_cast<uint64_t>(hi) << 16);
-}
-
-// the sum of the wave's 64 words modulo 2^64: four 16-bit limbs
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
-  const uint32_t lo = static_cast<uint32_t>(x), hi = static_cast<uint32_t>(x >> 32);
-  return wave_sum_u32(lo) + (wave_sum_u32(hi) << 32);
-}
-
+// (wave_sum_u32 / wave_sum_u64, the wave's exact and modulo-2^64 sums, stand beside wave_add in book_device.hpp)
 // the sum of the wave's 64 word pairs modulo 2^128: the low word's sum is exact (70 bits), its carry goes to the high word
 __device__ __forceinline__ void wave_sum_u128(uint64_t lo, uint64_t hi, uint64_t& out_lo, uint64_t& out_hi) {
   const uint64_t s0 = wave_sum_u32(static_cast<uint32_t>(lo));        // < 2^38

@@ -45,18 +45,7 @@ struct FoldArgs {
   uint32_t consume;
 };
 
-// the exact sum of the wave's 64 words: two 16-bit limbs, each summed in a u32
-__device__ __forceinline__ uint64_t wave_sum_u32(uint32_t x) {
-  const uint32_t lo = wave_add(x & 0xFFFFu), hi = wave_add(x >> 16);
-  return static_cast<uint64_t>(lo) + (static_cast<uint64_t>(hi) << 16);
-}
-
-// the sum of the wave's 64 words modulo 2^64: four 16-bit limbs
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
-  const uint32_t lo = static_cast<uint32_t>(x), hi = static_cast<uint32_t>(x >> 32);
-  return wave_sum_u32(lo) + (wave_sum_u32(hi) << 32);
-}
-
+// (wave_sum_u32 / wave_sum_u64, the wave's exact and modulo-2^64 sums, stand beside wave_add in book_device.hpp)
 // one 48-byte row by the calling lane
 __device__ __forceinline__ void store_bar(bk_u32x4* row, const Bar& r) {
   uint32_t w[12];

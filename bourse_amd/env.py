@@ -190,6 +190,7 @@ class ManyBookEnv:
         self._bars_window = 0     # enable_trade_bars
         self._series = False      # enable_series
         self._n_lags = 0          # enable_lags
+        self._flow_lags = 0       # enable_flow
         self._bins_shape = None   # enable_bins: (n_spans + 2, n_bins)
         self._open_shape = None   # enable_open_orders: (n_traders, depth)
         self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
@@ -1350,11 +1351,14 @@ class ManyBookEnv:
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
         ``history_capacity``) until ``n_steps`` are run: the way to run more steps than the ring holds.  Nothing waits
         between the chunks, or at the end.  With ``enable_lags`` / ``enable_bins`` those tables are folded after every chunk
-        too - and alone if only they are enabled."""
+        too - and alone if only they are enabled.  So is the flow table of ``enable_flow`` (``fold_flow()``: the chunk's trade
+        records; with ``consume_trades`` ``trade_capacity`` then only has to hold one chunk's trades), also as the only table
+        of the env: ``fold_series`` and its refusal come only where no table at all is enabled."""
         c = self.history_capacity if chunk is None else int(chunk)
         if not 1 <= c <= self.history_capacity:
             raise ValueError("run_series needs 1 <= chunk <= history_capacity")
         folds = ([self.fold_lags] if self._n_lags else []) + ([self.fold_bins] if self._bins_shape else [])
+        folds += [self.fold_flow] if self._flow_lags else []  # (enable_flow: the chunk's trade records as well)
         if self._series or not folds:  # (neither table: fold_series raises the library's refusal, as ever)
             folds.insert(0, self.fold_series)
         for fold in folds:
@@ -1421,6 +1425,72 @@ class ManyBookEnv:
         the carry of the books they reset: the sums go on across episodes and no span or pair reaches over a reset."""
         # (no check of its own in front: the library refuses an env without the table)
         self._masked_clear(self._L.bk_lags_clear_device, self._L.bk_lags_clear, mask, sync)
+
+    # ------------------------------------------------------------ per-book flow table of the trade records
+    FLOW_DTYPE = _lib.FLOW_DTYPE
+
+    def enable_flow(self, n_lags: int = 16, consume_trades: bool = False):
+        """``bk_flow_enable``: keep ``8 + 6 * n_lags`` integer sums per book in device memory, over the book's TRADE RECORDS
+        in record order - counts, volumes and notional of all trades and of the buys, and at lags ``1 .. n_lags`` (1 .. 64)
+        in trade time the sums behind the sign autocorrelation, the response function and the price variogram
+        (``flow_dtype(n_lags)``; include/bourse_amd.h states what one record and one pair add).  ``fold_flow()`` folds every
+        book's new records on the env's stream; a device-ingress env also folds behind every ``step``; nothing leaves the
+        device until ``flow()`` is read.  Needs ``trade_capacity > 0``; works with ``run`` on every pipeline, ``step``, the
+        device ingress, markets and Noise / Momentum members.  ``consume_trades=True`` marks the records consumed by the
+        fold (as ``clear_trades``), so ``trade_capacity`` only has to hold what is written between two folds.  A record the
+        table could not read - dropped beyond ``trade_capacity``, or cleared / drained before the fold - counts in
+        ``n_lost`` and forms no pair.  Records before the call are not counted.  The reference has no counterpart."""
+        if not 0 <= int(n_lags) <= 0xFFFFFFFF:
+            raise ValueError("n_lags out of range")
+        check(self._L.bk_flow_enable(self._h, int(n_lags), 1 if consume_trades else 0))
+        self._flow_lags = int(n_lags)
+
+    def _flow_count(self) -> int:
+        if not self._flow_lags:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no flow table: call enable_flow (bk_flow_enable) first")
+        return self._flow_lags
+
+    def flow_dtype(self) -> np.dtype:
+        """``flow_dtype(n_lags)`` of this env's table."""
+        return _lib.flow_dtype(self._flow_count())
+
+    def fold_flow(self, sync: bool = False):
+        """``bk_flow_fold``: queue one launch that folds every book's trade records since its cursor (a book without a new
+        record returns at once)."""
+        check(self._L.bk_flow_fold(self._h))
+        if sync:
+            self.sync()
+
+    def flow(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array
+        (``flow_dtype()``): the eight base fields and ``lags``, an int64 ``(n_lags, 6)`` sub-array.  Waits for the env's
+        stream; does NOT fold."""
+        return self._book_rows(self._L.bk_get_flow, first_book, n_books, ((), self.flow_dtype()))[0]
+
+    def flow_state(self, first_book: int = 0, n_books: Optional[int] = None):
+        """``(carry [n, n_lags] uint64, cursors [n] uint64)`` of the same books, for tests and debugging
+        (``bk_get_flow_state``)."""
+        return tuple(self._book_rows(self._L.bk_get_flow_state, first_book, n_books, ((self._flow_count(),), np.uint64),
+                                     ((), np.uint64)))
+
+    def flow_device_ptr(self) -> int:
+        """Device address of the table, ``uint64_t[n_books][8 + 6 * n_lags]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_flow_device_ptr)
+
+    def flow_view(self) -> "FlowView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, 8 + 6 * n_lags)``,
+        the words in ``flow_dtype()``'s order (unsigned words read as int64: the same bits).  ``torch.as_tensor(
+        env.flow_view(), device="cuda")`` is a zero-copy tensor that every later fold updates; it is written on the env's
+        stream, so read it there (or after ``sync()``)."""
+        return FlowView(self, self.flow_device_ptr(), (self.n_books, 8 + 6 * self._flow_count()), self._stream)
+
+    def clear_flow(self, mask=None, sync: bool = True):
+        """With a ``mask`` (one entry per BOOK): fold, then zero the words, invalidate the carry and move the cursor to the
+        trade count of the books with ``mask[b]`` set.  ``None``: the same for every book without folding.  ``mask`` /
+        ``sync`` as ``clear_accounts`` takes them (``bk_flow_clear`` / ``bk_flow_clear_device``).  ``reset_books`` /
+        ``reset_ingress_books`` fold and then only cut the books they reset: the sums go on across episodes and no pair
+        reaches over a reset."""
+        self._masked_clear(self._L.bk_flow_clear_device, self._L.bk_flow_clear, mask, sync)
 
     # ------------------------------------------------------------ per-book bin table of the level-2 history
     BINS_CONFIG_DTYPE = _lib.BINS_CONFIG_DTYPE
@@ -1675,6 +1745,10 @@ class SeriesView(AccountsView):
 
 class LagsView(AccountsView):
     """``ManyBookEnv.lags_view()``: the lag table where it lives, read the same way."""
+
+
+class FlowView(AccountsView):
+    """``ManyBookEnv.flow_view()``: the flow table where it lives, read the same way."""
 
 
 class BinsView(AccountsView):

@@ -958,6 +958,94 @@ int bk_bins_device_ptr(bk_env* env, void** out);
  * env's stream; does NOT fold.  (No counterpart in the reference.) */
 int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
 
+/* ------------------------------------------------------ per-book flow table of the trade records */
+/* An opt-in table flow[n_books][8 + 6 K] of u64 words in DEVICE memory, K = n_lags, 1 <= K <= 64: per book the sums over its
+ * TRADE RECORDS in record order - the buy share and the size moments, and at lags k = 1 .. K in TRADE time the sums behind
+ * the autocorrelation of the trade sign, the response function <s_i (p_{i+k} - p_i)> and the variogram of the price.  It is
+ * folded on the env's stream by one small kernel with no host wait (bourse_amd/csrc/flow.hpp, flow_fold.hpp; DESIGN.md
+ * 2.26) and serves every env that writes trade records: bk_run on all pipelines, bk_step, the device ingress, markets,
+ * Noise / Momentum members.  It is not one of the tables of the history ring: its cursor is per book and lives in device
+ * memory, as the trade bars' and the accounts' do.  The reference has no counterpart for any of these entries.
+ *
+ * Record i of a book - i counts as bk_trade_count's total does - has the price p_i, the volume v_i and the sign s_i = +1 if
+ * the aggressor bought (side_is_bid == 0, the PASSIVE order's side, as for bk_trade_bar) and -1 otherwise.  A record that was
+ * read adds to the base words
+ *   n_trades += 1, n_buy += [s_i > 0], sum_vol += v_i, buy_vol += [s_i > 0] v_i, sum_vol_sq += v_i^2,
+ *   notional += v_i p_i (the full 32 x 32 product), max_vol = max(max_vol, v_i)
+ * and, for every k in 1 .. K of which record i - k was read as well - whatever lies between them -, with
+ * dp = p_i - p_{i-k} (signed), to lag row k - 1, the words 8 + 6 (k - 1) .. :
+ *   n_pairs += 1, sum_ss += s_i s_{i-k}, sum_resp += s_{i-k} dp, sum_back += s_i dp, sum_abs_dp += |dp|, sum_dp2 += dp^2.
+ * All words are sums modulo 2^64; signed words are two's complement; a cleared table is all zeros.
+ *
+ * Lost records.  A fold covers the indices [flow_seen, total).  Index i can be read iff first_retained <= i < total and
+ * i - first_retained < trade_capacity (bk_trade_count's words as the fold reads them): a record dropped beyond
+ * trade_capacity, or consumed by bk_clear_trades / bk_drain_trades / a consuming fold before this table saw it, cannot.  Such
+ * an index adds 1 to n_lost, stands in the window as an invalid word and forms no pair; a pair whose two ends were read
+ * still counts at its true lag.  A lost record is never silent and needs no flag bit (a dropped record's book carries
+ * BK_FLAG_TRADE_OVERFLOW already).
+ *
+ * The carry.  The env keeps flow_carry[n_books][K] u64 beside the table: entry j is the record of index flow_seen - 1 - j -
+ * bit 63 = it was read, bit 62 = s > 0, the low 32 bits = p - and the whole word is 0 when it was not read or lies in front
+ * of the table's start.  So folding [x, y) and then [y, z) leaves the same words and carry as one fold over [x, z), for every
+ * split. */
+enum { /* the words of one book (one `NAME = N` per line: tools/gen_rust_sys.py reads them) */
+  BK_FLOW_N_TRADES = 0,
+  BK_FLOW_N_BUY = 1,
+  BK_FLOW_SUM_VOL = 2,
+  BK_FLOW_BUY_VOL = 3,
+  BK_FLOW_SUM_VOL_SQ = 4,
+  BK_FLOW_NOTIONAL = 5,
+  BK_FLOW_MAX_VOL = 6,
+  BK_FLOW_N_LOST = 7,
+  BK_FLOW_BASE_WORDS = 8,
+  /* of lag row k - 1, from word BK_FLOW_BASE_WORDS + BK_FLOW_LAG_WORDS * (k - 1) */
+  BK_FLOW_N_PAIRS = 0,
+  BK_FLOW_SUM_SS = 1,
+  BK_FLOW_SUM_RESP = 2,
+  BK_FLOW_SUM_BACK = 3,
+  BK_FLOW_SUM_ABS_DP = 4,
+  BK_FLOW_SUM_DP2 = 5,
+  BK_FLOW_LAG_WORDS = 6
+};
+/* Enabling.  Accepted on any env with trade_capacity > 0, at any time, once; n_lags in 1 .. 64.  Allocates the table, the
+ * carry and the cursors (arrays of their own: the state block, checkpoints and snapshots are unchanged), clears them and
+ * sets every book's cursor to its current trade count: earlier records are not counted.  consume_trades != 0: a fold ends by
+ * marking the records consumed, as bk_clear_trades does, so trade_capacity only has to hold what is written between two
+ * folds.  A refusal - here and in the entries below: a null env, trade_capacity == 0, n_lags outside 1 .. 64, a second call,
+ * any other entry before this one - returns BK_INVALID_ARGUMENT, leaves the env unchanged and puts the reason in
+ * bk_last_error().
+ *
+ * bk_step_async on such an env folds the step's records right behind the event kernel, in front of the trade bars' and the
+ * accounts' folds; the LAST fold of the step consumes, once, if any of the three asked.  bk_reset_books* and
+ * bk_ingress_reset_books* first fold what is outstanding, then cut the books they reset (every book of a masked market):
+ * the carry is invalidated and the cursor follows the restored trade count, so no pair reaches over a reset and the sums go
+ * on across episodes; clear by mask if new rows are wanted.  bk_checkpoint_load clears every word and carry and sets the
+ * cursors to the restored counts.  bk_load_book is refused.  bk_warm writes no trade record and restores the counts:
+ * unaffected.  An env without the table launches nothing new.  (No counterpart in the reference.) */
+int bk_flow_enable(bk_env* env, uint32_t n_lags, int consume_trades);
+/* Queues, on the env's stream and without any host wait, ONE launch that folds every book's records [flow_seen, total);
+ * consumes iff the enable asked.  (No counterpart in the reference.) */
+int bk_flow_fold(bk_env* env);
+/* Clearing.  mask [n_books] bytes, one per BOOK.  With a mask: folds first, then zeroes the words, invalidates the carry and
+ * sets the cursor to the trade count of the books b with mask[b] != 0.  NULL: the same for every book WITHOUT folding.  From a
+ * HOST mask: staged on the env's stream and waited for, the clear itself stays asynchronous.  (No counterpart in the
+ * reference.) */
+int bk_flow_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every book).  HOLDS NO HOST SYNCHRONISATION: at most
+ * two launches on the env's stream.  (No counterpart in the reference.) */
+int bk_flow_clear_device(bk_env* env, const uint8_t* mask_dev);
+/* Device pointer of the table, uint64_t[n_books][8 + 6 n_lags], for on-device consumers; valid for the env's life, written
+ * on the env's stream.  (No counterpart in the reference.) */
+int bk_flow_device_ptr(bk_env* env, void** out);
+/* The table's n_lags.  (No counterpart in the reference.) */
+int bk_flow_lags(bk_env* env, uint32_t* out);
+/* Words of books [first_book, first_book + n_books) to host memory, n_books * (8 + 6 n_lags) words.  Waits for the env's
+ * stream; does NOT fold.  (No counterpart in the reference.) */
+int bk_get_flow(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
+/* For tests and debugging: the carry [n_books][n_lags] (may be NULL) and the cursors [n_books] of the same books.  Waits for
+ * the env's stream; does NOT fold.  (No counterpart in the reference.) */
+int bk_get_flow_state(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* carry, uint64_t* seen);
+
 /* ------------------------------------------------------ open orders of a device-ingress env */
 /* An opt-in pair of tables in DEVICE memory: which orders of each trader rest in each book, at what price and with how much
  * volume left - the one thing a strategy that submits from device memory could not read there (the ids to cancel or

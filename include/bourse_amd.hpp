@@ -368,6 +368,33 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_lags_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-book flow table of the trade records (bk_flow_enable): 8 + 6 n_lags u64 words per book - the base words, then lag rows
+  // 1 .. n_lags in trade time (BK_FLOW_*) - folded on the device from each book's trade records (needs trade_capacity > 0);
+  // no counterpart in the reference
+  void enable_flow(uint32_t n_lags = 16, bool consume_trades = false) {
+    check(bk_flow_enable(h_, n_lags, consume_trades ? 1 : 0));
+    flow_lags_ = n_lags;
+  }
+  // queue one launch that folds every book's new trade records (no host wait)
+  void fold_flow() { check(bk_flow_fold(h_)); }
+  // words [n_books][8 + 6 n_lags] of books [first_book, first_book + n_books) (waits for the env's stream; does not fold)
+  std::vector<uint64_t> flow(uint32_t first_book, uint32_t n_books) {
+    std::vector<uint64_t> words(static_cast<size_t>(n_books) * (BK_FLOW_BASE_WORDS + BK_FLOW_LAG_WORDS * flow_lags_));
+    check(bk_get_flow(h_, first_book, n_books, words.data()));
+    return words;
+  }
+  std::vector<uint64_t> flow() { return flow(0, n_books_); }
+  // the table in device memory, uint64_t[n_books][8 + 6 n_lags]
+  uint64_t* flow_device_ptr() {
+    void* p = nullptr;
+    check(bk_flow_device_ptr(h_, &p));
+    return static_cast<uint64_t*>(p);
+  }
+  // a mask (one byte per book): fold, then clear those books' words and carry; an empty mask: clear all without folding
+  void clear_flow(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
+    check(bk_flow_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // per-book bin table of the level-2 history (bk_bins_enable): n_spans + 2 rows of n_bins u64 counts per book - the change
   // of twice the mid over each span, the spread, the traded volume - folded on the device from the history ring (needs
   // history_capacity > 0); no counterpart in the reference
@@ -459,7 +486,7 @@ class ManyEnv {
 
  private:
   bk_env* h_ = nullptr;
-  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0, bins_per_book_ = 0;
+  uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0, bins_per_book_ = 0, flow_lags_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
