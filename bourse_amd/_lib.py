@@ -164,6 +164,59 @@ def series_moments(rows) -> np.ndarray:
     return out
 
 
+# the depth table (ManyBookEnv.depth): per book levels + 1 rows of 16 words of 8 bytes - a level's row, and the header's
+DEPTH_FIELDS = ("sum_bid_vol", "sum_ask_vol", "sum_bid_vol_sq", "sum_ask_vol_sq", "sum_bid_orders", "sum_ask_orders", "n_bid_steps",
+                "n_ask_steps", "sum_imb", "sum_imb_sq", "n_signed", "sum_sign_d", "n_agree", "sum_imb_d", "n_move", "sum_abs_imb")
+DEPTH_HEADER_FIELDS = ("n_steps", "n_two_sided", "n_pairs", "sum_d", "sum_abs_d", "n_up", "n_down", "n_bid_side", "n_ask_side")
+DEPTH_SIGNED = ("sum_imb", "sum_sign_d", "sum_imb_d")
+DEPTH_ROW_WORDS = 16
+
+DEPTH_MOMENTS_DTYPE = np.dtype([(n, "<f8") for n in (
+    "mean_bid_vol", "mean_ask_vol", "var_bid_vol", "var_ask_vol", "mean_bid_orders", "mean_ask_orders", "bid_occupancy",
+    "ask_occupancy", "mean_imb", "var_imb", "response", "hit_rate", "slope")])
+
+
+def depth_moments(rows) -> np.ndarray:
+    """Depth rows ``[n_books, L + 1, 16]`` (``ManyBookEnv.depth()``; one book's ``[L + 1, 16]`` too) -> float64 moments per
+    book and level, ``[n_books, L]`` (``DEPTH_MOMENTS_DTYPE``).  Per step, from the header's ``n_steps``: ``mean_bid_vol``,
+    ``mean_ask_vol``, ``var_bid_vol``, ``var_ask_vol`` (population variances), ``mean_bid_orders``, ``mean_ask_orders`` and
+    the share of steps at which the level held an order, ``bid_occupancy``, ``ask_occupancy``.  Over two-sided steps
+    (``n_two_sided``): ``mean_imb`` and ``var_imb`` of the cumulative imbalance ``I_q``.  Over pairs of consecutive two-sided
+    steps, with ``J`` the imbalance of the first and ``d`` the change of TWICE the mid: ``response`` = sum_sign_d / n_signed
+    / 2, the mean move of the mid in the direction the imbalance pointed, in mid-price units; ``hit_rate`` = n_agree /
+    n_move, how often a move went that way; ``slope`` = sum_imb_d / sum_imb_sq, the regression of ``d`` on ``J`` through
+    the origin.  NaN where a count or a denominator is 0.  The words are read as they are: a sum that has wrapped modulo
+    2^64 is not detected."""
+    rows = np.asarray(rows)
+    if rows.ndim == 2:
+        rows = rows[None]
+    if rows.ndim != 3 or rows.shape[1] < 2 or rows.shape[2] != DEPTH_ROW_WORDS or rows.dtype.kind not in "iu" or rows.dtype.itemsize != 8:
+        raise ValueError("depth_moments needs 64-bit integer rows [n_books, levels + 1, 16]")
+    u = np.ascontiguousarray(rows).view(np.uint64)
+    w = {n: (u[:, :-1, i].view(np.int64) if n in DEPTH_SIGNED else u[:, :-1, i]).astype(np.float64) for i, n in enumerate(DEPTH_FIELDS)}
+    h = {n: u[:, -1:, i].astype(np.float64) for i, n in enumerate(DEPTH_HEADER_FIELDS)}
+    out = np.full((u.shape[0], u.shape[1] - 1), np.nan, dtype=DEPTH_MOMENTS_DTYPE)
+
+    def div(a, b):
+        b = np.broadcast_to(b, a.shape)
+        return np.divide(a, b, out=np.full(a.shape, np.nan), where=b != 0)
+
+    ns, n2 = h["n_steps"], h["n_two_sided"]
+    for side in ("bid", "ask"):
+        mean = div(w[f"sum_{side}_vol"], ns)
+        out[f"mean_{side}_vol"] = mean
+        out[f"var_{side}_vol"] = div(w[f"sum_{side}_vol_sq"], ns) - mean * mean
+        out[f"mean_{side}_orders"] = div(w[f"sum_{side}_orders"], ns)
+        out[f"{side}_occupancy"] = div(w[f"n_{side}_steps"], ns)
+    mean = div(w["sum_imb"], n2)
+    out["mean_imb"] = mean
+    out["var_imb"] = div(w["sum_imb_sq"], n2) - mean * mean
+    out["response"] = div(w["sum_sign_d"], w["n_signed"]) / 2.0
+    out["hit_rate"] = div(w["n_agree"], w["n_move"])
+    out["slope"] = div(w["sum_imb_d"], w["sum_imb_sq"])
+    return out
+
+
 # bk_lag_row: one book's row of one lag of the lag table (ManyBookEnv.lags), 10 words of 8 bytes
 LAG_FIELDS = ("n_pairs", "sum_dd", "sum_abs_dd", "n_h", "sum_h", "sum_abs_h", "sum_h2", "sum_h4_lo", "sum_h4_hi", "max_abs_h")
 LAG_SIGNED = ("sum_dd", "sum_h")
@@ -521,6 +574,9 @@ SIGNATURES = {
     "bk_series_clear_device": (_i32, [_vp, _vp]),
     "bk_series_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_series": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_depth_enable": (_i32, [_vp]),
+    "bk_depth_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_depth": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_lags_enable": (_i32, [_vp, _u32]),
     "bk_lags_fold": (_i32, [_vp]),
     "bk_lags_clear": (_i32, [_vp, _vp]),

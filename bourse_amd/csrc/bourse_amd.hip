@@ -54,6 +54,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "ingress_reset.hpp"
 #include "accounts.hpp"
 #include "trade_bars.hpp"
+#include "depth.hpp"
 #include "series.hpp"
 #include "open_orders.hpp"
 #include "open_queue.hpp"
@@ -298,6 +299,10 @@ struct bk_env {
       {"bin table", "bin table", "a ", "bins", launch_bins_fold, launch_bins_clear}};
   // bk_series_enable: one row of series moments per book [n_books] of 192 B (series.hpp)
   DevBuf<bk_u32x4> series_rows;
+  // bk_depth_enable: the series' companion over the ladder, (levels + 1) rows of 128 B per book [n_books][L + 1][8] vectors
+  // and the carry [n_books][L + 1] (depth.hpp); folded, cleared and cut by the series' two launches, with no cursor of its own
+  DevBuf<bk_u32x4> depth_rows;
+  DevBuf<uint64_t> depth_carry;
   // bk_lags_enable: n_lags rows per book [n_books][n_lags] of 80 B and the carry [n_books][n_lags + 1] (lags.hpp)
   DevBuf<bk_u32x4> lag_rows;
   DevBuf<uint64_t> lag_carry;
@@ -2865,6 +2870,14 @@ static void launch_series_fold(bk_env* env, const ring::Span& span) {
   g.ring = span;
   g.rows = env->series_rows.p;
   launch_wave_per_book(env, series::k_fold, series::FOLD_WAVES, span.n_books, g);
+  if (env->depth_rows.p) {  // the ladder's companion table: the same span, right behind
+    depth::FoldArgs d{};
+    d.ring = span;
+    d.L = env->cfg.levels;
+    d.rows = env->depth_rows.p;
+    d.carry = env->depth_carry.p;
+    launch_wave_per_book(env, depth::k_fold, depth::FOLD_WAVES, span.n_books, d);
+  }
 }
 
 static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
@@ -2873,6 +2886,15 @@ static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M
   g.carry_only = carry_only ? 1u : 0u;
   g.rows = env->series_rows.p;
   launch_wave_per_book(env, series::k_clear, series::FOLD_WAVES, g.books.n_books, g);
+  if (env->depth_rows.p) {
+    depth::ClearArgs d{};
+    d.books = g.books;
+    d.L = env->cfg.levels;
+    d.carry_only = g.carry_only;
+    d.rows = env->depth_rows.p;
+    d.carry = env->depth_carry.p;
+    launch_wave_per_book(env, depth::k_clear, depth::FOLD_WAVES, d.books.n_books, d);
+  }
 }
 
 static void launch_lags_fold(bk_env* env, const ring::Span& span) {
@@ -4312,6 +4334,57 @@ int bk_series_device_ptr(bk_env* env, void** out) {
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out) {
   if (int rc = table_ok(env, T_SERIES)) return rc;
   return get_book_rows(env, first_book, n_books, {{env->series_rows.p, sizeof(bk_series_row), out}});
+}
+
+// ------------------------------------------------------------------ per-book depth table, the series' companion
+// No counterpart in the reference.  depth_rows[n_books][levels + 1] rows of 16 u64 words and depth_carry[n_books][levels + 1]
+// (depth.hpp): no HistTable of its own - the series' cursor, fold, clear and cut act on both tables.
+static int depth_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->depth_rows.p) return fail(BK_INVALID_ARGUMENT, "this env has no depth table: call bk_depth_enable first");
+  return BK_OK;
+}
+
+int bk_depth_enable(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->tables[T_SERIES].on)
+    return fail(BK_INVALID_ARGUMENT, "the depth table is the series moments' companion and shares their cursor: call bk_series_enable first");
+  if (env->depth_rows.p) return fail(BK_INVALID_ARGUMENT, "the depth table is already enabled on this env");
+  static_assert(depth::MAX_LEVELS == 64, "cfg.levels is 1..64");
+  // the series' outstanding steps first (lost steps refuse, the env unchanged): both tables then stand at steps_done
+  if (int rc = table_fold(env, T_SERIES)) return rc;
+  if (int rc = use_device(env)) return rc;
+  const size_t rows_per_book = env->cfg.levels + 1u;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<uint64_t> carry;
+  HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * rows_per_book * depth::ROW_VECS));
+  HIPCHK(carry.alloc(static_cast<size_t>(env->cfg.n_books) * rows_per_book));
+  depth::ClearArgs d{};
+  d.books = masked_books(env, nullptr, 1);
+  d.L = env->cfg.levels;
+  d.carry_only = 0u;
+  d.rows = rows.p;
+  d.carry = carry.p;
+  launch_wave_per_book(env, depth::k_clear, depth::FOLD_WAVES, d.books.n_books, d);
+  const hipError_t launched = hipGetLastError();
+  if (launched != hipSuccess)  // the env stays without the table: the new blocks leave with `rows` and `carry`
+    return fail(BK_HIP_ERROR, std::string("bk_depth_enable: the clear could not be launched: ") + hipGetErrorString(launched));
+  env->depth_rows.swap(rows);
+  env->depth_carry.swap(carry);
+  return BK_OK;
+}
+
+int bk_depth_device_ptr(bk_env* env, void** out) {
+  if (int rc = depth_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->depth_rows.p;
+  return BK_OK;
+}
+
+int bk_get_depth(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out) {
+  if (int rc = depth_ok(env)) return rc;
+  return get_book_rows(env, first_book, n_books,
+                       {{env->depth_rows.p, (env->cfg.levels + 1u) * static_cast<size_t>(depth::ROW_WORDS) * sizeof(uint64_t), out}});
 }
 
 // ------------------------------------------------------------------ per-book lag table

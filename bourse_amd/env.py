@@ -1371,6 +1371,34 @@ class ManyBookEnv:
                 fold()
             left -= n
 
+    # ------------------------------------------------------------ per-level depth table, the series moments' companion
+    def enable_depth(self):
+        """``bk_depth_enable``: beside the series moments keep ``levels + 1`` rows of sixteen integer sums per book in
+        device memory, folded from the LADDER of the level-2 records - per level the sums of the resting volume, its
+        square and the order count on either side and how often the level was occupied, the sums of the cumulative depth
+        imbalance ``I_q``, and of the next move of the mid against it (``bourse_amd.DEPTH_FIELDS``); in the last row the
+        header (``DEPTH_HEADER_FIELDS``).  Needs ``enable_series()`` first and shares its cursor: ``fold_series``,
+        ``clear_series``, ``run_series``, the resets (which cut the carry) and ``restore`` (which clears) act on both
+        tables.  Folds the series' outstanding steps first - and refuses as ``fold_series`` does if steps were lost - so
+        the depth rows count from the current step on.  ``depth_moments`` turns the rows into moments.  The reference has
+        no counterpart."""
+        check(self._L.bk_depth_enable(self._h))
+
+    def depth(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The rows of books ``[first_book, first_book + n_books)`` (default: to the last book) as a uint64 array of
+        shape ``[n, levels + 1, 16]``.  Waits for the env's stream; does NOT fold (``fold_series`` folds both tables)."""
+        return self._book_rows(self._L.bk_get_depth, first_book, n_books, ((self.levels + 1, _lib.DEPTH_ROW_WORDS), np.uint64))[0]
+
+    def depth_device_ptr(self) -> int:
+        """Device address of the table, ``uint64_t[n_books][levels + 1][16]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_depth_device_ptr)
+
+    def depth_view(self) -> "DepthView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, levels + 1, 16)``
+        (unsigned words read as int64: the same bits).  ``torch.as_tensor(env.depth_view(), device="cuda")`` is a zero-copy
+        tensor that every later fold updates; it is written on the env's stream, so read it there (or after ``sync()``)."""
+        return DepthView(self, self.depth_device_ptr(), (self.n_books, self.levels + 1, _lib.DEPTH_ROW_WORDS), self._stream)
+
     # ------------------------------------------------------------ per-book lag table of the level-2 history
     LAG_DTYPE = _lib.LAG_DTYPE
 
@@ -1741,6 +1769,10 @@ class TradeBarsView(AccountsView):
 
 class SeriesView(AccountsView):
     """``ManyBookEnv.series_view()``: the table of series moments where it lives, read the same way."""
+
+
+class DepthView(AccountsView):
+    """``ManyBookEnv.depth_view()``: the depth table where it lives, read the same way."""
 
 
 class LagsView(AccountsView):

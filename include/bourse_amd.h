@@ -807,6 +807,55 @@ int bk_series_device_ptr(bk_env* env, void** out);
  * (No counterpart in the reference.) */
 int bk_get_series(bk_env* env, uint32_t first_book, uint32_t n_books, bk_series_row* out);
 
+/* ------------------------------------------------------ per-level depth table, the series moments' companion */
+/* An opt-in table depth[n_books][L + 1][16] of uint64_t in DEVICE memory, L = cfg.levels (1..64), 128 B a row: the LADDER
+ * half of the series moments.  bk_series_* reads words 0..4 of a level-2 record; this table reads the other 4 L, the levels
+ * {bid_vol_i, bid_n_i, ask_vol_i, ask_n_i} as the stepping kernels wrote them - per level the sums behind the average book
+ * shape (mean and variance of resting volume and order count, how often the level is occupied) and behind the response of
+ * the next move of the mid to the cumulative depth imbalance (bourse_amd/csrc/depth.hpp, depth_fold.hpp).
+ * It is no table of its own: it shares the series' cursor, and bk_series_fold, bk_series_clear*, bk_reset_books* and
+ * bk_ingress_reset_books* (which cut the carry), bk_checkpoint_load (which clears) act on both tables.  It has no fold or
+ * clear entry and adds no flag bit.
+ *
+ * What one record adds.  Let level q of the record of step s be bv, bn, av, an; two = the step is two-sided (bid != 0 &&
+ * ask != 0xFFFFFFFF); m = bid + ask; I_q = sum_{i <= q} bv_i - sum_{i <= q} av_i, an exact integer (|I_q| < 2^38).  A PAIR
+ * is two consecutive folded steps s - 1, s, both two-sided, with no cut between them; for a pair d = m_s - m_{s-1} and
+ * J = I_q(s - 1).  Row q < L, word by word:
+ *    0, 1  sum_bid_vol, sum_ask_vol         sum of bv, of av, over every step
+ *    2, 3  sum_bid_vol_sq, sum_ask_vol_sq   sum of bv^2, of av^2
+ *    4, 5  sum_bid_orders, sum_ask_orders   sum of bn, of an
+ *    6, 7  n_bid_steps, n_ask_steps         steps with bn > 0, with an > 0
+ *    8     sum_imb                          sum of I_q over two-sided steps (signed)
+ *    9     sum_imb_sq                       sum of I_q^2 over two-sided steps
+ *   10     n_signed                         pairs with J != 0
+ *   11     sum_sign_d                       sum of sgn(J) * d over pairs (signed)
+ *   12     n_agree                          pairs with sgn(J) * d > 0
+ *   13     sum_imb_d                        sum of J * d over pairs (signed)
+ *   14     n_move                           pairs with J != 0 and d != 0
+ *   15     sum_abs_imb                      sum of |I_q| over two-sided steps
+ * Row L, the header: 0 n_steps (steps folded since the last clear), 1 n_two_sided, 2 n_pairs, 3 sum_d (signed), 4 sum_abs_d,
+ * 5 n_up, 6 n_down (pairs with d > 0, with d < 0), 7 n_bid_side, 8 n_ask_side (steps with bid != 0, with ask != 0xFFFFFFFF),
+ * 9..15 zero.  All sums are modulo 2^64; signed words are two's complement.  With a huge tick several levels may alias:
+ * that is the record's affair, the table takes the levels as they stand.
+ *
+ * The carry, uint64_t[n_books][L + 1], is I_q of the last folded step per level and then that step's window word (bit 63
+ * set if two-sided, the low bits m).  A cut zeroes the whole carry, so no pair reaches over a reset and the sums go on.
+ * Folding steps [x, y) and then [y, z) leaves exactly the rows and carry of one fold over [x, z), for every split.
+ *
+ * Enabling.  Needs bk_series_enable on the same env (else BK_INVALID_ARGUMENT, bk_last_error() names bk_series_enable);
+ * refuses a second call.  First folds the series' outstanding steps - if steps were lost that fold refuses as
+ * bk_series_fold does, and so does the enable, the env unchanged - then allocates and clears rows and carry: both tables
+ * stand at bk_steps_done and the depth rows count from here.  A clear that cannot be launched leaves the env without the
+ * table.  An env without it launches nothing new.  (No counterpart in the reference.) */
+int bk_depth_enable(bk_env* env);
+/* Device pointer of the table, uint64_t[n_books][L + 1][16], for on-device consumers; valid for the env's life, written on
+ * the env's stream.  On an env without the table: BK_INVALID_ARGUMENT, "this env has no depth table: call bk_depth_enable
+ * first".  (No counterpart in the reference.) */
+int bk_depth_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory, (L + 1) * 16 words per book.  Waits for the env's
+ * stream; does NOT fold (bk_series_fold folds both tables).  (No counterpart in the reference.) */
+int bk_get_depth(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
+
 /* ------------------------------------------------------ per-book lag table of the level-2 history */
 /* An opt-in table lags[n_books][n_lags] in DEVICE memory, n_lags = K, 1 <= K <= 64: per book and lag k = 1 .. K the sums
  * behind the autocorrelation of the mid's step-to-step change and of its magnitude at lag k (volatility clustering), and

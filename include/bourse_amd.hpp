@@ -342,6 +342,22 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_series_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-level depth table (bk_depth_enable): the series moments' companion over the ladder of the level-2 records, levels + 1
+  // rows of 16 words per book; needs enable_series() and shares its fold, clears and cuts; no counterpart in the reference
+  void enable_depth() { check(bk_depth_enable(h_)); }
+  // (levels + 1) * 16 words per book of books [first_book, first_book + n_books) (waits for the env's stream; does not fold)
+  std::vector<uint64_t> depth(uint32_t first_book, uint32_t n_books) {
+    std::vector<uint64_t> rows(static_cast<size_t>(n_books) * (levels_ + 1u) * 16u);
+    check(bk_get_depth(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<uint64_t> depth() { return depth(0, n_books_); }
+  // the table in device memory, uint64_t[n_books][levels + 1][16]
+  uint64_t* depth_device_ptr() {
+    void* p = nullptr;
+    check(bk_depth_device_ptr(h_, &p));
+    return static_cast<uint64_t*>(p);
+  }
   // per-book lag table of the level-2 history (bk_lags_enable): n_lags rows (1 .. 64) of integer sums per book, row k - 1
   // for lag / span k, folded on the device from the history ring (needs history_capacity > 0); no counterpart in the reference
   void enable_lags(uint32_t n_lags) {
