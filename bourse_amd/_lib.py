@@ -217,6 +217,61 @@ def depth_moments(rows) -> np.ndarray:
     return out
 
 
+# the candle table (ManyBookEnv.candles): per book n_candles rows of 16 words of 8 bytes, one bar of `width` steps each
+CANDLE_FIELDS = ("first_step", "n_steps", "n_two_sided", "open_m", "high_m", "low_m", "close_m", "sum_m", "sum_spread", "sum_trade_vol",
+                 "n_trade_steps", "n_ret", "sum_d", "sum_abs_d", "sum_d2", "max_abs_d")
+CANDLE_SIGNED = ("sum_d",)
+CANDLE_ROW_WORDS = 16
+CANDLE_DTYPE = np.dtype({"names": list(CANDLE_FIELDS), "formats": ["<i8" if n in CANDLE_SIGNED else "<u8" for n in CANDLE_FIELDS],
+                         "offsets": [8 * i for i in range(CANDLE_ROW_WORDS)], "itemsize": 8 * CANDLE_ROW_WORDS})
+
+CANDLE_SERIES_DTYPE = np.dtype([(n, "<f8") for n in ("open", "high", "low", "close", "twap", "mean_spread", "volume", "trade_share",
+                                                     "realized_var")] + [("bar", "<i8"), ("complete", "?")])
+
+
+def candle_series(rows, width: int) -> np.ndarray:
+    """``CANDLE_DTYPE`` rows ``[n_books, N]`` (``ManyBookEnv.candles()``; one book's ``[N]`` too) of bars of ``width`` steps
+    -> per book the bars ordered OLDEST TO NEWEST, ``[n_books, N]`` (``CANDLE_SERIES_DTYPE``), empty slots first.  In
+    mid-price units: ``open``, ``high``, ``low``, ``close`` (the words over 2), ``twap`` = sum_m / (2 n_two_sided),
+    ``mean_spread`` = sum_spread / n_two_sided, ``realized_var`` = sum_d2 / 4 (the sum of the squared changes of the mid
+    whose later step lies in the bar).  ``volume`` = sum_trade_vol, ``trade_share`` = n_trade_steps / n_steps.  ``bar`` is
+    the bar's index first_step // width, -1 for a slot that holds no bar; ``complete`` = n_steps == width (the newest bar,
+    and the first behind an enable or a clear, may be partial).  A value is NaN where its count is 0.  The words are read as
+    they are: a sum that has wrapped modulo 2^64 is not detected."""
+    rows = np.asarray(rows)
+    if rows.dtype != CANDLE_DTYPE:
+        raise ValueError("candle_series needs CANDLE_DTYPE rows")
+    width = int(width)
+    if width < 1:
+        raise ValueError("width must be >= 1")
+    if rows.ndim == 1:
+        rows = rows[None]
+    if rows.ndim != 2:
+        raise ValueError("candle_series needs rows [n_books, n_candles]")
+    n_steps = rows["n_steps"]
+    bar = np.where(n_steps > 0, (rows["first_step"] // np.uint64(width)).astype(np.int64), np.int64(-1))
+    order = np.argsort(bar, axis=1, kind="stable")
+    rows, bar = np.take_along_axis(rows, order, axis=1), np.take_along_axis(bar, order, axis=1)
+    out = np.zeros(rows.shape, dtype=CANDLE_SERIES_DTYPE)
+
+    def div(a, b):
+        a, b = a.astype(np.float64), b.astype(np.float64)
+        return np.divide(a, b, out=np.full(a.shape, np.nan), where=b != 0)
+
+    n2, ns = rows["n_two_sided"], rows["n_steps"]
+    one = np.ones(rows.shape)
+    for name, word in (("open", "open_m"), ("high", "high_m"), ("low", "low_m"), ("close", "close_m")):
+        out[name] = div(rows[word], (n2 > 0) * one) / 2.0
+    out["twap"] = div(rows["sum_m"], n2) / 2.0
+    out["mean_spread"] = div(rows["sum_spread"], n2)
+    out["volume"] = div(rows["sum_trade_vol"], (ns > 0) * one)
+    out["trade_share"] = div(rows["n_trade_steps"], ns)
+    out["realized_var"] = div(rows["sum_d2"], (rows["n_ret"] > 0) * one) / 4.0
+    out["bar"] = bar
+    out["complete"] = ns == np.uint64(width)
+    return out
+
+
 # bk_lag_row: one book's row of one lag of the lag table (ManyBookEnv.lags), 10 words of 8 bytes
 LAG_FIELDS = ("n_pairs", "sum_dd", "sum_abs_dd", "n_h", "sum_h", "sum_abs_h", "sum_h2", "sum_h4_lo", "sum_h4_hi", "max_abs_h")
 LAG_SIGNED = ("sum_dd", "sum_h")
@@ -577,6 +632,10 @@ SIGNATURES = {
     "bk_depth_enable": (_i32, [_vp]),
     "bk_depth_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_depth": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_candles_enable": (_i32, [_vp, _u32, _u32]),
+    "bk_candles_config_get": (_i32, [_vp, C.POINTER(_u32)]),
+    "bk_candles_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_candles": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_lags_enable": (_i32, [_vp, _u32]),
     "bk_lags_fold": (_i32, [_vp]),
     "bk_lags_clear": (_i32, [_vp, _vp]),

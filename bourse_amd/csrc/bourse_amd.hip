@@ -55,6 +55,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "accounts.hpp"
 #include "trade_bars.hpp"
 #include "depth.hpp"
+#include "candles.hpp"
 #include "series.hpp"
 #include "open_orders.hpp"
 #include "open_queue.hpp"
@@ -303,6 +304,11 @@ struct bk_env {
   // and the carry [n_books][L + 1] (depth.hpp); folded, cleared and cut by the series' two launches, with no cursor of its own
   DevBuf<bk_u32x4> depth_rows;
   DevBuf<uint64_t> depth_carry;
+  // bk_candles_enable: the series' other companion, the last candle_n bars of candle_width steps per book [n_books][N][8]
+  // vectors of 128 B a bar and the carry [n_books] (candles.hpp); folded, cleared and cut by the series' two launches too
+  DevBuf<bk_u32x4> candle_rows;
+  DevBuf<uint64_t> candle_carry;
+  uint32_t candle_width = 0, candle_n = 0;
   // bk_lags_enable: n_lags rows per book [n_books][n_lags] of 80 B and the carry [n_books][n_lags + 1] (lags.hpp)
   DevBuf<bk_u32x4> lag_rows;
   DevBuf<uint64_t> lag_carry;
@@ -2878,6 +2884,19 @@ static void launch_series_fold(bk_env* env, const ring::Span& span) {
     d.carry = env->depth_carry.p;
     launch_wave_per_book(env, depth::k_fold, depth::FOLD_WAVES, span.n_books, d);
   }
+  if (env->candle_rows.p) {  // the bars' companion table: the same span; its first step is the series' cursor, not yet advanced
+    const uint64_t seen = env->tables[T_SERIES].seen;
+    candles::FoldArgs c{};
+    c.ring = span;
+    c.W = env->candle_width;
+    c.N = env->candle_n;
+    const candles::Pass at = candles::first_pass(seen, c.W, c.N);
+    c.bar = at.bar, c.phase = at.phase, c.slot = at.slot;
+    c.last_bar = candles::bar_of(seen + span.n - 1u, c.W);
+    c.rows = env->candle_rows.p;
+    c.carry = env->candle_carry.p;
+    launch_wave_per_book(env, candles::k_fold, candles::FOLD_WAVES, span.n_books, c);
+  }
 }
 
 static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, bool carry_only) {
@@ -2894,6 +2913,15 @@ static void launch_series_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M
     d.rows = env->depth_rows.p;
     d.carry = env->depth_carry.p;
     launch_wave_per_book(env, depth::k_clear, depth::FOLD_WAVES, d.books.n_books, d);
+  }
+  if (env->candle_rows.p) {
+    candles::ClearArgs c{};
+    c.books = g.books;
+    c.N = env->candle_n;
+    c.carry_only = g.carry_only;
+    c.rows = env->candle_rows.p;
+    c.carry = env->candle_carry.p;
+    launch_wave_per_book(env, candles::k_clear, candles::FOLD_WAVES, c.books.n_books, c);
   }
 }
 
@@ -4385,6 +4413,66 @@ int bk_get_depth(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* o
   if (int rc = depth_ok(env)) return rc;
   return get_book_rows(env, first_book, n_books,
                        {{env->depth_rows.p, (env->cfg.levels + 1u) * static_cast<size_t>(depth::ROW_WORDS) * sizeof(uint64_t), out}});
+}
+
+// ------------------------------------------------------------------ per-book candle table, the series' companion
+// No counterpart in the reference.  candle_rows[n_books][candle_n] rows of 16 u64 words and candle_carry[n_books]
+// (candles.hpp): no HistTable of its own - the series' cursor, fold, clear and cut act on it too.
+static int candles_ok(bk_env* env) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->candle_rows.p) return fail(BK_INVALID_ARGUMENT, "this env has no candle table: call bk_candles_enable first");
+  return BK_OK;
+}
+
+int bk_candles_enable(bk_env* env, uint32_t width, uint32_t n_candles) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!env->tables[T_SERIES].on)
+    return fail(BK_INVALID_ARGUMENT, "the candle table is the series moments' companion and shares their cursor: call bk_series_enable first");
+  if (env->candle_rows.p) return fail(BK_INVALID_ARGUMENT, "the candle table is already enabled on this env");
+  if (width < 1u || width > candles::MAX_WIDTH) return fail(BK_INVALID_ARGUMENT, "width must be in 1..1048576 steps a bar");
+  if (n_candles < 1u || n_candles > candles::MAX_CANDLES) return fail(BK_INVALID_ARGUMENT, "n_candles must be in 1..65536 bars a book");
+  // the series' outstanding steps first (lost steps refuse, the env unchanged): both tables then stand at steps_done
+  if (int rc = table_fold(env, T_SERIES)) return rc;
+  if (int rc = use_device(env)) return rc;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<uint64_t> carry;
+  HIPCHK(rows.alloc(static_cast<size_t>(env->cfg.n_books) * n_candles * candles::ROW_VECS));
+  HIPCHK(carry.alloc(static_cast<size_t>(env->cfg.n_books)));
+  candles::ClearArgs c{};
+  c.books = masked_books(env, nullptr, 1);
+  c.N = n_candles;
+  c.carry_only = 0u;
+  c.rows = rows.p;
+  c.carry = carry.p;
+  launch_wave_per_book(env, candles::k_clear, candles::FOLD_WAVES, c.books.n_books, c);
+  const hipError_t launched = hipGetLastError();
+  if (launched != hipSuccess)  // the env stays without the table: the new blocks leave with `rows` and `carry`
+    return fail(BK_HIP_ERROR, std::string("bk_candles_enable: the clear could not be launched: ") + hipGetErrorString(launched));
+  env->candle_rows.swap(rows);
+  env->candle_carry.swap(carry);
+  env->candle_width = width;
+  env->candle_n = n_candles;
+  return BK_OK;
+}
+
+int bk_candles_config_get(bk_env* env, uint32_t out[2]) {
+  if (int rc = candles_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  out[0] = env->candle_width, out[1] = env->candle_n;
+  return BK_OK;
+}
+
+int bk_candles_device_ptr(bk_env* env, void** out) {
+  if (int rc = candles_ok(env)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->candle_rows.p;
+  return BK_OK;
+}
+
+int bk_get_candles(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out) {
+  if (int rc = candles_ok(env)) return rc;
+  return get_book_rows(env, first_book, n_books,
+                       {{env->candle_rows.p, env->candle_n * static_cast<size_t>(candles::ROW_WORDS) * sizeof(uint64_t), out}});
 }
 
 // ------------------------------------------------------------------ per-book lag table

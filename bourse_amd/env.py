@@ -189,6 +189,7 @@ class ManyBookEnv:
         self._n_traders = 0       # enable_accounts
         self._bars_window = 0     # enable_trade_bars
         self._series = False      # enable_series
+        self._candles = None      # enable_candles: width, n_candles and where the series' cursor stood / stands
         self._n_lags = 0          # enable_lags
         self._flow_lags = 0       # enable_flow
         self._bins_shape = None   # enable_bins: (n_spans + 2, n_bins)
@@ -1122,6 +1123,7 @@ class ManyBookEnv:
             raise _lib.BourseError(_lib.BK_INVALID, f"restore: {buf.nbytes} bytes is not a checkpoint of this env's shape ({n} bytes, "
                                                    f"or {n + tail} with the reported-flags trailer)")
         check(self._L.bk_checkpoint_load(self._h, buf.ctypes.data_as(C.c_void_p), n))
+        self._candles_folded(restart=True)
         self._flags_sticky, self._warned_bits = None, 0
         if has_tail:
             self._flags_sticky = buf[n + 16:].view(np.uint32).copy()
@@ -1174,6 +1176,7 @@ class ManyBookEnv:
                 raise ValueError(f"mask / seeds: {n_units} elements are needed ({per})")
             check(host_entry(self._h, int(slot), m.ctypes.data_as(C.c_void_p),
                              None if s is None else s.ctypes.data_as(C.c_void_p)))
+        self._candles_folded()  # (a reset folds the series' outstanding steps first)
         if sync:
             self.sync()
 
@@ -1319,6 +1322,7 @@ class ManyBookEnv:
         ``clear_history()`` - naming how many were lost; rows and cursor are then unchanged and ``clear_series()`` starts
         again."""
         check(self._L.bk_series_fold(self._h))
+        self._candles_folded()
         if sync:
             self.sync()
 
@@ -1346,6 +1350,7 @@ class ManyBookEnv:
         the carry of the books they reset: the sums go on across episodes and no return spans a reset."""
         # (no check of its own in front: the library refuses an env without the table)
         self._masked_clear(self._L.bk_series_clear_device, self._L.bk_series_clear, mask, sync)
+        self._candles_folded(restart=mask is None)
 
     def run_series(self, n_steps: int, chunk: Optional[int] = None):
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
@@ -1398,6 +1403,71 @@ class ManyBookEnv:
         (unsigned words read as int64: the same bits).  ``torch.as_tensor(env.depth_view(), device="cuda")`` is a zero-copy
         tensor that every later fold updates; it is written on the env's stream, so read it there (or after ``sync()``)."""
         return DepthView(self, self.depth_device_ptr(), (self.n_books, self.levels + 1, _lib.DEPTH_ROW_WORDS), self._stream)
+
+    # ------------------------------------------------------------ per-book candle table, the series moments' other companion
+    CANDLE_DTYPE = _lib.CANDLE_DTYPE
+
+    def enable_candles(self, width: int, n_candles: int):
+        """``bk_candles_enable``: beside the series moments keep per book a ring of the last ``n_candles`` (1 .. 65536) bars
+        of ``width`` (1 .. 1048576) steps each in device memory, sixteen integer words a bar, folded from the same level-2
+        records: open / high / low / close of twice the mid, the sums behind the time-weighted mid and spread, the traded
+        volume, and the returns' sums up to the realised variance (``bourse_amd.CANDLE_FIELDS`` / ``CANDLE_DTYPE``;
+        include/bourse_amd.h states what one record adds).  Bars are aligned to the env's absolute step count, the same
+        for every book: step ``s`` is of bar ``s // width`` in slot ``(s // width) % n_candles``.  Needs ``enable_series()``
+        first and shares its cursor: ``fold_series``, ``clear_series``, ``run_series``, the resets (which cut the carry)
+        and ``restore`` (which clears) act on it too; ``enable_depth`` may stand beside it, in either order.  Folds the
+        series' outstanding steps first - and refuses as ``fold_series`` does if steps were lost - so the bars count from
+        the current step on.  ``candle_series`` turns the rows into prices.  The reference has no counterpart."""
+        for name, x in (("width", width), ("n_candles", n_candles)):
+            if not 0 <= int(x) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} out of range")
+        check(self._L.bk_candles_enable(self._h, int(width), int(n_candles)))
+        done = self.steps_done()
+        self._candles = {"width": int(width), "n": int(n_candles), "start": done, "seen": done}
+
+    def _candles_folded(self, restart: bool = False):
+        """a call that folded the series' outstanding steps has returned: the candle table stands at ``steps_done`` too
+        (``restart``: its rows were cleared as well)"""
+        c = getattr(self, "_candles", None)
+        if c is not None:
+            c["seen"] = self.steps_done()
+            if restart:
+                c["start"] = c["seen"]
+
+    def candles_config(self) -> Tuple[int, int]:
+        """``bk_candles_config_get``: ``(width, n_candles)`` as enabled."""
+        out = (C.c_uint32 * 2)()
+        check(self._L.bk_candles_config_get(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def candles(self, first_book: int = 0, n_books: Optional[int] = None) -> np.ndarray:
+        """The bars of books ``[first_book, first_book + n_books)`` (default: to the last book) as a structured array of
+        shape ``[n, n_candles]`` (``CANDLE_DTYPE``), slot by slot: bar ``j`` in slot ``j % n_candles``, ``n_steps == 0``
+        where a slot holds no bar.  Waits for the env's stream; does NOT fold (``fold_series`` folds both tables)."""
+        return self._book_rows(self._L.bk_get_candles, first_book, n_books, ((self.candles_config()[1],), _lib.CANDLE_DTYPE))[0]
+
+    def candles_device_ptr(self) -> int:
+        """Device address of the table, ``uint64_t[n_books][n_candles][16]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_candles_device_ptr)
+
+    def candles_view(self) -> "CandlesView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_books, n_candles, 16)``
+        (unsigned words read as int64: the same bits).  ``torch.as_tensor(env.candles_view(), device="cuda")`` is a
+        zero-copy tensor that every later fold updates; it is written on the env's stream, so read it there (or after
+        ``sync()``)."""
+        ptr = self.candles_device_ptr()
+        return CandlesView(self, ptr, (self.n_books, self.candles_config()[1], _lib.CANDLE_ROW_WORDS), self._stream)
+
+    def candles_latest(self) -> Optional[Tuple[int, int]]:
+        """``(bar, slot)`` of the newest folded bar - that of the last step in front of the series' cursor, the same for
+        every book - from host integers, with no wait; ``None`` while no step is folded since the enable, a full clear or
+        a restore."""
+        width, n = self.candles_config()
+        c = self._candles
+        if c["seen"] <= c["start"]:
+            return None
+        bar = (c["seen"] - 1) // width
+        return bar, bar % n
 
     # ------------------------------------------------------------ per-book lag table of the level-2 history
     LAG_DTYPE = _lib.LAG_DTYPE
@@ -1773,6 +1843,10 @@ class SeriesView(AccountsView):
 
 class DepthView(AccountsView):
     """``ManyBookEnv.depth_view()``: the depth table where it lives, read the same way."""
+
+
+class CandlesView(AccountsView):
+    """``ManyBookEnv.candles_view()``: the candle table where it lives, read the same way."""
 
 
 class LagsView(AccountsView):

@@ -856,6 +856,66 @@ int bk_depth_device_ptr(bk_env* env, void** out);
  * stream; does NOT fold (bk_series_fold folds both tables).  (No counterpart in the reference.) */
 int bk_get_depth(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
 
+/* ------------------------------------------------------ per-book candle table, the series moments' other companion */
+/* An opt-in table candles[n_books][N][16] of uint64_t in DEVICE memory, 128 B a row: per book a ring of the last N bars of W
+ * steps each - the PATH that bk_series_* collapses to one row: how mid, spread, volume and volatility evolved.  It reads
+ * words 0..2 of a level-2 record {trade_vol, bid_price, ask_price} as the stepping kernels wrote them
+ * (bourse_amd/csrc/candles.hpp, candle_fold.hpp).  It is no table of its own: it shares the series' cursor,
+ * and bk_series_fold, bk_series_clear*, bk_reset_books* and bk_ingress_reset_books* (which cut the carry), bk_checkpoint_load
+ * (which clears) act on it too.  It has no fold or clear entry and adds no flag bit.
+ *
+ * Bars are aligned to the env's absolute step count (bk_steps_done), the same for every book: step s belongs to bar
+ * j = s / W, and bar j lives in slot j % N of every book.  The newest folded bar is that of step seen - 1, seen the series'
+ * cursor - a host integer.
+ *
+ * What one record adds.  two = the step is two-sided (bid != 0 && ask != 0xFFFFFFFF); m = bid + ask, twice the mid (up to
+ * 33 bits).  A RETURN d = m_s - m_{s-1} exists where steps s - 1 and s are consecutive folded steps, both two-sided, with
+ * no cut between them - the series' own rule; it counts in the bar of the LATER step s, the earlier may lie in the bar
+ * before.  The row of bar j, word by word:
+ *    0  first_step     absolute step of the first record folded into this bar
+ *    1  n_steps        records folded into it; 0: the slot holds no bar; < W: a partial bar - the newest, or the first
+ *                      behind an enable or a clear
+ *    2  n_two_sided    records with two
+ *    3  open_m         m of the first two-sided step        (3..6 are 0 while n_two_sided == 0)
+ *    4  high_m         the largest m
+ *    5  low_m          the smallest m
+ *    6  close_m        m of the last two-sided step
+ *    7  sum_m          sum of m over two-sided steps; sum_m / (2 n_two_sided) is the time-weighted mid
+ *    8  sum_spread     sum of (ask - bid), a wrapping u32, over two-sided steps
+ *    9  sum_trade_vol  sum of trade_vol over every step
+ *   10  n_trade_steps  steps with trade_vol > 0
+ *   11  n_ret          returns whose later step lies in this bar
+ *   12  sum_d          sum of d (signed, two's complement)
+ *   13  sum_abs_d      sum of |d|
+ *   14  sum_d2         sum of d^2; divided by 4 the realised variance in mid-price units
+ *   15  max_abs_d      the largest |d|
+ * All sums are modulo 2^64.
+ *
+ * The merge.  The row of slot j % N is CONTINUED if n_steps > 0 and first_step / W == j, else RESTARTED with first_step the
+ * first folded step of bar j.  Folding steps [x, y) and then [y, z) leaves exactly the rows and carry of one fold over
+ * [x, z), for every split.  A fold may span more bars than N: bar j with j + N <= (the bar of the fold's last step) is then
+ * not written, its slot is a later bar's.  The carry, uint64_t[n_books], is the window word of the last folded step (bit
+ * 63 set if two-sided, the low bits m); a cut zeroes it, so no return reaches over a reset, and the rows go on.
+ *
+ * Enabling.  width W in 1..1048576, n_candles N in 1..65536 (else BK_INVALID_ARGUMENT).  Needs bk_series_enable on the same
+ * env (else BK_INVALID_ARGUMENT, bk_last_error() names bk_series_enable); refuses a second call.  First folds the series'
+ * outstanding steps - if steps were lost that fold refuses as bk_series_fold does, and so does the enable, the env
+ * unchanged - then allocates and clears rows and carry: the bars count from bk_steps_done on.  An allocation that fails is
+ * BK_HIP_ERROR and leaves the env without the table, as does a clear that cannot be launched.  An env without the table
+ * launches nothing new.  bk_depth_enable and this may both be called, in either order.  (No counterpart in the reference.) */
+int bk_candles_enable(bk_env* env, uint32_t width, uint32_t n_candles);
+/* out[0] = W, out[1] = N as enabled.  One record adds nothing here: the shape is fixed at the enable.  On an env without
+ * the table: BK_INVALID_ARGUMENT, "this env has no candle table: call bk_candles_enable first".
+ * (No counterpart in the reference.) */
+int bk_candles_config_get(bk_env* env, uint32_t out[2]);
+/* Device pointer of the table, uint64_t[n_books][N][16], for on-device consumers; valid for the env's life, written on the
+ * env's stream: one record adds to the one row of its bar's slot.  (No counterpart in the reference.) */
+int bk_candles_device_ptr(bk_env* env, void** out);
+/* Rows of books [first_book, first_book + n_books) to host memory, N * 16 words per book, slot by slot: one record has
+ * added to the row of slot (s / W) % N.  Waits for the env's stream; does NOT fold (bk_series_fold folds both tables).
+ * (No counterpart in the reference.) */
+int bk_get_candles(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
+
 /* ------------------------------------------------------ per-book lag table of the level-2 history */
 /* An opt-in table lags[n_books][n_lags] in DEVICE memory, n_lags = K, 1 <= K <= 64: per book and lag k = 1 .. K the sums
  * behind the autocorrelation of the mid's step-to-step change and of its magnitude at lag k (volatility clustering), and

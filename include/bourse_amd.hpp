@@ -358,6 +358,30 @@ class ManyEnv {
     check(bk_depth_device_ptr(h_, &p));
     return static_cast<uint64_t*>(p);
   }
+  // per-book candle table (bk_candles_enable): the series moments' other companion, a ring of the last n_candles bars of
+  // width steps per book, 16 words a bar; needs enable_series() and shares its fold, clears and cuts; no counterpart in the
+  // reference
+  void enable_candles(uint32_t width, uint32_t n_candles) { check(bk_candles_enable(h_, width, n_candles)); }
+  // {width, n_candles} as enabled
+  std::pair<uint32_t, uint32_t> candles_config() {
+    uint32_t c[2] = {0u, 0u};
+    check(bk_candles_config_get(h_, c));
+    return {c[0], c[1]};
+  }
+  // n_candles * 16 words per book of books [first_book, first_book + n_books), slot by slot (waits for the env's stream;
+  // does not fold)
+  std::vector<uint64_t> candles(uint32_t first_book, uint32_t n_books) {
+    std::vector<uint64_t> rows(static_cast<size_t>(n_books) * candles_config().second * 16u);
+    check(bk_get_candles(h_, first_book, n_books, rows.data()));
+    return rows;
+  }
+  std::vector<uint64_t> candles() { return candles(0, n_books_); }
+  // the table in device memory, uint64_t[n_books][n_candles][16]
+  uint64_t* candles_device_ptr() {
+    void* p = nullptr;
+    check(bk_candles_device_ptr(h_, &p));
+    return static_cast<uint64_t*>(p);
+  }
   // per-book lag table of the level-2 history (bk_lags_enable): n_lags rows (1 .. 64) of integer sums per book, row k - 1
   // for lag / span k, folded on the device from the history ring (needs history_capacity > 0); no counterpart in the reference
   void enable_lags(uint32_t n_lags) {
