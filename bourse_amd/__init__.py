@@ -9,7 +9,7 @@ from .compat import install_as_bourse, uninstall_bourse_alias
 from ._lib import (ACCOUNT_DTYPE, ACTION_MODIFY, AGENT_DESC_DTYPE, OPEN_ORDER_DTYPE, OPEN_QUEUE_DTYPE, OPEN_SUMMARY_DTYPE, QUOTE_DTYPE, QUOTE_KEEP, RANDOM_AGENTS_DTYPE, SERIES_DTYPE, TRADE_BAR_DTYPE, BourseError,
                    CapacityError, NoDeviceError, series_moments, LAG_DTYPE, lag_moments, BINS_CONFIG_DTYPE, bin_edges, bin_quantiles,
                    FLOW_DTYPE, flow_dtype, flow_moments, DEPTH_FIELDS, DEPTH_HEADER_FIELDS, depth_moments,
-                   CANDLE_FIELDS, CANDLE_DTYPE, candle_series)
+                   CANDLE_FIELDS, CANDLE_DTYPE, candle_series, CROSS_FIELDS, CROSS_DTYPE, CROSS_CONFIG_DTYPE, cross_moments)
 from .env import (MAX_PRICE, ManyBookEnv, ManyMarketEnv, MomentumAgent, MomentumParams, NoiseAgent, NoiseAgentParams,
                   RandomAgents, RandomMarketAgents, market_sim_runner, sim_runner)
 
@@ -19,4 +19,4 @@ __all__ = ["core", "step_sim", "data_processing", "install_as_bourse", "uninstal
            "OPEN_ORDER_DTYPE", "OPEN_QUEUE_DTYPE", "QUOTE_DTYPE", "QUOTE_KEEP", "TRADE_BAR_DTYPE", "SERIES_DTYPE",
            "series_moments", "LAG_DTYPE", "lag_moments", "BINS_CONFIG_DTYPE", "bin_edges", "bin_quantiles",
            "FLOW_DTYPE", "flow_dtype", "flow_moments", "DEPTH_FIELDS", "DEPTH_HEADER_FIELDS", "depth_moments",
-           "CANDLE_FIELDS", "CANDLE_DTYPE", "candle_series"]
+           "CANDLE_FIELDS", "CANDLE_DTYPE", "candle_series", "CROSS_FIELDS", "CROSS_DTYPE", "CROSS_CONFIG_DTYPE", "cross_moments"]

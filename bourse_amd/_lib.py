@@ -397,6 +397,55 @@ def flow_moments(rows) -> np.ndarray:
     return out
 
 
+# bk_cross_row: one market's row of one span and one ordered pair of assets of the cross table (ManyMarketEnv.cross), 8 words
+# of 8 bytes; bk_cross_config: n_spans and four spans, five u32
+CROSS_FIELDS = ("n", "sum_x", "sum_y", "sum_xx", "sum_yy", "sum_xy", "n_lead", "sum_lead")
+CROSS_SIGNED = ("sum_x", "sum_y", "sum_xy", "sum_lead")
+CROSS_DTYPE = np.dtype(
+    {"names": list(CROSS_FIELDS), "formats": ["<i8" if n in CROSS_SIGNED else "<u8" for n in CROSS_FIELDS],
+     "offsets": [8 * i for i in range(8)], "itemsize": 64})
+CROSS_CONFIG_DTYPE = np.dtype({"names": ["n_spans", "spans"], "formats": ["<u4", ("<u4", (4,))], "offsets": [0, 4], "itemsize": 20})
+CROSS_MOMENTS_DTYPE = np.dtype([(n, "<f8") for n in ("n", "cov", "corr", "beta", "lead_corr")])
+
+
+def cross_moments(rows) -> np.ndarray:
+    """``CROSS_DTYPE`` rows of any shape (``ManyMarketEnv.cross()``: ``[markets, spans, a, b]``) -> float64 moments of the
+    same shape (``CROSS_MOMENTS_DTYPE``), computed exactly in Python integers and rounded once.  With ``x`` and ``y`` the
+    changes of TWICE the mid of assets ``a`` and ``b`` over the row's span, counted where both are defined:
+
+    ``n`` the count; ``cov`` = (sum_xy / n - mean_x mean_y) / 4, the covariance of the two MID changes (each factor halved);
+    ``corr`` = cov / sqrt(var_x var_y); ``beta`` = cov / var_y, the slope of a's change on b's; ``lead_corr`` =
+    (sum_lead / n_lead - mean_x mean_y) / (4 sqrt(var_x var_y)), the correlation of a's change with b's PREVIOUS one - its
+    normalisation borrows the contemporaneous means and standard deviations, those of the ``n`` steps, not of the ``n_lead``
+    steps the product was summed over.  A division by a zero count or a zero variance gives NaN.  The words are read as they
+    are: a sum that has wrapped modulo 2^64 is not detected."""
+    from fractions import Fraction as F
+    from math import sqrt
+
+    rows = np.asarray(rows)
+    if rows.dtype != CROSS_DTYPE:
+        raise ValueError("cross_moments needs CROSS_DTYPE rows")
+    out = np.full(rows.shape, np.nan, dtype=CROSS_MOMENTS_DTYPE)
+    for r, o in zip(rows.reshape(-1), out.reshape(-1)):
+        w = {n: int(r[n]) for n in CROSS_FIELDS}
+        n = w["n"]
+        o["n"] = float(n)
+        if not n:
+            continue
+        mx, my = F(w["sum_x"], n), F(w["sum_y"], n)
+        cov = (F(w["sum_xy"], n) - mx * my) / 4
+        var_x, var_y = (F(w["sum_xx"], n) - mx * mx) / 4, (F(w["sum_yy"], n) - my * my) / 4
+        o["cov"] = float(cov)
+        if var_y:
+            o["beta"] = float(cov / var_y)
+        if var_x and var_y:
+            sd = sqrt(float(var_x)) * sqrt(float(var_y))
+            o["corr"] = float(cov) / sd
+            if w["n_lead"]:
+                o["lead_corr"] = float((F(w["sum_lead"], w["n_lead"]) - mx * my) / 4) / sd
+    return out
+
+
 # bk_bins_config: the configuration of the bin table (ManyBookEnv.enable_bins), nine u32
 BINS_CONFIG_DTYPE = np.dtype(
     {"names": ["n_bins", "n_spans", "spans", "ret_width", "spread_width", "vol_width"],
@@ -649,6 +698,13 @@ SIGNATURES = {
     "bk_bins_clear_device": (_i32, [_vp, _vp]),
     "bk_bins_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
     "bk_get_bins": (_i32, [_vp, _u32, _u32, _vp]),
+    "bk_cross_enable": (_i32, [_vp, _vp]),
+    "bk_cross_config_get": (_i32, [_vp, _vp]),
+    "bk_cross_fold": (_i32, [_vp]),
+    "bk_cross_clear": (_i32, [_vp, _vp]),
+    "bk_cross_clear_device": (_i32, [_vp, _vp]),
+    "bk_cross_device_ptr": (_i32, [_vp, C.POINTER(_vp)]),
+    "bk_get_cross": (_i32, [_vp, _u32, _u32, _vp]),
     "bk_flow_enable": (_i32, [_vp, _u32, _i32]),
     "bk_flow_fold": (_i32, [_vp]),
     "bk_flow_clear": (_i32, [_vp, _vp]),

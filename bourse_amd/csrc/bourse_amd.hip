@@ -64,6 +64,7 @@ extern template __global__ void k_agents_fsm<8, true>(DevArgs, const Group*);
 #include "stamp_compact.hpp"
 #include "lags.hpp"
 #include "bins.hpp"
+#include "cross.hpp"
 #include "flow.hpp"
 
 using namespace bkd;
@@ -94,6 +95,13 @@ static_assert(BK_FLOW_BASE_WORDS == flow::BASE_WORDS && BK_FLOW_LAG_WORDS == flo
 static_assert(sizeof(bk_bins_config) == 36 && offsetof(bk_bins_config, spans) == 8 && offsetof(bk_bins_config, ret_width) == 24 &&
                   sizeof(static_cast<bk_bins_config*>(nullptr)->spans) == bins::MAX_SPANS * 4,
               "bk_bins_config layout (bin_fold.hpp)");
+static_assert(sizeof(bk_cross_row) == 64 && sizeof(bk_cross_row) == cross::ROW_VECS * sizeof(bk_u32x4) &&
+                  sizeof(bk_cross_row) == cross::ROW_WORDS * 8 && offsetof(bk_cross_row, sum_xx) == cross::SUM_XX * 8 &&
+                  offsetof(bk_cross_row, sum_xy) == cross::SUM_XY * 8 && offsetof(bk_cross_row, sum_lead) == cross::SUM_LEAD * 8,
+              "bk_cross_row layout (cross_fold.hpp)");
+static_assert(sizeof(bk_cross_config) == 20 && offsetof(bk_cross_config, spans) == 4 &&
+                  sizeof(static_cast<bk_cross_config*>(nullptr)->spans) == cross::MAX_SPANS * 4 && static_cast<int>(cross::MAX_ASSETS) == MAX_ASSETS,
+              "bk_cross_config layout / the assets of a market (cross_fold.hpp)");
 static_assert(sizeof(bk_open_summary) == 32 && sizeof(bk_open_summary) == 2 * sizeof(bk_u32x4) &&
                   sizeof(bk_open_order) == 16 && sizeof(bk_open_order) == sizeof(bk_u32x4) &&
                   sizeof(open_orders::Summary) == sizeof(bk_open_summary) && sizeof(open_orders::Entry) == sizeof(bk_open_order),
@@ -207,9 +215,9 @@ struct HostStage {
 
 }  // namespace
 
-// One table folded from the level-2 history ring by a host cursor - the series moments, the lag table, the bin table.
-// What the three share is written once over this struct (the cursor's rule is hist_cursor.hpp's); what differs is how a
-// table's fold over a span of the ring and its clear are launched.
+// One table folded from the level-2 history ring by a host cursor - the series moments, the lag table, the bin table, and
+// beside those three per-book tables the per-market cross table.  What they share is written once over this struct (the
+// cursor's rule is hist_cursor.hpp's); what differs is how a table's fold over a span of the ring and its clear are launched.
 struct HistTable {
   const char* noun;     // in the lost steps' message: "of the <noun> were lost"
   const char* name;     // in the guard's: "this env has no <name>"
@@ -220,15 +228,19 @@ struct HistTable {
   void (*clear)(bk_env*, const uint8_t* mask_dev, uint32_t M, bool carry_only);
   bool on = false;
   uint64_t seen = 0;     // steps below it are folded (a host integer, as steps_done)
-  DevBuf<uint8_t> mask;  // bk_<prefix>_clear: device staging of the host mask [n_books]
+  DevBuf<uint8_t> mask;  // bk_<prefix>_clear: device staging of the host mask [n_books / clear_M]
+  uint32_t clear_M = 1;  // books per mask byte of bk_<prefix>_clear[_device] (the cross table's unit is the market: env->M)
 };
 enum { T_SERIES, T_LAGS, T_BINS, N_HIST_TABLES };
+enum { T_CROSS = N_HIST_TABLES };  // the per-market table: bk_env::cross_table, beside the three per-book tables[]
 static void launch_series_fold(bk_env*, const ring::Span&);
 static void launch_series_clear(bk_env*, const uint8_t*, uint32_t, bool);
 static void launch_lags_fold(bk_env*, const ring::Span&);
 static void launch_lags_clear(bk_env*, const uint8_t*, uint32_t, bool);
 static void launch_bins_fold(bk_env*, const ring::Span&);
 static void launch_bins_clear(bk_env*, const uint8_t*, uint32_t, bool);
+static void launch_cross_fold(bk_env*, const ring::Span&);
+static void launch_cross_clear(bk_env*, const uint8_t*, uint32_t, bool);
 
 struct bk_env {
   bk_config cfg{};
@@ -293,11 +305,13 @@ struct bk_env {
   DevBuf<uint8_t> flow_mask;  // bk_flow_clear: device staging of the host mask [n_books]
   uint32_t flow_lags = 0;     // 0: no flow table
   bool flow_consume = false;
-  // the three tables folded from the history ring (HistTable above), and what each keeps on the device:
+  // the three per-book tables folded from the history ring (HistTable above), the per-market one beside
+  // them (2.29), and what each keeps on the device:
   HistTable tables[N_HIST_TABLES] = {
       {"series", "series moments", "", "series", launch_series_fold, launch_series_clear},
       {"lag table", "lag table", "a ", "lags", launch_lags_fold, launch_lags_clear},
       {"bin table", "bin table", "a ", "bins", launch_bins_fold, launch_bins_clear}};
+  HistTable cross_table = {"cross table", "cross table", "a ", "cross", launch_cross_fold, launch_cross_clear};
   // bk_series_enable: one row of series moments per book [n_books] of 192 B (series.hpp)
   DevBuf<bk_u32x4> series_rows;
   // bk_depth_enable: the series' companion over the ladder, (levels + 1) rows of 128 B per book [n_books][L + 1][8] vectors
@@ -318,6 +332,12 @@ struct bk_env {
   DevBuf<uint64_t> bins_carry;
   bk_bins_config bins_cfg{};
   uint32_t bins_kmax = 0;  // the longest span
+  // bk_cross_enable: n_spans * assets * assets rows per MARKET [n_markets][S][A][A] of 64 B and the carry
+  // [n_markets][A][2 * cross_hmax] (cross.hpp)
+  DevBuf<bk_u32x4> cross_rows;
+  DevBuf<uint64_t> cross_carry;
+  bk_cross_config cross_cfg{};
+  uint32_t cross_hmax = 0;  // the longest span
   // bk_open_orders_enable: every trader's resting orders per book, recomputed from the pool behind every step (open_orders.hpp)
   DevBuf<bk_u32x4> open_summary;  // [n_books][open_traders][2]
   DevBuf<bk_u32x4> open_entries;  // [n_books][open_traders][open_depth]; empty with open_depth == 0
@@ -2866,9 +2886,10 @@ int bk_clear_history(bk_env* env) {
 // ------------------------------------------------------------------ the tables folded from the level-2 history ring
 // No counterpart in the reference.  Per book: series_rows[n_books] rows of 24 u64 words (series.hpp),
 // lag_rows[n_books][n_lags] rows of 10 u64 words and lag_carry[n_books][n_lags + 1] (lags.hpp, 2.24), and
-// bin_rows[n_books][n_spans + 2][n_bins] u64 counts and bins_carry[n_books][bins_kmax] (bins.hpp, 2.25) - each folded
-// by its k_fold on the env's stream when its bk_*_fold, a masked clear or a reset asks.  The six launches first, then the
-// one contract over HistTable (2.21a).
+// bin_rows[n_books][n_spans + 2][n_bins] u64 counts and bins_carry[n_books][bins_kmax] (bins.hpp, 2.25); per market:
+// cross_rows[n_markets][n_spans][A][A] rows of 8 u64 words and cross_carry[n_markets][A][2 * cross_hmax] (cross.hpp, 2.29) -
+// each folded by its k_fold on the env's stream when its bk_*_fold, a masked clear or a reset asks.  The eight launches
+// first, then the one contract over HistTable (2.21a).
 static ring::Masked masked_books(const bk_env* env, const uint8_t* mask_dev, uint32_t M) { return {mask_dev, M, env->cfg.n_books}; }
 
 static void launch_series_fold(bk_env* env, const ring::Span& span) {
@@ -2969,6 +2990,34 @@ static void launch_bins_clear(bk_env* env, const uint8_t* mask_dev, uint32_t M, 
   g.rows = env->bin_rows.p;
   g.carry = env->bins_carry.p;
   launch_wave_per_book(env, bins::k_clear, bins::FOLD_WAVES, g.books.n_books, g);
+}
+
+static void launch_cross_fold(bk_env* env, const ring::Span& span) {
+  const bk_cross_config& c = env->cross_cfg;
+  cross::FoldArgs g{};
+  g.ring = span;
+  g.A = env->M;
+  g.S = c.n_spans;
+  g.Hmax = env->cross_hmax;
+  g.spans = c.spans[0] | c.spans[1] << 8 | c.spans[2] << 16 | c.spans[3] << 24;
+  g.rows = env->cross_rows.p;
+  g.carry = env->cross_carry.p;
+  // one wave per MARKET (a launch of its own: the wave-per-book helper passes no dynamic LDS)
+  const uint32_t markets = span.n_books / env->M;
+  hipLaunchKernelGGL(cross::k_fold, dim3((markets + cross::FOLD_WAVES - 1) / cross::FOLD_WAVES), dim3(64 * cross::FOLD_WAVES),
+                     cross::fold_lds_bytes(g.A, g.Hmax), env->stream, g);
+}
+
+// (mask_dev holds one byte per MARKET from either caller - a reset's M is env->M, and so is the table's own clear_M)
+static void launch_cross_clear(bk_env* env, const uint8_t* mask_dev, uint32_t, bool carry_only) {
+  cross::ClearArgs g{};
+  g.markets = ring::Masked{mask_dev, 1u, env->cfg.n_books / env->M};
+  g.U = cross::units(env->cross_cfg.n_spans, env->M);
+  g.carry_words = env->M * cross::carry_words(env->cross_hmax);
+  g.carry_only = carry_only ? 1u : 0u;
+  g.rows = env->cross_rows.p;
+  g.carry = env->cross_carry.p;
+  launch_wave_per_book(env, cross::k_clear, cross::FOLD_WAVES, g.markets.n_books, g);
 }
 
 // a step of [seen, steps_done) that the ring no longer retains refuses; nothing is launched or changed
@@ -3168,9 +3217,9 @@ int bk_load_book(bk_env* env, uint32_t book, uint64_t t, uint32_t trade_vol, uin
   if (env->flow_lags)
     return fail(BK_INVALID_ARGUMENT, "loading a book into an env with a flow table (bk_flow_enable) is not supported: the "
                                      "book's trade records would pass as the successors of the replaced book's");
-  for (const HistTable& t : env->tables)
-    if (t.on)
-      return fail(BK_INVALID_ARGUMENT, std::string("loading a book into an env with ") + t.article + t.name + " (bk_" + t.prefix +
+  for (const HistTable* t : {&env->tables[T_SERIES], &env->tables[T_LAGS], &env->tables[T_BINS], &env->cross_table})
+    if (t->on)
+      return fail(BK_INVALID_ARGUMENT, std::string("loading a book into an env with ") + t->article + t->name + " (bk_" + t->prefix +
                                            "_enable) is not supported: the book's next record would pass as the successor of "
                                            "the replaced book's last");
   if ((n_orders && (!orders || !key_price || !key_time)) || (n_trades && !trades))
@@ -3661,6 +3710,11 @@ int bk_checkpoint_load(bk_env* env, const void* in, uint64_t nbytes) {
     HIPCHK(hipGetLastError());
     t.seen = env->steps_done;
   }
+  if (env->cross_table.on) {  // ... and the per-market one
+    launch_cross_clear(env, nullptr, 1, false);
+    HIPCHK(hipGetLastError());
+    env->cross_table.seen = env->steps_done;
+  }
   if (env->flow_lags) {  // nor is the flow table: every word starts again, the cursors at the restored counts
     launch_flow_clear(env, nullptr, 1, false);
     HIPCHK(hipGetLastError());
@@ -3763,10 +3817,10 @@ static int stage_mask(bk_env* env, size_t n, const uint8_t* mask_host, DevBuf<ui
 // The host form of a table's masked clear behind the table's own check: no mask is the _device form's business, a mask
 // (one byte per book) goes through the table's `staging` into it.
 static int clear_from_host(bk_env* env, const uint8_t* mask_host, DevBuf<uint8_t>& staging,
-                           int (*device_form)(bk_env*, const uint8_t*)) {
+                           int (*device_form)(bk_env*, const uint8_t*), uint32_t books_per_byte = 1) {
   if (!mask_host) return device_form(env, nullptr);
   if (int rc = use_device(env)) return rc;
-  if (int rc = stage_mask(env, env->cfg.n_books, mask_host, staging)) return rc;
+  if (int rc = stage_mask(env, env->cfg.n_books / books_per_byte, mask_host, staging)) return rc;
   return device_form(env, staging.p);
 }
 
@@ -3803,15 +3857,23 @@ static void launch_reset_books(bk_env* env, const uint32_t* snap, const uint8_t*
 static int reset_books_from(bk_env* env, const uint32_t* snap, uint64_t stamp_bound, const uint8_t* mask_dev,
                             const uint64_t* seeds_dev) {
   // the tables folded from the history ring: lost steps of any of them refuse the reset before one of them launches anything
-  // (checked bins, lags, series and launched series, lags, bins: the order decides whose message is seen when two have lost steps)
+  // (checked bins, lags, series, cross and launched series, lags, bins, cross: the order decides whose message is seen when two
+  // have lost steps)
   for (int i = N_HIST_TABLES - 1; i >= 0; --i)
     if (env->tables[i].on)
       if (int rc = table_lost_check(env, env->tables[i])) return rc;
+  if (env->cross_table.on)
+    if (int rc = table_lost_check(env, env->cross_table)) return rc;
   // ... then the steps so far belong to the old episode, and no return, span or pair reaches over the reset: cut the carry
   for (HistTable& t : env->tables) {
     if (!t.on) continue;
     if (int rc = table_fold_outstanding(env, t)) return rc;
     t.clear(env, mask_dev, env->M, true);
+    HIPCHK(hipGetLastError());
+  }
+  if (env->cross_table.on) {  // the per-market table: the reset's mask is already one byte per market
+    if (int rc = table_fold_outstanding(env, env->cross_table)) return rc;
+    launch_cross_clear(env, mask_dev, env->M, true);
     HIPCHK(hipGetLastError());
   }
   if (env->flow_lags) {  // the flow table: the records so far belong to the old episode
@@ -4299,26 +4361,29 @@ int bk_get_flow_state(bk_env* env, uint32_t first_book, uint32_t n_books, uint64
 
 // ------------------------------------------------------------------ the tables folded from the history ring: the entries
 // (the launches, the lost-step check and the fold of what is outstanding stand with the history ring above)
+// table `which`: one of the three per-book tables, or T_CROSS, the per-market one beside them
+static HistTable& table_at(bk_env* env, int which) { return which == T_CROSS ? env->cross_table : env->tables[which]; }
+
 // the guard of every entry but the enable
 static int table_ok(bk_env* env, int which) {
   if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
-  const HistTable& t = env->tables[which];
+  const HistTable& t = table_at(env, which);
   if (!t.on) return fail(BK_INVALID_ARGUMENT, std::string("this env has no ") + t.name + ": call bk_" + t.prefix + "_enable first");
   return BK_OK;
 }
 
 static int table_fold(bk_env* env, int which) {
   if (int rc = table_ok(env, which)) return rc;
-  return table_fold_outstanding(env, env->tables[which]);
+  return table_fold_outstanding(env, table_at(env, which));
 }
 
 static int table_clear_device(bk_env* env, int which, const uint8_t* mask_dev) {
   if (int rc = table_ok(env, which)) return rc;
   if (int rc = use_device(env)) return rc;
-  HistTable& t = env->tables[which];
+  HistTable& t = table_at(env, which);
   if (mask_dev) {
     if (int rc = table_fold_outstanding(env, t)) return rc;
-    t.clear(env, mask_dev, 1, false);
+    t.clear(env, mask_dev, t.clear_M, false);
   } else {
     table_start_again(env, t);  // nothing is folded
   }
@@ -4329,8 +4394,8 @@ static int table_clear_device(bk_env* env, int which, const uint8_t* mask_dev) {
 static int table_clear(bk_env* env, int which, const uint8_t* mask_host, int (*device_form)(bk_env*, const uint8_t*)) {
   if (int rc = table_ok(env, which)) return rc;
   if (mask_host)
-    if (int rc = table_lost_check(env, env->tables[which])) return rc;  // (refused before the mask is staged)
-  return clear_from_host(env, mask_host, env->tables[which].mask, device_form);
+    if (int rc = table_lost_check(env, table_at(env, which))) return rc;  // (refused before the mask is staged)
+  return clear_from_host(env, mask_host, table_at(env, which).mask, device_form, table_at(env, which).clear_M);
 }
 
 // ------------------------------------------------------------------ per-book series moments
@@ -4578,6 +4643,85 @@ int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* ou
   if (int rc = table_ok(env, T_BINS)) return rc;
   const size_t per_book = static_cast<size_t>(env->bins_cfg.n_spans + 2u) * env->bins_cfg.n_bins * sizeof(uint64_t);
   return get_book_rows(env, first_book, n_books, {{env->bin_rows.p, per_book, out}});
+}
+
+// ------------------------------------------------------------------ per-market cross table
+static const char* cross_config_fault(const bk_cross_config& c) {
+  if (c.n_spans < 1u || c.n_spans > cross::MAX_SPANS) return "n_spans must be in 1..4";
+  for (uint32_t j = 0; j < c.n_spans; ++j)
+    if (c.spans[j] < 1u || c.spans[j] > cross::MAX_SPAN) return "every used span must be in 1..64";
+  return nullptr;
+}
+
+int bk_cross_enable(bk_env* env, const bk_cross_config* cfg) {
+  if (!env) return fail(BK_INVALID_ARGUMENT, "null env");
+  if (!cfg) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (!env->cfg.history_capacity)
+    return fail(BK_INVALID_ARGUMENT, "the cross table is folded from the level-2 history ring: history_capacity must be > 0");
+  if (env->M < 2u)
+    return fail(BK_INVALID_ARGUMENT, "the cross table couples the assets of a market: it needs an env of markets with assets >= 2, "
+                                     "not an env of independent books (assets == 1)");
+  if (const char* why = cross_config_fault(*cfg)) return fail(BK_INVALID_ARGUMENT, why);
+  if (env->cross_table.on) return fail(BK_INVALID_ARGUMENT, "the cross table is already enabled on this env");
+  if (int rc = use_device(env)) return rc;
+  bk_cross_config c = *cfg;
+  uint32_t hmax = 0;
+  for (uint32_t j = 0; j < cross::MAX_SPANS; ++j) {
+    if (j >= c.n_spans) c.spans[j] = 0u;
+    hmax = std::max(hmax, c.spans[j]);
+  }
+  const size_t markets = env->cfg.n_books / env->M;
+  DevBuf<bk_u32x4> rows;
+  DevBuf<uint64_t> carry;
+  HIPCHK(rows.alloc(markets * cross::units(c.n_spans, env->M) * cross::ROW_VECS));
+  HIPCHK(carry.alloc(markets * env->M * cross::carry_words(hmax)));
+  env->cross_rows.swap(rows);
+  env->cross_carry.swap(carry);
+  env->cross_cfg = c;
+  env->cross_hmax = hmax;
+  env->cross_table.clear_M = env->M;  // its own clear's mask holds one byte per market, as a reset's
+  const int rc = table_commit_enable(env, env->cross_table);
+  if (rc) {  // the env stays without the table: the new blocks leave with `rows` and `carry`
+    env->cross_rows.swap(rows);
+    env->cross_carry.swap(carry);
+    env->cross_cfg = bk_cross_config{};
+    env->cross_hmax = 0;
+    env->cross_table.clear_M = 1;
+  }
+  return rc;
+}
+
+int bk_cross_config_get(bk_env* env, bk_cross_config* out) {
+  if (int rc = table_ok(env, T_CROSS)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->cross_cfg;
+  return BK_OK;
+}
+
+int bk_cross_fold(bk_env* env) { return table_fold(env, T_CROSS); }
+int bk_cross_clear_device(bk_env* env, const uint8_t* mask_dev) { return table_clear_device(env, T_CROSS, mask_dev); }
+int bk_cross_clear(bk_env* env, const uint8_t* mask_host) { return table_clear(env, T_CROSS, mask_host, bk_cross_clear_device); }
+
+int bk_cross_device_ptr(bk_env* env, void** out) {
+  if (int rc = table_ok(env, T_CROSS)) return rc;
+  if (!out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  *out = env->cross_rows.p;
+  return BK_OK;
+}
+
+// the rows of markets [first_market, first_market + n_markets) -> host (an empty range may start behind the last market)
+int bk_get_cross(bk_env* env, uint32_t first_market, uint32_t n_markets, bk_cross_row* out) {
+  if (int rc = table_ok(env, T_CROSS)) return rc;
+  const uint32_t markets = env->cfg.n_books / env->M;
+  if (first_market > markets || n_markets > markets - first_market) return fail(BK_INVALID_ARGUMENT, "market range out of bounds");
+  if (n_markets && !out) return fail(BK_INVALID_ARGUMENT, "null argument");
+  if (int rc = use_device(env)) return rc;
+  HIPCHK(hipStreamSynchronize(env->stream));
+  const size_t market_bytes = static_cast<size_t>(cross::units(env->cross_cfg.n_spans, env->M)) * sizeof(bk_cross_row);
+  if (n_markets)
+    HIPCHK(hipMemcpy(out, reinterpret_cast<const char*>(env->cross_rows.p) + first_market * market_bytes, n_markets * market_bytes,
+                     hipMemcpyDeviceToHost));
+  return BK_OK;
 }
 
 // ------------------------------------------------------------------ open orders of a device-ingress env

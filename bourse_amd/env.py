@@ -193,6 +193,7 @@ class ManyBookEnv:
         self._n_lags = 0          # enable_lags
         self._flow_lags = 0       # enable_flow
         self._bins_shape = None   # enable_bins: (n_spans + 2, n_bins)
+        self._cross_spans = 0     # ManyMarketEnv.enable_cross: n_spans
         self._open_shape = None   # enable_open_orders: (n_traders, depth)
         self._open_queue = False  # enable_open_queue: the queue table beside the open-order entries exists
         if stream is not None:
@@ -470,16 +471,18 @@ class ManyBookEnv:
         check(entry(self._h, first, n, *(None if o is None else o.ctypes.data_as(C.c_void_p) for o in outs)))
         return outs
 
-    def _masked_clear(self, device_entry, host_entry, mask, sync):
-        """``clear_accounts``' ``mask`` / ``sync`` for any per-book table: ``None``, a device object or a host array."""
+    def _masked_clear(self, device_entry, host_entry, mask, sync, n: Optional[int] = None, per: str = "one per book"):
+        """``clear_accounts``' ``mask`` / ``sync`` for any per-book table: ``None``, a device object or a host array
+        (``n``, ``per``: the entries of a table whose unit is not the book)."""
+        n = self.n_books if n is None else n
         if mask is None:
             check(device_entry(self._h, None))
         elif _is_dev(mask):
-            if _dev_count(mask) != self.n_books:
-                raise ValueError(f"mask: {self.n_books} elements are needed (one per book)")
+            if _dev_count(mask) != n:
+                raise ValueError(f"mask: {n} elements are needed ({per})")
             check(device_entry(self._h, self._dev_ptr(mask, 1, "mask")))
         else:
-            m = _host_mask(mask, self.n_books, "one per book")
+            m = _host_mask(mask, n, per)
             check(host_entry(self._h, m.ctypes.data_as(C.c_void_p)))
         if sync:
             self.sync()
@@ -1355,14 +1358,15 @@ class ManyBookEnv:
     def run_series(self, n_steps: int, chunk: Optional[int] = None):
         """``run(c, sync=False); fold_series()`` in chunks of ``chunk <= history_capacity`` steps (default:
         ``history_capacity``) until ``n_steps`` are run: the way to run more steps than the ring holds.  Nothing waits
-        between the chunks, or at the end.  With ``enable_lags`` / ``enable_bins`` those tables are folded after every chunk
-        too - and alone if only they are enabled.  So is the flow table of ``enable_flow`` (``fold_flow()``: the chunk's trade
+        between the chunks, or at the end.  With ``enable_lags`` / ``enable_bins`` / ``enable_cross`` those tables are folded
+        after every chunk too - and alone if only they are enabled.  So is the flow table of ``enable_flow`` (``fold_flow()``: the chunk's trade
         records; with ``consume_trades`` ``trade_capacity`` then only has to hold one chunk's trades), also as the only table
         of the env: ``fold_series`` and its refusal come only where no table at all is enabled."""
         c = self.history_capacity if chunk is None else int(chunk)
         if not 1 <= c <= self.history_capacity:
             raise ValueError("run_series needs 1 <= chunk <= history_capacity")
         folds = ([self.fold_lags] if self._n_lags else []) + ([self.fold_bins] if self._bins_shape else [])
+        folds += [self.fold_cross] if self._cross_spans else []  # (ManyMarketEnv.enable_cross)
         folds += [self.fold_flow] if self._flow_lags else []  # (enable_flow: the chunk's trade records as well)
         if self._series or not folds:  # (neither table: fold_series raises the library's refusal, as ever)
             folds.insert(0, self.fold_series)
@@ -1861,6 +1865,10 @@ class BinsView(AccountsView):
     """``ManyBookEnv.bins_view()``: the bin table where it lives, read the same way."""
 
 
+class CrossView(AccountsView):
+    """``ManyMarketEnv.cross_view()``: the cross table where it lives, read the same way."""
+
+
 def sim_runner(env: ManyBookEnv, agents: Sequence[RandomAgents | tuple], n_steps: int):
     """``sim_runner(env, agents, seed, n_steps, _)`` (ref runner.rs:46-69) for every book of ``env``.
 
@@ -1897,6 +1905,82 @@ class ManyMarketEnv(ManyBookEnv):
         """``reset_ingress_books`` spelt by market (an env with the device ingress): a masked market's books, and its
         queue, go back."""
         self.reset_ingress_books(mask, seeds, slot, sync)
+
+    # ------------------------------------------------------------ per-market cross table of the level-2 history
+    CROSS_DTYPE = _lib.CROSS_DTYPE
+
+    def enable_cross(self, spans=(1,)):
+        """``bk_cross_enable``: keep ``len(spans) * assets * assets`` rows of eight integer sums per MARKET in device memory,
+        row ``(j, a, b)`` for the ordered pair asset ``a`` against asset ``b`` at span ``spans[j]`` (1 .. 64 steps each, at
+        most four, any order): count, sums, squares and cross product of the two assets' changes of twice the mid over the
+        span where both are defined, and count and sum of a's change times b's PREVIOUS one (``CROSS_DTYPE`` /
+        ``bourse_amd.CROSS_FIELDS``; include/bourse_amd.h states what one step adds).  ``fold_cross()`` folds the steps run
+        since the last fold from the history ring, on the env's stream; nothing leaves the device until ``cross()`` is read.
+        Needs ``history_capacity > 0`` and ``assets >= 2``; works with ``run`` on every pipeline, ``step`` and the device
+        ingress, with or without the per-book tables.  Steps before the call are not counted.  ``bourse_amd.cross_moments``
+        turns the rows into covariance, correlation, beta and lead correlation.  The reference has no counterpart."""
+        spans = tuple(int(h) for h in spans)
+        slots = (spans + (0, 0, 0, 0))[:4]  # (more than four spans: the library refuses n_spans)
+        words = [len(spans), *slots]
+        if any(not 0 <= w <= 0xFFFFFFFF for w in words + list(spans)):
+            raise ValueError("enable_cross: every value is a 32-bit unsigned integer")
+        cfg = np.array(words, dtype=np.uint32)
+        check(self._L.bk_cross_enable(self._h, cfg.ctypes.data_as(C.c_void_p)))
+        self._cross_spans = len(spans)
+
+    def _cross_dims(self) -> Tuple[int, int, int]:
+        if not self._cross_spans:
+            raise _lib.BourseError(_lib.BK_INVALID, "this env has no cross table: call enable_cross (bk_cross_enable) first")
+        return self._cross_spans, self.assets, self.assets
+
+    def cross_config(self) -> np.ndarray:
+        """``bk_cross_config_get``: the configuration the table was enabled with, a ``CROSS_CONFIG_DTYPE`` record."""
+        self._cross_dims()
+        cfg = np.zeros((), dtype=_lib.CROSS_CONFIG_DTYPE)
+        check(self._L.bk_cross_config_get(self._h, cfg.ctypes.data_as(C.c_void_p)))
+        return cfg
+
+    def fold_cross(self, sync: bool = False):
+        """``bk_cross_fold``: queue the fold of every step run since the last fold (no new step: no launch).  Raises if one
+        of them is no longer retained by the ring - more than ``history_capacity`` steps since the last fold, or
+        ``clear_history()`` - naming how many were lost; rows, carry and cursor are then unchanged and ``clear_cross()``
+        starts again."""
+        check(self._L.bk_cross_fold(self._h))
+        if sync:
+            self.sync()
+
+    def cross(self, first_market: int = 0, n_markets: Optional[int] = None) -> np.ndarray:
+        """The rows of markets ``[first_market, first_market + n_markets)`` (default: to the last market) as a structured
+        array of shape ``[n, n_spans, assets, assets]`` (``CROSS_DTYPE``).  Waits for the env's stream; does NOT fold."""
+        dims = self._cross_dims()
+        first = int(first_market)
+        n = self.n_markets - first if n_markets is None else int(n_markets)
+        if first < 0 or n < 0:
+            raise ValueError("market range out of bounds")
+        out = np.zeros((n,) + dims, dtype=_lib.CROSS_DTYPE)
+        check(self._L.bk_get_cross(self._h, first, n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def cross_device_ptr(self) -> int:
+        """Device address of the table, ``bk_cross_row[n_markets][n_spans][assets][assets]`` (for on-device consumers)."""
+        return self._device_ptr(self._L.bk_cross_device_ptr)
+
+    def cross_view(self) -> "CrossView":
+        """The table in place as an object with ``__cuda_array_interface__``: int64, shape ``(n_markets, n_spans, assets,
+        assets, 8)``, the words in ``CROSS_DTYPE``'s order (unsigned words read as int64: the same bits).
+        ``torch.as_tensor(env.cross_view(), device="cuda")`` is a zero-copy tensor that every later fold updates; it is
+        written on the env's stream, so read it there (or after ``sync()``)."""
+        return CrossView(self, self.cross_device_ptr(), (self.n_markets,) + self._cross_dims() + (8,), self._stream)
+
+    def clear_cross(self, mask=None, sync: bool = True):
+        """With a ``mask`` (one entry per MARKET, as ``reset_markets`` takes it): fold what is outstanding (raising as
+        ``fold_cross`` does), then clear the rows and the carry of the markets with ``mask[m]`` set.  ``None``: clear
+        everything and count from the current step on without folding - the way on after lost steps.  ``mask`` / ``sync`` as
+        ``clear_accounts`` takes them (``bk_cross_clear`` / ``bk_cross_clear_device``).  ``reset_markets`` /
+        ``reset_ingress_markets`` fold and then cut only the carry of the markets they reset: the sums go on across episodes
+        and no span or lead reaches over a reset."""
+        # (no check of its own in front: the library refuses an env without the table)
+        self._masked_clear(self._L.bk_cross_clear_device, self._L.bk_cross_clear, mask, sync, self.n_markets, "one per market")
 
     def place_order(self, market: int, asset: int, bid: bool, vol: int, trader_id: int, price: Optional[int] = None):
         """``MarketEnv::place_order(asset, side, vol, trader_id, price)`` (market_env.rs:163-176) -> per-asset order id"""

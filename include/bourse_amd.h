@@ -1067,6 +1067,93 @@ int bk_bins_device_ptr(bk_env* env, void** out);
  * env's stream; does NOT fold.  (No counterpart in the reference.) */
 int bk_get_bins(bk_env* env, uint32_t first_book, uint32_t n_books, uint64_t* out);
 
+/* ------------------------------------------------------ per-market cross table of the level-2 history */
+/* An opt-in table cross[n_markets][S][A][A] in DEVICE memory on an env of markets (A = assets >= 2 books a market,
+ * n_markets = n_books / A, book = market * A + asset): per market, span h_j = spans[j] and ORDERED pair of assets (a, b) the
+ * sums behind the covariance and correlation of the two assets' changes of the mid over h_j steps - how the correlation
+ * grows with the span (the Epps effect) - and behind the product of a's change with b's PREVIOUS one (which asset leads).
+ * It is the fourth table folded on the env's stream from the history ring with no host wait (bourse_amd/csrc/cross.hpp,
+ * cross_fold.hpp), the only one whose unit is the market and not the book, and needs none of the others.
+ * It serves every flow that writes the ring of such an env - bk_run on all pipelines, bk_step, the device ingress - and
+ * touches no stepping kernel.  The reference has no counterpart for any of these entries.
+ *
+ * The configuration.  S = n_spans is in 1 .. 4; each used span h_j = spans[j], j < S, is in 1 .. 64, in any order,
+ * duplicates allowed (spans[j] for j >= S is ignored and read back as 0).  Hmax is the longest used span.
+ *
+ * What one step adds.  Of the record of step s and book market * A + x only bid_price and ask_price are read (words 1 and
+ * 2); an empty side reads bid_price == 0 / ask_price == 0xFFFFFFFF.
+ *   two_x(s) = bid != 0 && ask != 0xFFFFFFFF;  m_x(s) = bid + ask (TWICE the mid, a u64), as for bk_lags_*;
+ *   a step in front of the table's START - the enable, a clear of that market, or a cut by a reset - is not two-sided.
+ * Step s adds to row (market, j, a, b), for every j < S and every a, b < A, with h = h_j:
+ *   CONTEMPORANEOUS, if two_a(s) && two_a(s-h) && two_b(s) && two_b(s-h), with x = m_a(s) - m_a(s-h) and
+ *                    y = m_b(s) - m_b(s-h) (signed, |x|, |y| < 2^33):
+ *                      n += 1, sum_x += x, sum_y += y, sum_xx += x * x, sum_yy += y * y, sum_xy += x * y;
+ *   LEAD, b's previous window against a's current one, if two_a(s) && two_a(s-h) && two_b(s-h) && two_b(s-2h) (m_b(s) is
+ *                    NOT required), with z = m_b(s-h) - m_b(s-2h):
+ *                      n_lead += 1, sum_lead += x * z.
+ * All words are sums modulo 2^64; signed words are two's complement, and the products are the 64-bit products of the
+ * two's-complement values; a cleared row is all zeros.  The definition is pairwise complete: the books are one-sided at
+ * different steps, so n of (a, b) is usually below n of (a, a) and of (b, b).  By construction row (., j, a, a) holds in n
+ * the n_h, in sum_x and sum_y the sum_h and in sum_xx, sum_yy and sum_xy the sum_h2 of row h_j - 1 of book market * A + a's
+ * lag table (bk_lags_*) over the same steps and cuts, at h_j == 1 also its n_pairs in n_lead and its sum_dd in sum_lead; rows
+ * (a, b) and (b, a) share n and sum_xy and swap sum_x / sum_y and sum_xx / sum_yy.
+ *
+ * The carry.  A fold must know the 2 * Hmax records of every asset in front of its first step, which the ring may no longer
+ * hold.  The env keeps cross_carry[n_markets][A][2 * Hmax] u64, an array of its own beside the table: entry i of an asset is
+ * the record of step cross_seen - 2 * Hmax + i - bit 63 = two, the low bits = m - and the whole word is 0 when that step is
+ * one-sided or lies in front of the start.  So folding steps [x, y) and then [y, z) leaves the same rows and carry as one
+ * fold over [x, z), for every split - single steps and a ring shorter than 2 * Hmax included. */
+typedef struct bk_cross_config { /* 20 B, five u32 */
+  uint32_t n_spans;
+  uint32_t spans[4];
+} bk_cross_config;
+typedef struct bk_cross_row { /* 64 B, four 16-byte vectors, little-endian */
+  uint64_t n;
+  int64_t sum_x, sum_y;
+  uint64_t sum_xx, sum_yy;
+  int64_t sum_xy;
+  uint64_t n_lead;
+  int64_t sum_lead;
+} bk_cross_row;
+/* Enabling.  Accepted on an env of markets (assets >= 2) with history_capacity > 0, at any time, once.  Allocates the rows
+ * and the carry (arrays of their own: the state block, checkpoints and snapshots are unchanged), clears both and sets the
+ * env's step cursor cross_seen, a host integer as bk_steps_done is and independent of the siblings' cursors, to
+ * bk_steps_done: earlier steps are not counted.  A refusal - here and in the entries below: a null env or config,
+ * history_capacity == 0, an env of independent books (assets == 1), a configuration outside the bounds above, a second call,
+ * any other entry before this one - returns BK_INVALID_ARGUMENT, leaves the env unchanged and puts the reason in
+ * bk_last_error().
+ *
+ * bk_reset_books* and bk_ingress_reset_books* on such an env first fold what is outstanding (and refuse the reset if steps
+ * were lost, see bk_cross_fold; every table of the history ring on the same env is checked before any folds), then zero only
+ * the CARRY of every asset of the markets they reset: the sums go on across episodes and no span or lead reaches over a
+ * reset; clear by mask if new rows are wanted.  bk_checkpoint_load clears every row and carry and sets the cursor to the
+ * restored step count.  bk_load_book is refused.  bk_warm writes no history and restores the counter: unaffected.  An env
+ * without the table launches nothing new.  (No counterpart in the reference.) */
+int bk_cross_enable(bk_env* env, const bk_cross_config* cfg);
+/* The configuration the table was enabled with (spans beyond n_spans read 0).  (No counterpart in the reference.) */
+int bk_cross_config_get(bk_env* env, bk_cross_config* out);
+/* Queues, on the env's stream and without any host wait, the fold of steps [cross_seen, bk_steps_done) of every market; then
+ * cross_seen = bk_steps_done.  No new step: no launch.  If a step of that range is no longer retained by the ring - it
+ * wrapped (more than history_capacity steps since the last fold), or bk_clear_history was called - returns
+ * BK_INVALID_ARGUMENT with the number of lost steps in bk_last_error() and leaves rows, carry and cursor unchanged: a lost
+ * step is never silent and needs no flag bit.  bk_cross_clear with a NULL mask is the way on.  (No counterpart in the
+ * reference.) */
+int bk_cross_fold(bk_env* env);
+/* Clearing.  mask [n_markets] bytes, one per MARKET (as the resets' masks).  With a mask: folds what is outstanding first
+ * (refusing as bk_cross_fold does), then clears the rows and the carry of the markets m with mask[m] != 0.  NULL: clears
+ * every row and carry and sets the cursor to bk_steps_done WITHOUT folding.  From a HOST mask: staged on the env's stream and
+ * waited for, the clear itself stays asynchronous.  (No counterpart in the reference.) */
+int bk_cross_clear(bk_env* env, const uint8_t* mask_host);
+/* The same from DEVICE memory written on the env's stream (NULL = every market).  HOLDS NO HOST SYNCHRONISATION: at most
+ * two launches on the env's stream.  (No counterpart in the reference.) */
+int bk_cross_clear_device(bk_env* env, const uint8_t* mask_dev);
+/* Device pointer of the table, bk_cross_row[n_markets][n_spans][assets][assets], for on-device consumers; valid for the env's
+ * life, written on the env's stream.  (No counterpart in the reference.) */
+int bk_cross_device_ptr(bk_env* env, void** out);
+/* Rows of markets [first_market, first_market + n_markets) to host memory, n_markets * n_spans * assets * assets rows.
+ * Waits for the env's stream; does NOT fold.  (No counterpart in the reference.) */
+int bk_get_cross(bk_env* env, uint32_t first_market, uint32_t n_markets, bk_cross_row* out);
+
 /* ------------------------------------------------------ per-book flow table of the trade records */
 /* An opt-in table flow[n_books][8 + 6 K] of u64 words in DEVICE memory, K = n_lags, 1 <= K <= 64: per book the sums over its
  * TRADE RECORDS in record order - the buy share and the size moments, and at lags k = 1 .. K in TRADE time the sums behind

@@ -467,6 +467,41 @@ class ManyEnv {
     if (!mask.empty() && mask.size() != n_books_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per book");
     check(bk_bins_clear(h_, mask.empty() ? nullptr : mask.data()));
   }
+  // per-market cross table of the level-2 history (bk_cross_enable), for an env of markets of `assets` >= 2 books each
+  // (book = market * assets + asset): n_spans * assets * assets rows of integer sums per market, row (j, a, b) the ordered pair
+  // asset a against asset b at span spans[j] - folded on the device from the history ring (needs history_capacity > 0); no
+  // counterpart in the reference
+  void enable_cross(const bk_cross_config& cfg, uint32_t assets) {
+    check(bk_cross_enable(h_, &cfg));
+    cross_markets_ = n_books_ / assets;
+    cross_per_market_ = cfg.n_spans * assets * assets;
+  }
+  bk_cross_config cross_config() {
+    bk_cross_config cfg{};
+    check(bk_cross_config_get(h_, &cfg));
+    return cfg;
+  }
+  // queue the fold of the steps run since the last fold (no host wait); throws, naming the count, if steps were lost
+  void fold_cross() { check(bk_cross_fold(h_)); }
+  // rows [n_markets][n_spans][assets][assets] of markets [first_market, first_market + n_markets) (waits for the env's
+  // stream; does not fold)
+  std::vector<bk_cross_row> cross(uint32_t first_market, uint32_t n_markets) {
+    std::vector<bk_cross_row> rows(static_cast<size_t>(n_markets) * cross_per_market_);
+    check(bk_get_cross(h_, first_market, n_markets, rows.data()));
+    return rows;
+  }
+  std::vector<bk_cross_row> cross() { return cross(0, cross_markets_); }
+  // the table in device memory, bk_cross_row[n_markets][n_spans][assets][assets]
+  bk_cross_row* cross_device_ptr() {
+    void* p = nullptr;
+    check(bk_cross_device_ptr(h_, &p));
+    return static_cast<bk_cross_row*>(p);
+  }
+  // a mask (one byte per MARKET): fold, then clear those markets' rows and carry; an empty mask: clear all without folding
+  void clear_cross(const std::vector<uint8_t>& mask = {}) {
+    if (!mask.empty() && mask.size() != cross_markets_) throw Error(BK_INVALID_ARGUMENT, "the mask needs one byte per market");
+    check(bk_cross_clear(h_, mask.empty() ? nullptr : mask.data()));
+  }
   // open orders of an env with the device ingress (bk_open_orders_enable): per book and trader 0 .. n_traders - 1 a summary
   // row and the `depth` oldest resting orders, recomputed on the device behind every step; the reference has no counterpart
   void enable_open_orders(uint32_t n_traders, uint32_t depth = 8) {
@@ -527,6 +562,7 @@ class ManyEnv {
  private:
   bk_env* h_ = nullptr;
   uint32_t n_books_ = 0, levels_ = 10, n_traders_ = 0, open_traders_ = 0, open_depth_ = 0, bars_window_ = 0, n_lags_ = 0, bins_per_book_ = 0, flow_lags_ = 0;
+  uint32_t cross_markets_ = 0, cross_per_market_ = 0;
 };
 
 // `Agent::update(&mut self, env: &mut Env, rng: &mut R)` (agents/mod.rs:46-55).  The device owns each book's
